@@ -1,6 +1,6 @@
 """Headline benchmark: batched env-steps/s of the PISO hot path + pressure-Poisson roofline.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 (`python bench.py --gpus N` started plainly launches that line itself, as child processes.)
@@ -15,8 +15,12 @@ holds mean / max iterations per solve over the whole timed region, ``warm_start_
 warm-start performance mode next to it.  Scaling is WEAK: every GPU carries 64 envs; one broadcast and one
 all_gather per step by ``ParallelFluidEnv``.
 
-The ONE JSON line printed (``compact_line``, < 4 KB: the driver keeps a tail of stdout) carries the required keys and a
-summary of every leg; the full per-leg / per-kernel tables go to ``profiles/bench_detail.json``:
+A plain run sets up, warms up, times exactly K steps (one region), writes the arrays the last timed step returned when
+``--dump-outputs DIR`` is given, and prints the headline line (``ms_per_step`` = milliseconds of one timed step).  Everything
+else below is measured only with ``--full``, which also times ``--repeats`` regions (default 5) and reports their median.
+
+The ONE JSON line printed (``compact_line``, < 4 KB: the driver keeps a tail of stdout) carries the required keys and, with
+``--full``, a summary of every leg; the full per-leg / per-kernel tables go to ``profiles/bench_detail.json``:
   * ``roofline``: the solver kernel with the largest share of the timed region, timed live with kernel-accurate
     HIP events inside the timed region (fg_profile_*), and the measured STREAM-triad roof;
   * ``poisson_256``: the 256^3 pressure-Poisson micro-benchmark (Jacobi sweep / apply / CG iteration), the
@@ -730,14 +734,68 @@ def write_detail(out, path=None):
             pass
 
 
+DUMP_LIMIT = 60 << 20   # bytes of the arrays of --dump-outputs together (with the .npy headers: below 64 MB)
+
+
+def step_arrays(result):
+    """{name: float32 / float64 array} of what one ``ParallelFluidEnv.step`` returned to its caller: every observation, the
+    rewards, the per-env terminated / truncated flags (as 0 / 1) and every numeric entry of the per-env info dicts, stacked over envs."""
+    import numpy as np
+    import torch
+
+    def arr(v):
+        if isinstance(v, torch.Tensor):
+            v = v.detach().cpu()
+            return v.double().numpy() if v.dtype == torch.float64 else v.float().numpy()
+        a = np.asarray(v)
+        if a.dtype.kind not in "biuf":
+            return None
+        return a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+
+    obs, reward, terminated, truncated, infos = result
+    out = {"obs_" + k: arr(v) for k, v in obs.items()}
+    out["reward"], out["terminated"], out["truncated"] = arr(reward), arr(terminated), arr(truncated)
+    for k in infos[0]:
+        rows = [arr(d[k]) for d in infos]
+        if all(r is not None and r.shape == rows[0].shape for r in rows):
+            out["info_" + k] = np.stack(rows)
+    return {"".join(c if c.isalnum() or c in "_-." else "_" for c in k): a for k, a in out.items() if a is not None}
+
+
+def write_outputs(directory, arrays, limit=DUMP_LIMIT):
+    """``directory/<name>.npy`` for every array.  Past ``limit`` bytes in all, the largest arrays are replaced by a fixed, seeded
+    sample of their elements (``<name>.npy``, flattened) and the flat indices it took (``<name>_index.npy``)."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    left = limit
+    names = sorted(arrays, key=lambda k: arrays[k].nbytes)
+    for i, name in enumerate(names):
+        a = arrays[name]
+        share = left // (len(names) - i)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=max(1, share // (a.itemsize + 8)), replace=False))
+            np.save(os.path.join(directory, name + "_index.npy"), idx.astype(np.float64))
+            left -= idx.size * 8
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(directory, name + ".npy"), a)
+        left -= a.nbytes
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=5,
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the live per-kernel roofline, the STREAM triad, the 256^3 Poisson "
+                         "micro-benchmark, the extra legs, the CPU baseline, the sharded cylinder run (N > 1), the detail file and --repeats regions")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (observations, rewards, flags, info) as DIR/<name>.npy")
+    ap.add_argument("--repeats", type=int, default=None,
                     help="the timed region of --steps steps is run this many times back to back (each bracketed by its own fence); the line "
-                         "reports the MEDIAN region and the spread (boxes and runs differ by a few per cent: VERDICT r5, bench method)")
+                         "reports the MEDIAN region and the spread (boxes and runs differ by a few per cent: VERDICT r5, bench method). "
+                         "Default 1, with --full 5")
     ap.add_argument("--envs-per-gpu", type=int, default=ENVS_PER_GPU)
     ap.add_argument("--env-id", default=ENV_ID)
     ap.add_argument("--lanes", type=int, default=LANES,
@@ -832,7 +890,8 @@ def main():
     solver = solvers[0]
     for sv in solvers:
         sv.solver_counters(reset=True)
-        sv.profile_enable(True)
+        if args.full:      # (the live per-kernel timing behind `roofline`)
+            sv.profile_enable(True)
 
     def fence():
         torch.cuda.synchronize(device)
@@ -840,22 +899,38 @@ def main():
             dist.barrier()
         torch.cuda.synchronize(device)
 
+    def new_episode(seed):
+        penv.reset(seed=seed, randomize=True)
+        for _ in range(args.warmup):
+            one_step()
+
     penv.time_shards = world > 1      # per-rank time of the shard's own step (one sync per step, in front of the all_gather that waits anyway)
     penv.shard_seconds = 0.0
     regions = []
-    n_rep = max(1, args.repeats)
+    n_rep = max(1, args.repeats if args.repeats is not None else (5 if args.full else 1))
+    n_inner = 0
+    last = None
     for k_rep in range(n_rep):
         if env._n_steps + args.steps > env.episode_length:
             # an episode is 80 env steps: a region never straddles its end -- a new episode (and its warm-up) starts outside the timed region
-            penv.reset(seed=1234 + k_rep, randomize=True)
-            for _ in range(args.warmup):
-                one_step()
-        fence()
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            one_step()
-        fence()
-        regions.append(time.perf_counter() - t0)
+            new_episode(1234 + k_rep)
+        region, left = 0.0, args.steps
+        while left > 0:
+            if env._n_steps >= env.episode_length:
+                # --steps longer than an episode: the clock stops at its end, and the next episode and its warm-up start outside it
+                n_inner += 1
+                new_episode(1234 + n_rep + n_inner)
+            chunk = min(left, env.episode_length - env._n_steps)
+            fence()
+            t0 = time.perf_counter()
+            for _ in range(chunk):
+                last = one_step()
+            fence()
+            region += time.perf_counter() - t0
+            left -= chunk
+        regions.append(region)
+    if args.dump_outputs and penv.is_driver:
+        write_outputs(args.dump_outputs, step_arrays(last))
     per_rank = None
     if world > 1:
         t = torch.tensor(regions, dtype=torch.float64, device=coll_device)
@@ -875,18 +950,21 @@ def main():
         per_rank = {"shard_ms_per_step": [round(v, 3) for v in ms], "min_ms": round(min(ms), 3), "max_ms": round(max(ms), 3),
                     "imbalance": round(max(ms) / max(min(ms), 1e-9), 3),
                     "mean_substeps_per_sim_step": [round(r[1] / max(args.steps * n_rep * env._n_sim_steps, 1), 2) for r in allr]}
-    prof = merge_profiles([sv.profile_read() for sv in solvers])
-    for sv in solvers:
-        sv.profile_enable(False)
+    prof = {}
+    if args.full:
+        prof = merge_profiles([sv.profile_read() for sv in solvers])
+        for sv in solvers:
+            sv.profile_enable(False)
     its = merge_iterations([solver_iterations(sv) for sv in solvers])      # (piso_steps: summed over the lanes)
     n_lanes = len(solvers)
     n_sim = env._n_sim_steps
 
     grid_desc = [solver.nx, solver.ny, solver.nz] if single_block else {"cells_per_env": int(solver.n_cells), "blocks": len(solver.blocks)}
+    micro = args.full and not args.no_micro
     if rank == 0:
         roof = roofline_from_profile(prof, solver) if single_block else None
         triad = None
-        if not args.no_micro:
+        if micro:
             try:
                 triad = stream_triad(device)
             except Exception as exc:
@@ -932,18 +1010,18 @@ def main():
                        "solver_iterations": its, "capped_solves": capped_solves(its),
                        "floor_released_solves": sum(int((solver_switches(sv) or {}).get("jacobi_floor_released") or 0) for sv in solvers) if single_block else None,
                        "iters_are": "iterations per solve (counts; 0 = initial residual met the tolerance)",
-                       "launches_per_piso_step": launches_per_piso_step(prof, its) if single_block else None,
-                       "solver_kernels_GBps": step_gbps(prof, total_elapsed) if single_block else None,
-                       "whole_step_GBps_model": whole_step_gbps_model(prof, total_elapsed, its, solver) if single_block else None,
+                       "launches_per_piso_step": launches_per_piso_step(prof, its) if single_block and prof else None,
+                       "solver_kernels_GBps": step_gbps(prof, total_elapsed) if single_block and prof else None,
+                       "whole_step_GBps_model": whole_step_gbps_model(prof, total_elapsed, its, solver) if single_block and prof else None,
                        "mean_substeps_per_sim_step": round(its["piso_steps"] / n_lanes / max(args.steps * n_rep * n_sim, 1), 2),
                        "per_rank": per_rank, "switches": solver_switches(solver)},
             "roofline": roof,
             "legs": {},
         }
-        if not args.no_micro:
+        if micro:
             out["poisson_256"] = poisson_micro(device)
     penv.close()
-    if world > 1:
+    if world > 1 and args.full:
         # the multi-GPU run also times the env the 7x scaling target names (every rank takes part; rank 0 prints it in the same line)
         try:
             cyl = cylinder_sharded(world, rank, device, coll_device, args.share_gpu, envs_per_gpu=args.envs_per_gpu)
@@ -954,7 +1032,7 @@ def main():
     if rank == 0:
         out["config"]["collective_backend"] = dist.get_backend() if dist.is_initialized() else None
         out["config"]["collective_world_size"] = dist.get_world_size() if dist.is_initialized() else 1
-    if rank == 0 and world == 1 and not args.no_micro:
+    if rank == 0 and world == 1 and micro:
         t_legs = time.perf_counter()
 
         def leg(name, fn, *a, **kw):
@@ -1011,10 +1089,11 @@ def main():
     if rank == 0:
         q = out["legs"].get("quiescent_mode")
         out["value_unforced"] = q.get("value") if isinstance(q, dict) else None     # the same workload without the body force
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline()
-        write_detail(out)
-        print(compact_line(out), flush=True)
+        if args.full:
+            write_detail(out)
+        print(compact_line(out, DETAIL_PATH if args.full else None), flush=True)
     if world > 1 and dist.is_initialized():
         dist.destroy_process_group()
 

@@ -1,7 +1,7 @@
 #!/bin/bash
 # The headline (64 envs on one GPU) as 1, 2 and 4 lanes (ParallelFluidEnv(lanes=L): sub-batches stepped concurrently on their own HIP
 # streams), same box, same command otherwise.  bash profiles/headline_lanes.sh
-F="--steps 20 --warmup 5 --no-cpu-baseline --no-micro --no-airfoil-leg --leg-budget 0"
+F="--full --steps 20 --warmup 5 --no-cpu-baseline --no-micro --no-airfoil-leg --leg-budget 0"
 for L in 1 2 4 2 1; do
   python bench.py $F --lanes $L 2>/tmp/err_$L.txt | python -c "
 import json,sys

@@ -1,4 +1,4 @@
-run() { python bench.py --no-cpu-baseline --no-micro --steps 10 --warmup 3 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$1', d['value'], d['roofline']['avg_launch_us'], d['config']['iters_per_solve[mean,max]']['velocity'])"; }
+run() { python bench.py --full --no-cpu-baseline --no-micro --steps 10 --warmup 3 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$1', d['value'], d['roofline']['avg_launch_us'], d['config']['iters_per_solve[mean,max]']['velocity'])"; }
 for i in 1 2; do
 FG_JAC_SHAPE=1 run rows_S6
 FG_JAC_SHAPE=2 run bands_S8
