@@ -615,7 +615,8 @@ static int max_iters(const fg_solve_info* info, int n) {
 // One advection-diffusion solve under the handle's preconditioner policy (fg_set_advection_preconditioner), the single-block
 // form of the reference's retry chain (_linear_solve, PISOtorch_diff.py:449-476): mode 1 preconditions every solve
 // (preconditionBiCG), mode 2 repeats a solve that ended unconverged or non-finite from zero WITH the preconditioner
-// (BiCG_precondition_fallback) -- the reference's preconditioner is cuSPARSE ILU(0), here the y-line solve of fg_linepre.hip.
+// (BiCG_precondition_fallback) -- the reference's preconditioner is cuSPARSE ILU(0), here the y-line solve of fg_linepre.hip;
+// modes 4 / 5 are the same two rules with ILU(0) itself (fg_ilu0.hip), the only preconditioner of the fp64 build.
 static int advection_solve(fg_state* s, FgBicgArgs a, fg_solve_info* info, hipStream_t st, int for_scalar, int channel) {
     a.precond = (s->adv_precond == 1) ? 1 : (s->adv_precond == 3 ? 2 : (s->adv_precond == 4 ? 3 : 0));
     if (a.precond == 2 && !for_scalar && s->visc_field) a.precond = 0;   // the Helmholtz operator is built for ONE viscosity

@@ -1,7 +1,8 @@
 // fp64 build (libfluidgym_hip_f64.so, -DFG_REAL_DOUBLE) only: the kernels that exist in fp32 form alone -- the fast-diagonalisation
-// preconditioner's MFMA basis changes and LDS FFT (its operator itself runs in doubles since round 6: fg_f64_fd.hip), the z-marching 3-D Poisson kernels, the y-line preconditioner -- are not
-// instantiated for double.  The core translation units call them through these definitions: "not available", and the callers fall
-// back to the generic kernels (plain CG, generic stencil kernels, unpreconditioned BiCGStab).
+// preconditioner's MFMA basis changes and LDS FFT (its operator itself runs in doubles since round 6: fg_f64_fd.hip), the z-marching 3-D Poisson kernels, the y-line and
+// Helmholtz preconditioners -- are not instantiated for double.  The core translation units call them through these definitions: "not
+// available", and the callers fall back to the generic kernels (plain CG, generic stencil kernels; the advection-diffusion rungs of
+// this build are preconditioned by ILU(0), fg_ilu0.hip, modes 4 / 5 of fg_set_advection_preconditioner).
 #include "fg_internal.h"
 
 #if !FG_F64
@@ -22,9 +23,7 @@ int fg_line_alloc(fg_state*) {
     return FG_ERR_UNSUPPORTED;
 }
 int fg_helm_alloc(fg_state*) { return FG_ERR_UNSUPPORTED; }
-int fg_ilu_alloc(fg_state*) { fg_set_error("the ILU(0) preconditioner is not part of the fp64 build"); return FG_ERR_UNSUPPORTED; }
-int fg_ilu_factor(fg_state*, const fg_real*, const fg_real*, hipStream_t) { return FG_ERR_UNSUPPORTED; }
-int fg_ilu_apply(fg_state*, const fg_real*, const fg_real*, int, const fg_real*, fg_real*, hipStream_t) { return FG_ERR_UNSUPPORTED; }
+// (fg_ilu_*: fg_ilu0.hip -- ILU(0) runs in doubles, the preconditioner of the fp64 build's advection-diffusion rungs)
 int fg_helm_factor(fg_state*, const fg_real*, fg_real, int, int, int, hipStream_t, int) { return FG_ERR_UNSUPPORTED; }
 int fg_fd_helmholtz_apply(fg_state*, int, const fg_real*, fg_real*, hipStream_t) { return FG_ERR_UNSUPPORTED; }
 int fg_line_factor(fg_state*, const fg_real*, const fg_real*, int, hipStream_t) { return FG_ERR_UNSUPPORTED; }

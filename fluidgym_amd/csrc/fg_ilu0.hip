@@ -13,6 +13,13 @@
 // them: a sequential algorithm, ~1 us per hyperplane, i.e. 0.5 - 1 ms per application on the bench grids against 60 us for a whole
 // plain iteration.  It is here because the reference's rung is THIS preconditioner (tests/test_gpu_ilu0.py holds it against a generic
 // CSR ILU(0) in NumPy); the y-line solve of fg_linepre.hip stays the default of the rung (fg_set_advection_preconditioner).
+//
+// The file is written on fg_real and compiled into both libraries.  In the fp64 build (-DFG_REAL_DOUBLE) it is the ONLY
+// preconditioner of the advection-diffusion rungs -- the reference's cusparseDcsrilu02 path for double fields -- and Simulation maps
+// preconditionBiCG / BiCG_precondition_fallback onto modes 4 / 5 there (tests/test_gpu_f64_ilu0.py).  In double the three sweeps
+// keep the 1024-thread workgroup: 22-28 VGPRs, no scratch (fp32: 19-20).  Measured on the bench grid (256 x 128, 64 envs, two
+// components; kernel trace): forward + backward sweep 1.38 ms per application in fp64 against 1.33 ms in fp32, factorisation 0.76 /
+// 0.64 ms -- the sweeps are bound by the hyperplane barriers (~1.9 us each), not by the width of the values.
 #include "fg_internal.h"
 
 namespace {
@@ -34,26 +41,26 @@ __device__ __forceinline__ int ilu_nbr(const IluGeo& g, int i, int j, int k, int
 
 // MODE 0: modified diagonal; 1: forward (unit lower) sweep out = L^-1 in; 2: backward sweep out = U^-1 out (in place)
 template <int MODE>
-__device__ __forceinline__ void ilu_cell(const IluGeo& g, int i, int j, int k, const float* __restrict__ diag, const float* __restrict__ off,
-                                         const float* __restrict__ dmod, float* __restrict__ dmod_out, const float* __restrict__ in,
-                                         float* __restrict__ out) {
+__device__ __forceinline__ void ilu_cell(const IluGeo& g, int i, int j, int k, const fg_real* __restrict__ diag, const fg_real* __restrict__ off,
+                                         const fg_real* __restrict__ dmod, fg_real* __restrict__ dmod_out, const fg_real* __restrict__ in,
+                                         fg_real* __restrict__ out) {
     const int c = i + g.nx * (j + g.ny * k), F = 2 * g.dims;
     if (MODE == 0) {
-        float d = diag[c];
+        fg_real d = diag[c];
         for (int f = 0; f < F; ++f) {
             const int n = ilu_nbr(g, i, j, k, f);
             if (n >= 0 && n < c) d -= off[(size_t)f * g.n + c] * off[(size_t)(f ^ 1) * g.n + n] / dmod_out[n];
         }
         dmod_out[c] = d;
     } else if (MODE == 1) {
-        float y = in[c];
+        fg_real y = in[c];
         for (int f = 0; f < F; ++f) {
             const int n = ilu_nbr(g, i, j, k, f);
             if (n >= 0 && n < c) y -= off[(size_t)f * g.n + c] / dmod[n] * out[n];
         }
         out[c] = y;
     } else {
-        float z = out[c];
+        fg_real z = out[c];
         for (int f = 0; f < F; ++f) {
             const int n = ilu_nbr(g, i, j, k, f);
             if (n >= 0 && n > c) z -= off[(size_t)f * g.n + c] * out[n];
@@ -64,16 +71,16 @@ __device__ __forceinline__ void ilu_cell(const IluGeo& g, int i, int j, int k, c
 
 // hyperplane sweep; grid = (systems per env, B).  MODE 0 runs with one system per env (the matrix belongs to the env).
 template <int MODE>
-__global__ __launch_bounds__(1024) void k_ilu0(IluGeo g, int nc, const float* __restrict__ diag, const float* __restrict__ off,
-                                               float* __restrict__ dmod, const float* __restrict__ in, float* __restrict__ out,
+__global__ __launch_bounds__(1024) void k_ilu0(IluGeo g, int nc, const fg_real* __restrict__ diag, const fg_real* __restrict__ off,
+                                               fg_real* __restrict__ dmod, const fg_real* __restrict__ in, fg_real* __restrict__ out,
                                                const int32_t* __restrict__ flags) {
     const int b = blockIdx.y, comp = blockIdx.x, sys = b * nc + comp;
     if (MODE != 0 && flags && flags[sys] != 0) return;
-    const float* dg = diag + (size_t)b * g.n;
-    const float* of = off + (size_t)b * 2 * g.dims * g.n;
-    float* dm = dmod + (size_t)b * g.n;
-    const float* src = MODE == 1 ? in + (size_t)sys * g.n : nullptr;
-    float* dst = MODE == 0 ? nullptr : out + (size_t)sys * g.n;
+    const fg_real* dg = diag + (size_t)b * g.n;
+    const fg_real* of = off + (size_t)b * 2 * g.dims * g.n;
+    fg_real* dm = dmod + (size_t)b * g.n;
+    const fg_real* src = MODE == 1 ? in + (size_t)sys * g.n : nullptr;
+    fg_real* dst = MODE == 0 ? nullptr : out + (size_t)sys * g.n;
     const int planes = g.nx + g.ny + g.nz - 2, jk = g.ny * g.nz;
     for (int step = 0; step < planes; ++step) {
         const int L = (MODE == 2) ? planes - 1 - step : step;
@@ -101,20 +108,20 @@ int fg_ilu_alloc(fg_state* s) {
         const int ext = a == 0 ? G.nx : (a == 1 ? G.ny : G.nz);
         if (ext < 4) { fg_set_error("ILU(0) preconditioner: every axis needs at least four cells (closed form of the factorisation)"); return FG_ERR_UNSUPPORTED; }
     }
-    FG_HIP_CHECK(hipMalloc(&s->ilu_d, sizeof(float) * (size_t)G.B * G.n));
+    FG_HIP_CHECK(hipMalloc(&s->ilu_d, sizeof(fg_real) * (size_t)G.B * G.n));
     return FG_OK;
 }
 
 // modified diagonal of every env's matrix (once per solve: the matrix is the solve's)
-int fg_ilu_factor(fg_state* s, const float* diag, const float* off, hipStream_t st) {
-    hipLaunchKernelGGL(k_ilu0<0>, dim3(1, s->grid.B), dim3(1024), 0, st, geo_of(s), 1, diag, off, s->ilu_d, (const float*)nullptr,
-                       (float*)nullptr, (const int32_t*)nullptr);
+int fg_ilu_factor(fg_state* s, const fg_real* diag, const fg_real* off, hipStream_t st) {
+    hipLaunchKernelGGL(k_ilu0<0>, dim3(1, s->grid.B), dim3(1024), 0, st, geo_of(s), 1, diag, off, s->ilu_d, (const fg_real*)nullptr,
+                       (fg_real*)nullptr, (const int32_t*)nullptr);
     FG_HIP_CHECK(hipGetLastError());
     return FG_OK;
 }
 
 // z = U^-1 L^-1 r for the nc systems of every env (systems whose flag is set are skipped)
-int fg_ilu_apply(fg_state* s, const float* diag, const float* off, int nc, const float* r, float* z, hipStream_t st) {
+int fg_ilu_apply(fg_state* s, const fg_real* diag, const fg_real* off, int nc, const fg_real* r, fg_real* z, hipStream_t st) {
     const IluGeo g = geo_of(s);
     hipLaunchKernelGGL(k_ilu0<1>, dim3(nc, s->grid.B), dim3(1024), 0, st, g, nc, diag, off, s->ilu_d, r, z, (const int32_t*)s->flags);
     hipLaunchKernelGGL(k_ilu0<2>, dim3(nc, s->grid.B), dim3(1024), 0, st, g, nc, diag, off, s->ilu_d, r, z, (const int32_t*)s->flags);

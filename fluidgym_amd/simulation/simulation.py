@@ -141,7 +141,7 @@ class Simulation:
         domain.solver.set_advection_start((not non_orthogonal) or self.advection_warm_start)
         # The reference's retry chain of the advection-diffusion solves (_linear_solve, PISOtorch_diff.py:449-476) on this path:
         # preconditionBiCG preconditions every solve, BiCG_precondition_fallback repeats a failed one with the preconditioner
-        # (cuSPARSE ILU(0) there, the y-line solve of csrc/fg_linepre.hip here).  On top of that the policy switch
+        # (cuSPARSE ILU(0) there, the y-line solve of csrc/fg_linepre.hip here; ILU(0) itself in the fp64 build).  On top of that the policy switch
         # advection_line_preconditioner (policy.py, default OFF) preconditions every solve on grids refined towards a y wall, where
         # the plain recurrence needs 20-35 iterations (RBC 512 x 128): same system, same tolerance, another Krylov trajectory.
         # solver_double_fallback (PISOtorch_diff.py:418-445): a solve that failed in fp32 is repeated in fp64 on the same matrix and
@@ -160,6 +160,15 @@ class Simulation:
             # policy advection_rung_preconditioner = "ilu0": the rungs use the reference's own preconditioner (ILU(0), modes 4 / 5)
             if get_solver_policy()["advection_rung_preconditioner"] == "ilu0" and min(len(w) for w in solver.widths[:solver.dims]) >= 4 and not refined:
                 self.advection_preconditioner = {1: 4, 2: 5}.get(self.advection_preconditioner, self.advection_preconditioner)
+            # fp64 build (solver.f64): ILU(0) is the one preconditioner it carries in doubles (csrc/fg_ilu0.hip) -- the reference's own
+            # for double fields (cusparseDcsrilu02) -- so the rungs are modes 4 / 5 there, whatever the policy says
+            if getattr(solver, "f64", False) and self.advection_preconditioner in (1, 2):
+                short = [a for a in range(solver.dims) if len(solver.widths[a]) < 4]
+                if short:
+                    raise ValueError(f"dtype=float64: preconditionBiCG / BiCG_precondition_fallback run ILU(0) (the only preconditioner of "
+                                     f"the fp64 build), which needs at least four cells on every axis; axis {short[0]} has "
+                                     f"{len(solver.widths[short[0]])} -- pass preconditionBiCG=False, BiCG_precondition_fallback=False")
+                self.advection_preconditioner += 3
             # policy advection_fd_preconditioner (default on): where the grid allows it -- periodic, uniform x (and z), walls in y:
             # the RBC and TCF families -- every advection-diffusion solve is right-preconditioned by the exact inverse of its
             # diffusion part (separable Helmholtz operator, fast diagonalisation).  2-D only by default: in 3-D the four basis
