@@ -30,6 +30,15 @@ FG_BOUND_VELOCITY, FG_BOUND_SCALAR = 8, 16
 FG_SOLVER_CG, FG_SOLVER_JACOBI, FG_SOLVER_RBGS, FG_SOLVER_MGCG, FG_SOLVER_FDCG = 0, 1, 2, 3, 4
 (FG_BUF_A, FG_BUF_C_OFF, FG_BUF_ADV_RHS, FG_BUF_VEL_RESULT, FG_BUF_H, FG_BUF_DIV, FG_BUF_P_RESULT,
  FG_BUF_SCALAR_RESULT) = range(8)
+FG_ERR_UNSUPPORTED = -4
+# forms_out of the debug preconditioner entries (include/fluidgym_hip.h FG_FORM_*): slots, then the codes per slot
+FG_FORM_SLOTS = 8
+FG_FORM_SLOT_X, FG_FORM_SLOT_Z, FG_FORM_SLOT_TRIDIAG, FG_FORM_SLOT_FACTORS, FG_FORM_SLOT_HELM, FG_FORM_SLOT_LINE = range(6)
+(FG_FORM_GEMM_SPLITK, FG_FORM_GEMM_T64, FG_FORM_GEMM_T128, FG_FORM_GEMM_Z64, FG_FORM_DCT, FG_FORM_FFT, FG_FORM_F64) = range(1, 8)
+(FG_FORM_TRI_STREAM, FG_FORM_TRI_LDS3, FG_FORM_TRI_LDS2, FG_FORM_TRI_LDS3_FAC, FG_FORM_TRI_LDS2_FAC, FG_FORM_TRI_F64) = range(1, 7)
+FG_FORM_FAC_GRID, FG_FORM_FAC_ROWMEAN, FG_FORM_FAC_MADE = 1, 2, 3
+FG_FORM_HELM_ARRAY, FG_FORM_HELM_ROW32, FG_FORM_HELM_ROW64 = 1, 2, 3
+FG_FORM_LINE_LDS, FG_FORM_LINE_STREAM = 1, 2
 
 
 class FgConfig(Structure):
@@ -231,7 +240,9 @@ SIGNATURES = {
     "fg_solver_unconverged": (c_int, [c_void_p, POINTER(c_int64)]),
     "fg_mb_solver_counters": (c_int, [c_void_p, POINTER(c_int64), c_int32]),
     "fg_set_advection_preconditioner": (c_int, [c_void_p, c_int]),
-    "fg_debug_apply_preconditioner": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "fg_debug_apply_preconditioner": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, POINTER(c_int32), c_void_p]),
+    "fg_debug_apply_pressure_preconditioner": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, POINTER(ctypes.c_double),
+                                                       POINTER(c_int32), c_void_p]),
     "fg_sgs_smagorinsky": (c_int, [c_void_p, c_float, c_void_p, c_void_p]),
     "fg_set_fd_helmholtz": (c_int, [c_void_p, POINTER(c_float)]),
     "fg_advection_retries": (c_int, [c_void_p, POINTER(c_int64), c_int32]),

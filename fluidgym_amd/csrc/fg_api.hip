@@ -239,6 +239,11 @@ extern "C" int fg_set_fd_preconditioner(fg_handle s, const float* Qx, const floa
     // (the arrays are floats in both builds: the fp64 library's plain kernels promote them on load, fg_f64_fd.hip)
     FG_REQUIRE(s->grid.fixed[2] && s->grid.fixed[3], FG_ERR_UNSUPPORTED, "FD preconditioner needs FIXED y faces");
     FG_REQUIRE(s->grid.dims == 2 || (Qz && QzT), FG_ERR_INVALID_ARG, "Qz required in 3-D");
+#if !FG_F64
+    // beyond 320 rows every grid takes the streaming tridiagonal kernel (fg_fd_tridiag), whose y buffer of roundup(ny, 64) x 64 floats
+    // fits the 160 KB of LDS up to 640 rows: refuse here, where the caller can pick another solver, not inside a solve
+    FG_REQUIRE(s->grid.ny <= 640, FG_ERR_UNSUPPORTED, "FD preconditioner: at most 640 cells along y (LDS of the tridiagonal solve)");
+#endif
     const size_t nx = s->grid.nx, ny = s->grid.ny, nz = s->grid.nz;
     auto up = [&](float** dst, const float* src, size_t count) -> hipError_t {
         if (*dst) (void)hipFree(*dst);
@@ -324,13 +329,32 @@ extern "C" int fg_ladder(fg_handle s, int64_t* out4, int32_t force_mask) {
     if (force_mask >= 0) s->ladder_force = force_mask;
     return FG_OK;
 }
-extern "C" int fg_debug_apply_preconditioner(fg_handle s, int mode, int nc, const fg_real* r, fg_real* z, void* stream) {
-    FG_REQUIRE(s && r && z && nc >= 1 && nc <= s->grid.dims && (mode == 1 || mode == 4), FG_ERR_INVALID_ARG,
-               "fg_debug_apply_preconditioner: mode 1 (y-line) or 4 (ILU(0)), 1 <= nc <= dims");
+namespace {
+// forms_rec of the test entries: the dispatchers fill it while the entry runs, forms_out receives it on every way out
+struct FormsRecord {
+    fg_state* s; int32_t* out; int32_t rec[FG_FORM_SLOTS] = {0};
+    FormsRecord(fg_state* st, int32_t* o) : s(st), out(o) { s->forms_rec = rec; }
+    ~FormsRecord() {
+        s->forms_rec = nullptr;
+        if (out) memcpy(out, rec, sizeof(rec));
+    }
+};
+}  // namespace
+
+extern "C" int fg_debug_apply_preconditioner(fg_handle s, int mode, int nc, const fg_real* r, fg_real* z, int32_t* forms_out, void* stream) {
+    FG_REQUIRE(s && r && z && nc >= 1 && nc <= s->grid.dims && (mode == 1 || mode == 3 || mode == 4), FG_ERR_INVALID_ARG,
+               "fg_debug_apply_preconditioner: mode 1 (y-line), 3 (Helmholtz) or 4 (ILU(0)), 1 <= nc <= dims");
     hipStream_t st = (hipStream_t)stream;
+    FormsRecord forms(s, forms_out);
     s->bicg_ready_nc = 0; s->cg_ready_ns = 0;
     FG_HIP_CHECK(hipMemsetAsync(s->flags, 0, sizeof(int32_t) * (size_t)s->grid.B * s->grid.dims, st));
-    if (mode == 4) {
+    if (mode == 3) {
+        // the velocity system's operator (both y walls prescribed), factorised and applied as the Helmholtz-preconditioned BiCGStab does
+        FG_REQUIRE(s->fd_lam != nullptr, FG_ERR_UNSUPPORTED, "fg_debug_apply_preconditioner: mode 3 needs fg_set_fd_helmholtz (fp32 build)");
+        FG_REQUIRE(s->adv_last_dt != nullptr, FG_ERR_INVALID_ARG, "fg_debug_apply_preconditioner: mode 3 needs a velocity fg_setup_advection first");
+        if (int rc = fg_helm_factor(s, s->adv_last_dt, s->viscosity, 1, 1, nc, st)) return rc;
+        if (int rc = fg_fd_helmholtz_apply(s, nc, r, z, st)) return rc;
+    } else if (mode == 4) {
         if (int rc = fg_ilu_alloc(s)) return rc;
         if (int rc = fg_ilu_factor(s, s->A, s->Coff, st)) return rc;
         if (int rc = fg_ilu_apply(s, s->A, s->Coff, nc, r, z, st)) return rc;
@@ -341,6 +365,59 @@ extern "C" int fg_debug_apply_preconditioner(fg_handle s, int mode, int nc, cons
     }
     FG_HIP_CHECK(hipStreamSynchronize(st));
     return FG_OK;
+}
+
+extern "C" int fg_debug_apply_pressure_preconditioner(fg_handle s, int form, const fg_real* rA, const fg_real* r, fg_real* z, double* rz_out,
+                                                      int32_t* forms_out, void* stream) {
+    FG_REQUIRE(s && r && z && form >= 0 && form <= 2, FG_ERR_INVALID_ARG, "fg_debug_apply_pressure_preconditioner: form 0, 1 or 2");
+    FG_REQUIRE(s->fd_Qx && s->fd_inv, FG_ERR_INVALID_ARG, "fg_debug_apply_pressure_preconditioner: fg_set_fd_preconditioner was not called");
+#if FG_F64
+    FG_REQUIRE(form == 0, FG_ERR_UNSUPPORTED, "fg_debug_apply_pressure_preconditioner: the row-mean operator (forms 1, 2) is not part of the fp64 build");
+#else
+    if (form >= 1)
+        FG_REQUIRE(fg_fd_rowmean_ok(s), FG_ERR_UNSUPPORTED,
+                   "fg_debug_apply_pressure_preconditioner: the row-mean operator needs a 2-D grid, a fast x transform, nx % 64 == 0 and ny <= 320");
+    if (form == 1) FG_REQUIRE(rA != nullptr, FG_ERR_INVALID_ARG, "fg_debug_apply_pressure_preconditioner: form 1 needs rA");
+    if (form == 2) {
+        FG_REQUIRE(fg_fd_tridiag_can_factor(s), FG_ERR_UNSUPPORTED,
+                   "fg_debug_apply_pressure_preconditioner: form 2 needs the factoring tridiagonal launch (LDS for ny, FG_FD_FACFUSE=1)");
+        FG_REQUIRE(rA == nullptr && s->fd_row_part && s->fd_row_part_epoch == s->rA_epoch, FG_ERR_INVALID_ARG,
+                   "fg_debug_apply_pressure_preconditioner: form 2 reads the row sums of the last velocity fg_setup_advection (rA = nullptr)");
+    }
+#endif
+    hipStream_t st = (hipStream_t)stream;
+    const int B = s->grid.B;
+    FormsRecord forms(s, forms_out);
+    s->bicg_ready_nc = 0; s->cg_ready_ns = 0;
+    FG_HIP_CHECK(hipMemsetAsync(s->flags, 0, sizeof(int32_t) * (size_t)B * s->grid.dims, st));
+    FgDacc* acc = nullptr;
+    if (rz_out) {
+        FG_HIP_CHECK(hipMalloc(&acc, sizeof(FgDacc) * (size_t)B));
+        FG_HIP_CHECK(hipMemsetAsync(acc, 0, sizeof(FgDacc) * (size_t)B, st));
+    }
+    int rc = FG_OK;
+    if (form == 0) {
+        rc = fg_fd_apply(s, r, z, acc, 1, 1, B, st);
+    } else {
+#if !FG_F64
+        // the fused CG's application (fg_poisson.hip): forward transform, tridiagonal solve with the row-mean factors, inverse transform
+        float* t1 = s->w[3];
+        if (form == 1) rc = fg_fd_rowmean_factor(s, rA, nullptr, st, nullptr, 0);
+        if (rc == FG_OK) rc = fg_fd_dct_forward(s, r, t1, st, 0, nullptr);
+        if (rc == FG_OK) rc = fg_fd_tridiag(s, t1, st, nullptr, true, form == 2 ? s->fd_row_part : nullptr, nullptr);
+        if (rc == FG_OK) rc = fg_fd_dct_inverse(s, t1, z, r, acc, 1, 1, st, 0);
+        s->fd_row_epoch = -1;      // these factors belong to no 1/A the solvers know: their next solve makes its own
+#endif
+    }
+    if (rc == FG_OK && hipStreamSynchronize(st) != hipSuccess) rc = FG_ERR_HIP;
+    if (rc == FG_OK && acc) {
+        std::vector<FgDacc> host((size_t)B);
+        if (hipMemcpy(host.data(), acc, sizeof(FgDacc) * (size_t)B, hipMemcpyDeviceToHost) != hipSuccess) rc = FG_ERR_HIP;
+        else
+            for (int b = 0; b < B; ++b) rz_out[b] = fg_dacc_host_value(host[b]);
+    }
+    if (acc) (void)hipFree(acc);
+    return rc;
 }
 extern "C" int fg_sgs_smagorinsky(fg_handle s, fg_real coefficient, fg_real* out_BN, void* stream) {
     FG_REQUIRE(s && out_BN, FG_ERR_INVALID_ARG, "fg_sgs_smagorinsky: null argument");
@@ -448,6 +525,7 @@ static int setup_advection(fg_handle s, const fg_real* dt_B, int for_scalar, int
         a.visc = s->visc_field;
         a.nu = s->viscosity;
         a.rA = s->rA;
+        s->adv_last_dt = dt_B;
         s->rA_epoch++;
         s->jac_rA_epoch = s->rA_epoch;      // (rA = 1 / A of THIS velocity matrix: what the streaming Jacobi sweeps read, fg_jacobi.hip)
 #if !FG_F64

@@ -116,6 +116,12 @@ int fg_fd_apply(fg_state* s, const fg_real* r, fg_real* z, FgDacc* rz_acc, int r
     double* t1 = s->w[3];
     double* t2 = s->w[4];
     if (judge && judge->acc) hipLaunchKernelGGL(k64_fd_judge, dim3(B), dim3(64), 0, st, *judge, B);
+    if (s->forms_rec) {
+        s->forms_rec[FG_FORM_SLOT_X] = FG_FORM_F64;
+        s->forms_rec[FG_FORM_SLOT_Z] = G.dims == 3 ? FG_FORM_F64 : 0;
+        s->forms_rec[FG_FORM_SLOT_TRIDIAG] = FG_FORM_TRI_F64;
+        s->forms_rec[FG_FORM_SLOT_FACTORS] = FG_FORM_FAC_GRID;
+    }
     const int rows = ny * nz;
     const dim3 rgrid((rows + RT - 1) / RT, B);
     const size_t lds = (size_t)RT * nx * sizeof(double);

@@ -241,6 +241,7 @@ int fg_fd_dct_forward(fg_state* s, const float* r, float* out, hipStream_t st, i
     if (judge) a.judge = *judge;
     // per env: the row read + written; ~5 n log2 n flops per row
     const int slot = fg_prof_slot(s, FG_PK_DCT, s->flags, batch, 8.0 * G.n, 5.0 * G.n * log2((double)G.nx), st);
+    if (s->forms_rec) s->forms_rec[FG_FORM_SLOT_X] = s->fd_dct_x == 2 ? FG_FORM_FFT : FG_FORM_DCT;
     return launch_dct<false>(s, G.nx, a, slot, batch, st);
 }
 int fg_fd_dct_inverse(fg_state* s, const float* u, float* z, const float* dot_with, FgDacc* dot_acc, int dot_stride,

@@ -687,22 +687,24 @@ __global__ __launch_bounds__(64) void k_fd_rowmean_factor(const float* __restric
 
 }  // namespace
 
-// dynamic LDS above 64 KB needs an explicit opt-in per kernel (once per process and size class)
-static bool tridiag_lds_ready(size_t bytes, bool fac = false) {
+// dynamic LDS above 64 KB needs an explicit opt-in per kernel (once per process and size class); family 0: the plain LDS kernels,
+// 1: their FAC forms, 2: the streaming k_tridiag_y (its y buffer passes 64 KB beyond 256 rows)
+static bool tridiag_lds_ready(size_t bytes, int family = 0) {
     static std::mutex mu;
-    static size_t granted_dev[64][2] = {{0}};      // per device (the attribute belongs to the device current when it is set) and kernel family
-    static bool failed_dev[64][2] = {{false}};
+    static size_t granted_dev[64][3] = {{0}};      // per device (the attribute belongs to the device current when it is set) and kernel family
+    static bool failed_dev[64][3] = {{false}};
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { (void)hipGetLastError(); return false; }
     std::lock_guard<std::mutex> lock(mu);
-    size_t& granted = granted_dev[dev][fac ? 1 : 0];
-    bool& failed = failed_dev[dev][fac ? 1 : 0];
+    size_t& granted = granted_dev[dev][family];
+    bool& failed = failed_dev[dev][family];
     if (bytes <= granted) return true;
     if (failed) return false;
-    const void* plain[2] = {reinterpret_cast<const void*>(k_tridiag_y_lds<false, 64>), reinterpret_cast<const void*>(k_tridiag_y_lds<true, 64>)};
-    const void* facs[2] = {reinterpret_cast<const void*>(k_tridiag_y_lds<false, 64, true>), reinterpret_cast<const void*>(k_tridiag_y_lds<true, 64, true>)};
-    for (const void* f : (fac ? facs : plain))
-        if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
+    const void* kernels[3][2] = {{reinterpret_cast<const void*>(k_tridiag_y_lds<false, 64>), reinterpret_cast<const void*>(k_tridiag_y_lds<true, 64>)},
+                                 {reinterpret_cast<const void*>(k_tridiag_y_lds<false, 64, true>), reinterpret_cast<const void*>(k_tridiag_y_lds<true, 64, true>)},
+                                 {reinterpret_cast<const void*>(k_tridiag_y), nullptr}};
+    for (const void* f : kernels[family])
+        if (f && hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
             (void)hipGetLastError();
             failed = true;
             return false;
@@ -711,7 +713,9 @@ static bool tridiag_lds_ready(size_t bytes, bool fac = false) {
     return true;
 }
 
-static int launch_gemm(const fg_state* s, const GemmArgs& g, int batch, int expect_active, hipStream_t st) {
+// rec: the forms_rec slot this basis change reports its form in (fg_debug_apply_*; -1: none)
+static int launch_gemm(const fg_state* s, const GemmArgs& g, int batch, int expect_active, hipStream_t st, int rec = -1) {
+    auto note = [&](int form) { if (rec >= 0 && s->forms_rec) s->forms_rec[rec] = form; };
     // algorithmic traffic per env: A read + C written (+ the dot operand); the transform matrix stays in L2
     const double bytes = 4.0 * ((double)g.M * g.K + (double)g.M * g.N + (g.dot_with ? (double)g.M * g.N : 0.0));
     const long big_blocks = (long)((g.N + 127) / 128) * ((g.M + 127) / 128) * batch;
@@ -728,18 +732,22 @@ static int launch_gemm(const fg_state* s, const GemmArgs& g, int batch, int expe
         // stage -- the 128 x 128 tile below spent half its MFMAs on padding rows and four barrier pairs on a K of 64 (round 4:
         // 21 us per transform at 24 TFLOP/s; the transform moves 34 MB per launch, i.e. ~7 us of traffic)
         const int tn = (g.N + 127) / 128;
+        note(FG_FORM_GEMM_Z64);
         FG_LAUNCH_P(s, slot, (k_gemm_f32<1, 2, 64>), dim3((unsigned)(tn * batch)), dim3(256), 0, st, g, tn, 1);
     } else if (big_blocks >= 512) {  // >= 2 workgroups per CU with the 128 x 128 tile
         const int tn = (g.N + 127) / 128, tm = (g.M + 127) / 128;
+        note(FG_FORM_GEMM_T128);
         FG_LAUNCH_P(s, slot, (k_gemm_f32<2, 2, 16>), dim3((unsigned)(tn * tm * batch)), dim3(256), 0, st, g, tn, tm);
     } else if (live_tiles >= 384) {
         // enough live 64 x 64 tiles for ~1.5 workgroups per CU: the LDS-staged tile reads each operand half as often
         // (measured at 256 x 128, all envs live: B = 64 17.5 us vs 27 us split-K; B = 16 10.1 vs 8.8; B = 4 9.6 vs 6.5)
         const int tn = (g.N + 63) / 64, tm = (g.M + 63) / 64;
+        note(FG_FORM_GEMM_T64);
         FG_LAUNCH_P(s, slot, (k_gemm_f32<1, 1, 64>), dim3((unsigned)(tn * tm * batch)), dim3(256), 0, st, g, tn, tm);
     } else {
         const int tn = (g.N + 31) / 32, tm = (g.M + 31) / 32;
         dim3 grid((unsigned)(tn * tm * batch));
+        note(FG_FORM_GEMM_SPLITK);
         if (g.Bt) FG_LAUNCH_P(s, slot, (k_gemm_sk<true>), grid, dim3(256), 0, st, g, tn, tm);
         else FG_LAUNCH_P(s, slot, (k_gemm_sk<false>), grid, dim3(256), 0, st, g, tn, tm);
     }
@@ -805,13 +813,16 @@ int fg_fd_tridiag(fg_state* s, float* cur, hipStream_t st, const FgCgLead* lead,
         FgFacArgs fa;
         fa.row_part = factor_from; fa.tiles_x = (nx + 63) / 64; fa.lam = s->fd_lam_x; fa.hy = G.h[1]; fa.rhy = G.rh[1]; fa.dt = factor_dt;
         fa.inv_out = s->fd_row_inv; fa.cp_out = s->fd_row_cp; fa.lower_out = s->fd_row_lower;
-        if (lds_coop + rows <= 160 * 1024 && tridiag_lds_ready(lds_coop + rows, true))
+        if (s->forms_rec) s->forms_rec[FG_FORM_SLOT_FACTORS] = FG_FORM_FAC_MADE;
+        if (lds_coop + rows <= 160 * 1024 && tridiag_lds_ready(lds_coop + rows, 1)) {
+            if (s->forms_rec) s->forms_rec[FG_FORM_SLOT_TRIDIAG] = FG_FORM_TRI_LDS3_FAC;
             FG_LAUNCH_P(s, slot, (k_tridiag_y_lds<false, 64, true>), grid, dim3(256), lds_coop + rows, st, cur, (const float*)nullptr, (const float*)nullptr,
                         (const float*)nullptr, s->flags, nx, ny, nz, ld, N, ny, fa);
-        else if (lds_two + rows <= 160 * 1024 && tridiag_lds_ready(lds_two + rows, true))
+        } else if (lds_two + rows <= 160 * 1024 && tridiag_lds_ready(lds_two + rows, 1)) {
+            if (s->forms_rec) s->forms_rec[FG_FORM_SLOT_TRIDIAG] = FG_FORM_TRI_LDS2_FAC;
             FG_LAUNCH_P(s, slot, (k_tridiag_y_lds<true, 64, true>), grid, dim3(256), lds_two + rows, st, cur, (const float*)nullptr, (const float*)nullptr,
                         (const float*)nullptr, s->flags, nx, ny, nz, ld, N, ny, fa);
-        else { fg_set_error("fg_fd_tridiag: no LDS for the factoring launch (fg_fd_tridiag_can_factor said otherwise)"); return FG_ERR_HIP; }
+        } else { fg_set_error("fg_fd_tridiag: no LDS for the factoring launch (fg_fd_tridiag_can_factor said otherwise)"); return FG_ERR_HIP; }
         FG_HIP_CHECK(hipGetLastError());
         return FG_OK;
     }
@@ -822,14 +833,25 @@ int fg_fd_tridiag(fg_state* s, float* cur, hipStream_t st, const FgCgLead* lead,
     const float* f_lower = rowf ? s->fd_row_lower : s->fd_lower;
     const long fstride = rowf ? N : 0;
     const int lstride = rowf ? ny : 0;
+    if (s->forms_rec) s->forms_rec[FG_FORM_SLOT_FACTORS] = rowf ? FG_FORM_FAC_ROWMEAN : FG_FORM_FAC_GRID;
     if ((nx & 3) == 0 && lds_coop <= 160 * 1024 && tridiag_lds_ready(lds_coop)) {
+        if (s->forms_rec) s->forms_rec[FG_FORM_SLOT_TRIDIAG] = FG_FORM_TRI_LDS3;
         FG_LAUNCH_P(s, slot, (k_tridiag_y_lds<false, 64>), grid, dim3(256), lds_coop, st, cur, f_inv, f_cp, f_lower,
                     s->flags, nx, ny, nz, ld, fstride, lstride, FgFacArgs{});
     } else if ((nx & 3) == 0 && lds_two <= 160 * 1024 && tridiag_lds_ready(lds_two)) {
+        if (s->forms_rec) s->forms_rec[FG_FORM_SLOT_TRIDIAG] = FG_FORM_TRI_LDS2;
         FG_LAUNCH_P(s, slot, (k_tridiag_y_lds<true, 64>), grid, dim3(256), lds_two, st, cur, f_inv, f_cp, f_lower,
                     s->flags, nx, ny, nz, ld, fstride, lstride, FgFacArgs{});
     } else {
-        FG_LAUNCH_P(s, slot, k_tridiag_y, grid, dim3(64), (size_t)((ny + 63) / 64 * 64) * 64 * sizeof(float), st, cur,
+        // the y buffer of the streaming kernel: past 64 KB (ny > 256) it needs the opt-in like the LDS kernels; past 160 KB (ny > 640)
+        // it cannot run at all, and fg_set_fd_preconditioner refuses such grids
+        const size_t lds_stream = (size_t)((ny + 63) / 64 * 64) * 64 * sizeof(float);
+        if (lds_stream > 160 * 1024 || !tridiag_lds_ready(lds_stream, 2)) {
+            fg_set_error("fg_fd_tridiag: the streaming tridiagonal kernel cannot hold this many rows in LDS (ny <= 640)");
+            return FG_ERR_UNSUPPORTED;
+        }
+        if (s->forms_rec) s->forms_rec[FG_FORM_SLOT_TRIDIAG] = FG_FORM_TRI_STREAM;
+        FG_LAUNCH_P(s, slot, k_tridiag_y, grid, dim3(64), lds_stream, st, cur,
                     s->fd_inv, s->fd_cp, s->fd_lower, s->flags, nx, ny, nz, ld);
     }
     FG_HIP_CHECK(hipGetLastError());
@@ -858,7 +880,7 @@ int fg_fd_apply(fg_state* s, const float* r, float* z, FgDacc* rz_acc, int rz_st
         g.B = s->fd_Qx; g.ldb = nx; g.strideB = 0; g.Bt = s->fd_QxT; g.ldbt = nx;
         g.C = t1; g.ldc = nx; g.strideC = N;
         g.M = ny * nz; g.N = nx; g.K = nx;
-        if (int rc = launch_gemm(s, g, B, expect_active, st)) return rc;
+        if (int rc = launch_gemm(s, g, B, expect_active, st, FG_FORM_SLOT_X)) return rc;
         g.judge = FgCgJudge{};
     }
     float* cur = t1;
@@ -868,7 +890,7 @@ int fg_fd_apply(fg_state* s, const float* r, float* z, FgDacc* rz_acc, int rz_st
         g.B = t1; g.ldb = (long)ny * nx; g.strideB = N; g.Bt = nullptr; g.ldbt = 0;
         g.C = t2; g.ldc = (long)ny * nx; g.strideC = N;
         g.M = nz; g.N = ny * nx; g.K = nz;
-        if (int rc = launch_gemm(s, g, B, expect_active, st)) return rc;
+        if (int rc = launch_gemm(s, g, B, expect_active, st, FG_FORM_SLOT_Z)) return rc;
         cur = t2;
     }
     if (int rc = fg_fd_tridiag(s, cur, st, nullptr, false)) return rc;
@@ -878,7 +900,7 @@ int fg_fd_apply(fg_state* s, const float* r, float* z, FgDacc* rz_acc, int rz_st
         g.B = t2; g.ldb = (long)ny * nx; g.strideB = N; g.Bt = nullptr; g.ldbt = 0;
         g.C = t1; g.ldc = (long)ny * nx; g.strideC = N;
         g.M = nz; g.N = ny * nx; g.K = nz;
-        if (int rc = launch_gemm(s, g, B, expect_active, st)) return rc;
+        if (int rc = launch_gemm(s, g, B, expect_active, st, FG_FORM_SLOT_Z)) return rc;
         cur = t1;
     }
     if (s->fd_dct_x) return fg_fd_dct_inverse(s, cur, z, r, rz_acc, rz_stride, rz_ns, st);
@@ -888,7 +910,7 @@ int fg_fd_apply(fg_state* s, const float* r, float* z, FgDacc* rz_acc, int rz_st
     g.C = z; g.ldc = nx; g.strideC = N;
     g.M = ny * nz; g.N = nx; g.K = nx;
     g.dot_with = rz_acc ? r : nullptr; g.strideW = N; g.dot_acc = rz_acc; g.dot_stride = rz_stride; g.dot_ns = rz_ns;
-    if (int rc = launch_gemm(s, g, B, expect_active, st)) return rc;
+    if (int rc = launch_gemm(s, g, B, expect_active, st, FG_FORM_SLOT_X)) return rc;
     FG_HIP_CHECK(hipGetLastError());
     return FG_OK;
 }
@@ -931,7 +953,7 @@ int fg_fd_helmholtz_apply(fg_state* s, int nc, const float* r, float* z, hipStre
         g.B = s->fd_Qx; g.ldb = nx; g.strideB = 0; g.Bt = s->fd_QxT; g.ldbt = nx;
         g.C = t1; g.ldc = nx; g.strideC = N;
         g.M = ny * nz; g.N = nx; g.K = nx;
-        if (int rc = launch_gemm(s, g, nsys, nsys, st)) return rc;
+        if (int rc = launch_gemm(s, g, nsys, nsys, st, FG_FORM_SLOT_X)) return rc;
     }
     float* cur = t1;
     if (G.dims == 3) {
@@ -939,7 +961,7 @@ int fg_fd_helmholtz_apply(fg_state* s, int nc, const float* r, float* z, hipStre
         g.B = t1; g.ldb = (long)ny * nx; g.strideB = N; g.Bt = nullptr; g.ldbt = 0;
         g.C = t2; g.ldc = (long)ny * nx; g.strideC = N;
         g.M = nz; g.N = ny * nx; g.K = nz;
-        if (int rc = launch_gemm(s, g, nsys, nsys, st)) return rc;
+        if (int rc = launch_gemm(s, g, nsys, nsys, st, FG_FORM_SLOT_Z)) return rc;
         cur = t2;
     }
     if (int rc = fg_helm_apply(s, nc, cur, cur, st)) return rc;   // per-mode Thomas solve, in place
@@ -948,7 +970,7 @@ int fg_fd_helmholtz_apply(fg_state* s, int nc, const float* r, float* z, hipStre
         g.B = t2; g.ldb = (long)ny * nx; g.strideB = N; g.Bt = nullptr; g.ldbt = 0;
         g.C = t1; g.ldc = (long)ny * nx; g.strideC = N;
         g.M = nz; g.N = ny * nx; g.K = nz;
-        if (int rc = launch_gemm(s, g, nsys, nsys, st)) return rc;
+        if (int rc = launch_gemm(s, g, nsys, nsys, st, FG_FORM_SLOT_Z)) return rc;
         cur = t1;
     }
     // inverse x: z[rows, i] = sum_a cur[rows, a] QxT[a, i]
@@ -957,7 +979,7 @@ int fg_fd_helmholtz_apply(fg_state* s, int nc, const float* r, float* z, hipStre
     g.B = s->fd_QxT; g.ldb = nx; g.strideB = 0; g.Bt = s->fd_Qx; g.ldbt = nx;
     g.C = z; g.ldc = nx; g.strideC = N;
     g.M = ny * nz; g.N = nx; g.K = nx;
-    if (int rc = launch_gemm(s, g, nsys, nsys, st)) return rc;
+    if (int rc = launch_gemm(s, g, nsys, nsys, st, FG_FORM_SLOT_X)) return rc;
     FG_HIP_CHECK(hipGetLastError());
     return FG_OK;
 }

@@ -795,6 +795,10 @@ struct fg_state {
     float* fd_lam_x; float* fd_row_inv; float* fd_row_cp; float* fd_row_lower; int fd_rowmean; long fd_row_epoch; mutable long rA_epoch;
     int fd_facfuse;               // FG_FD_FACFUSE (default 1): the first tridiagonal solve after 1/A changed makes the row-mean factors itself (0: k_fd_rowmean_factor, a launch of its own)
     float* fd_row_part; long fd_row_part_epoch;   // per-tile row sums of 1/A written by k_adv_build, and the rA epoch they belong to
+    // test entries only (fg_debug_apply_*): host array of FG_FORM_SLOTS the preconditioner dispatchers fill with the forms they launch
+    // (FG_FORM_* codes of include/fluidgym_hip.h); nullptr on every step path
+    int32_t* forms_rec;
+    const fg_real* adv_last_dt;   // dt of the last velocity fg_setup_advection (the Helmholtz operator of fg_debug_apply_preconditioner mode 3)
     fg_real** d_bvel_ptrs;   // device copy of bvel[6] (writable pointers for the flux balancing kernel)
     fg_real* diag_pinned;    // [2B] host-pinned: flux balance | max velocity
     fg_real* dt_pinned;      // [B] host-pinned per-env substep sizes of fg_single_step

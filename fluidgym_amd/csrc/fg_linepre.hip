@@ -754,6 +754,7 @@ int fg_helm_factor(fg_state* s, const float* dt, float nu, int wall_lo, int wall
 
 // z = M^-1 r (the per-mode Thomas solves of the Helmholtz operator factorised by the last fg_helm_factor), nc systems per env
 int fg_helm_apply(fg_state* s, int nc, const float* r, float* z, hipStream_t st) {
+    if (s->forms_rec) s->forms_rec[FG_FORM_SLOT_HELM] = !s->helm_cb ? FG_FORM_HELM_ARRAY : s->helm_cb == 64 ? FG_FORM_HELM_ROW64 : FG_FORM_HELM_ROW32;
     if (!s->helm_cb) return fg_line_apply(s, s->helm_diag, nullptr, nc, r, z, st);
     HelmArgs a = {};
     a.inv = s->helm_set ? s->line_inv2 : s->line_inv; a.cp = s->helm_set ? s->line_cp2 : s->line_cp;
@@ -786,7 +787,9 @@ int fg_line_apply(fg_state* s, const float* diag, const float* off, int nc, cons
     const int cols = s->grid.nx * s->grid.nz, nsys = s->grid.B * nc;
     // per system and cell: r, inv, c', l read + z written
     const int slot = fg_prof_slot(s, FG_PK_LINE, s->flags, nsys, 20.0 * s->grid.n, 5.0 * s->grid.n, st);
-    if (line_use_lds(s))
+    const bool lds = line_use_lds(s);
+    if (s->forms_rec) s->forms_rec[FG_FORM_SLOT_LINE] = lds ? FG_FORM_LINE_LDS : FG_FORM_LINE_STREAM;
+    if (lds)
         FG_LAUNCH_P(s, slot, k_line_apply_y, dim3((cols + 63) / 64, nsys), dim3(256), line_lds_bytes(s), st, a, r, z);
     else
         FG_LAUNCH_P(s, slot, k_line_apply_y_stream, dim3((cols + 255) / 256, nsys), dim3(256), 0, st, a, r, z);

@@ -104,8 +104,12 @@ class NativeSolver:
             fd = FDPreconditioner(self.widths, [f for f in range(6) if self.fixed[f]])
             fpp = lambda a: a.ctypes.data_as(fp)
             qz, qzt = (fpp(fd.Qz), fpp(fd.QzT)) if self.dims == 3 else (None, None)
-            L.check(self.lib.fg_set_fd_preconditioner(self.handle, fpp(fd.Qx), fpp(fd.QxT), qz, qzt, fpp(fd.lower),
-                                                      fpp(fd.inv), fpp(fd.cp)))
+            rc = self.lib.fg_set_fd_preconditioner(self.handle, fpp(fd.Qx), fpp(fd.QxT), qz, qzt, fpp(fd.lower), fpp(fd.inv), fpp(fd.cp))
+            # the library refuses grids its tridiagonal solve cannot hold (more than 640 rows in the fp32 build): plain CG there
+            self.has_fd = rc != L.FG_ERR_UNSUPPORTED
+            if self.has_fd:
+                L.check(rc, lib=self.lib)
+        if self.has_fd:
             no_fft = self.f64 or os.environ.get("FG_FD_NO_FFT", "0") != "0"      # (the row FFTs and the Helmholtz operator are fp32 kernels)
             if fd.x_cosine_width is not None and not no_fft:
                 # the x basis is the DCT-II basis: apply it as a fast cosine transform instead of the dense GEMM
@@ -469,14 +473,31 @@ class NativeSolver:
         carries ILU(0) alone: modes 0, 4 and 5 (``Simulation`` maps the reference's flags onto 4 / 5 there); 1 - 3 raise."""
         L.check(self.lib.fg_set_advection_preconditioner(self.handle, int(mode)), lib=self.lib)
 
-    def apply_advection_preconditioner(self, mode: int, r: torch.Tensor) -> torch.Tensor:
-        """``z = M^-1 r`` for ``r [B, nc, *grid]`` with the preconditioner of ``mode`` (1 y-line, 4 ILU(0)) built from the matrix
-        ``setup_advection`` assembled last (``fg_debug_apply_preconditioner``; tests)."""
+    def apply_advection_preconditioner(self, mode: int, r: torch.Tensor, return_forms: bool = False):
+        """``z = M^-1 r`` for ``r [B, nc, *grid]`` with the preconditioner of ``mode`` (1 y-line, 3 the velocity system's Helmholtz
+        operator, 4 ILU(0)) built from the matrix ``setup_advection`` assembled last (``fg_debug_apply_preconditioner``; tests).
+        ``return_forms``: also the ``FG_FORM_SLOTS`` kernel forms that ran (``_lib.FG_FORM_*``)."""
         r = r.to(self.device, self.dtype).contiguous()
         z = torch.empty_like(r)
+        forms = (ctypes.c_int32 * L.FG_FORM_SLOTS)()
         L.check(self.lib.fg_debug_apply_preconditioner(self.handle, int(mode), int(r.shape[1]), ctypes.c_void_p(r.data_ptr()),
-                                                       ctypes.c_void_p(z.data_ptr()), _stream(self.device)), lib=self.lib)
-        return z
+                                                       ctypes.c_void_p(z.data_ptr()), forms, _stream(self.device)), lib=self.lib)
+        return (z, list(forms)) if return_forms else z
+
+    def apply_pressure_preconditioner(self, form: int, r: torch.Tensor, rA: Optional[torch.Tensor] = None):
+        """``z = M^-1 r`` for ``r [B, *grid]`` with a preconditioner of the pressure CG, run by the solvers' own dispatch
+        (``fg_debug_apply_pressure_preconditioner``; tests): form 0 the grid's A = 1 operator, 1 the row-mean operator of ``rA``,
+        2 the row-mean operator of the last ``setup_advection`` with its factors made inside the tridiagonal launch (``rA`` None).
+        Returns ``(z, r.z per env, forms)``."""
+        r = r.to(self.device, self.dtype).contiguous()
+        z = torch.empty_like(r)
+        ra = ctypes.c_void_p(None) if rA is None else ctypes.c_void_p(rA.data_ptr())
+        rz = (ctypes.c_double * self.B)()
+        forms = (ctypes.c_int32 * L.FG_FORM_SLOTS)()
+        L.check(self.lib.fg_debug_apply_pressure_preconditioner(self.handle, int(form), ra, ctypes.c_void_p(r.data_ptr()),
+                                                                ctypes.c_void_p(z.data_ptr()), rz, forms, _stream(self.device)),
+                lib=self.lib)
+        return z, list(rz), list(forms)
 
     def advection_retries(self, reset: bool = False) -> int:
         out = ctypes.c_int64()

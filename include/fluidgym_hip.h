@@ -196,9 +196,55 @@ int fg_set_advection_preconditioner(fg_handle h, int mode);
  * |S| = sqrt(2 S:S) from the gradients of the bound velocity (getBlockDataGradient, :2997-3040: central differences, a Dirichlet face
  * counts as half a cell) and Delta^2 = the largest squared cell extent.  Asynchronous on `stream`. */
 int fg_sgs_smagorinsky(fg_handle h, fg_real coefficient, fg_real* out_BN, void* stream);
-/* Test / diagnosis entry, never on a step path: z = M^-1 r [B, nc, N] with the preconditioner of `mode` (1: y-line, 4: ILU(0)) built from
- * the advection-diffusion matrix currently assembled (fg_setup_advection).  Synchronises. */
-int fg_debug_apply_preconditioner(fg_handle h, int mode, int nc, const fg_real* r, fg_real* z, void* stream);
+/* Test / diagnosis entry, never on a step path: z = M^-1 r [B, nc, N] with the preconditioner of `mode` (1: y-line, 3: the separable
+ * Helmholtz operator of the velocity system, I/dt - nu Laplacian with the dt of the last velocity fg_setup_advection, applied by the
+ * dispatch the BiCGStab runs; 4: ILU(0)) built from the advection-diffusion matrix currently assembled (fg_setup_advection).
+ * forms_out (optional): int32_t[FG_FORM_SLOTS], the kernel forms that ran (FG_FORM_* below).  Synchronises. */
+int fg_debug_apply_preconditioner(fg_handle h, int mode, int nc, const fg_real* r, fg_real* z, int32_t* forms_out, void* stream);
+/* Test / diagnosis entry, never on a step path: z = M^-1 r [B, N] with a preconditioner of the pressure CG, run by the dispatch the
+ * solvers run on this grid.  form 0: the grid's A = 1 operator (fg_fd_apply, with its fused r.z); 1: the row-mean operator (1/A replaced
+ * by its mean along x per row and env), factors made from rA [B, N] by their own launch; 2: the same operator with the factors made
+ * inside the tridiagonal launch from the per-tile row sums the last velocity fg_setup_advection left (rA must be nullptr: that
+ * assembly's 1/A).  rz_out (optional, host): double[B], r.z per env.  forms_out (optional): int32_t[FG_FORM_SLOTS].  A form the grid
+ * or the build does not carry returns FG_ERR_UNSUPPORTED with its reason (forms 1 / 2: 2-D, fast x transform, nx % 64 == 0,
+ * ny <= 320; form 2 also the LDS of the factoring launch; the fp64 build carries form 0 only).  Synchronises. */
+int fg_debug_apply_pressure_preconditioner(fg_handle h, int form, const fg_real* rA, const fg_real* r, fg_real* z, double* rz_out,
+                                           int32_t* forms_out, void* stream);
+/* forms_out of the two entries above: slot -> the form of that step of the application (0 = the step did not run) */
+#define FG_FORM_SLOTS 8
+#define FG_FORM_SLOT_X 0          /* x basis change */
+#define FG_FORM_SLOT_Z 1          /* z basis change (3-D) */
+#define FG_FORM_SLOT_TRIDIAG 2    /* per-mode tridiagonal solve of the pressure operator */
+#define FG_FORM_SLOT_FACTORS 3    /* the factors that solve used */
+#define FG_FORM_SLOT_HELM 4       /* Helmholtz per-mode solve */
+#define FG_FORM_SLOT_LINE 5       /* y-line kernels (mode 1, and the array form of the Helmholtz solve) */
+/* basis changes: MFMA GEMM split-K | 64 x 64 tile | 128 x 128 tile | 64 x 128 tile with the whole K (64-plane z transform) | row FFT
+ * of the cosine basis | row FFT of the Fourier basis | the fp64 build's plain kernels */
+#define FG_FORM_GEMM_SPLITK 1
+#define FG_FORM_GEMM_T64 2
+#define FG_FORM_GEMM_T128 3
+#define FG_FORM_GEMM_Z64 4
+#define FG_FORM_DCT 5
+#define FG_FORM_FFT 6
+#define FG_FORM_F64 7
+/* tridiagonal solve: streaming | three LDS arrays | two LDS arrays | the same, making the row-mean factors (FAC) | fp64 kernel */
+#define FG_FORM_TRI_STREAM 1
+#define FG_FORM_TRI_LDS3 2
+#define FG_FORM_TRI_LDS2 3
+#define FG_FORM_TRI_LDS3_FAC 4
+#define FG_FORM_TRI_LDS2_FAC 5
+#define FG_FORM_TRI_F64 6
+/* factors: the grid's A = 1 operator | per-env row-mean factors read from memory | made by the FAC launch itself */
+#define FG_FORM_FAC_GRID 1
+#define FG_FORM_FAC_ROWMEAN 2
+#define FG_FORM_FAC_MADE 3
+/* Helmholtz: array form (k_helm_coeffs + the y-line kernels) | row form with 32 | 64 columns per workgroup */
+#define FG_FORM_HELM_ARRAY 1
+#define FG_FORM_HELM_ROW32 2
+#define FG_FORM_HELM_ROW64 3
+/* y-line: column block in LDS | streaming */
+#define FG_FORM_LINE_LDS 1
+#define FG_FORM_LINE_STREAM 2
 /* mode 3 of fg_set_advection_preconditioner: every advection-diffusion solve right-preconditioned by the separable Helmholtz
  * operator I/dt - nu Laplacian (the matrix without its advective part), inverted by fast diagonalisation: basis change along the
  * PERIODIC, uniform transform axes (x, z; the eigenvectors of fg_set_fd_preconditioner), one tridiagonal solve along y per mode

@@ -31,6 +31,12 @@ def test_library_exports_every_declared_symbol():
         assert name in L.SIGNATURES, f"{name} has no ctypes signature in fluidgym_amd/_lib.py"
     assert set(L.SIGNATURES) <= set(declared)
     assert lib.fg_abi_version() == 1
+    # the test entries of the preconditioner forms (forms_out: FG_FORM_SLOTS int32)
+    assert L.SIGNATURES["fg_debug_apply_preconditioner"][1][5] is ctypes.POINTER(ctypes.c_int32)
+    assert L.SIGNATURES["fg_debug_apply_pressure_preconditioner"][1][5:7] == [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)]
+    # the entry count the design document states
+    m = re.search(r"\((\d+) entry points", open(os.path.join(ROOT, "DESIGN.md")).read())
+    assert m and int(m.group(1)) == len(declared)
 
 
 def test_fp64_build_exports_the_single_block_entry_points_with_double_signatures():

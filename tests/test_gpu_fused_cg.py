@@ -340,7 +340,7 @@ def test_corrector_launched_behind_the_verdict_kernel_changes_no_bit(monkeypatch
         print("SPEC", mult, "iterations", a[3], "unstored solves", a[4])
 
 
-@pytest.mark.parametrize("n", [(128, 36), (256, 128), (512, 256)])
+@pytest.mark.parametrize("n", [(128, 36), (256, 128), (512, 256), (64, 192), (64, 193), (64, 304), (64, 305)])
 def test_factors_made_by_the_first_tridiagonal_solve_are_the_factor_kernels(n, monkeypatch):
     """Round 6: the per-env factors of the row-mean preconditioner are made by the first tridiagonal solve after 1/A changed
     (``k_tridiag_y_lds<.., FAC>``: k_fd_rowmean_factor's arithmetic inside wave 0's forward sweep) instead of by a launch of their
