@@ -117,11 +117,7 @@ extern "C" int fg_create(const fg_config* cfg, const fg_real* hx, const fg_real*
     if (int rc = fg_poll_create(&s->poll, (int)(nsys > 2 * (size_t)g.B ? nsys : 2 * (size_t)g.B))) return rc;
     for (int k = 0; k < 4; ++k) { s->pred_bicg[k] = 2; s->pred_cg[k] = 1; }
     s->wall_forcing_axis = -1;
-    s->adv_precond = 0; s->line_retries = 0; s->line_inv = nullptr; s->line_cp = nullptr; s->ilu_d = nullptr;
-    s->double_fallback = 0; s->ladder_force = 0; s->r64_buf = nullptr; s->r64_acc = nullptr;
-    s->ref64_outer = 0; s->ref64_tol = 0.f; s->ref64_inner = 1e-4f; s->ref64_x = nullptr; s->ref64_corrections = 0;
-    for (int k = 0; k < 4; ++k) s->rung_count[k] = 0;
-    s->fd_lam = nullptr; s->helm_diag = s->helm_lower = s->helm_upper = s->helm_tmp = nullptr;
+    s->ref64_inner = 1e-4f;
     s->cg_wgs_per_slot = 256;      // (FG_CG_WGS_PER_SLOT until round 5: never changed by a test or a bench leg -- a constant since round 6)
     // FG_BICG3: z-marching two-kernel BiCGStab in 3-D (fg_bicgstab3d.hip): 0 never | > 0 always, with that z-chunk length (tests on
     // small grids) | unset: when the grid fits the tiles and fills the chip.  FG_BICG3_BXL: 16 / 32 float4 lanes along x (tile shape)
@@ -156,15 +152,11 @@ extern "C" int fg_create(const fg_config* cfg, const fg_real* hx, const fg_real*
     FG_HIP_CHECK(hipMemset(s->fcg_xsum, 0, sizeof(FgDacc) * 2 * (size_t)g.B));
     FG_HIP_CHECK(hipMalloc(&s->fcg_lazy, sizeof(int32_t) * (size_t)g.B));
     FG_HIP_CHECK(hipMemset(s->fcg_lazy, 0, sizeof(int32_t) * (size_t)g.B));
-    s->fcg_check0_ran = 0; s->fcg_lazy_on = 0; s->fcg_lazy_z = nullptr; s->fcg_unstored = 0; s->fcg_first_polls = 0;
     { const char* e = getenv("FG_FCG_FIRST"); s->fcg_first = (e && atoi(e) == 0) ? 0 : 1; }
     { const char* e = getenv("FG_JAC_SPEC"); s->jac_spec = (e && atoi(e) == 0) ? 0 : 1; }
-    s->jac_spec_fn = nullptr; s->jac_spec_ctx = nullptr; s->jac_spec_done = 0; s->jac_spec_missed = 0;
     { const char* e = getenv("FG_FCG_SPEC"); s->fcg_spec = (e && atoi(e) == 0) ? 0 : 1; }
-    s->fcg_spec_fn = nullptr; s->fcg_spec_ctx = nullptr; s->fcg_spec_done = 0;
     { const char* e = getenv("FG_JAC_PREFACTOR"); s->jac_prefactor = (e && atoi(e) == 0) ? 0 : 1; }
     { const char* e = getenv("FG_JAC_WARM"); s->jac_warm = e ? (atoi(e) != 0 ? 1 : 0) : -1; }      // (-1: where it pays, jac_warm_start)
-    s->fcg_mean_ready = 0;
     s->cg_return_best = 1;
     s->cg_reset_steps = 100;
     s->adv_from_result = 1;
@@ -346,7 +338,7 @@ extern "C" int fg_debug_apply_preconditioner(fg_handle s, int mode, int nc, cons
                "fg_debug_apply_preconditioner: mode 1 (y-line), 3 (Helmholtz) or 4 (ILU(0)), 1 <= nc <= dims");
     hipStream_t st = (hipStream_t)stream;
     FormsRecord forms(s, forms_out);
-    s->bicg_ready_nc = 0; s->cg_ready_ns = 0;
+    s->prepared.clear();
     FG_HIP_CHECK(hipMemsetAsync(s->flags, 0, sizeof(int32_t) * (size_t)s->grid.B * s->grid.dims, st));
     if (mode == 3) {
         // the velocity system's operator (both y walls prescribed), factorised and applied as the Helmholtz-preconditioned BiCGStab does
@@ -388,7 +380,7 @@ extern "C" int fg_debug_apply_pressure_preconditioner(fg_handle s, int form, con
     hipStream_t st = (hipStream_t)stream;
     const int B = s->grid.B;
     FormsRecord forms(s, forms_out);
-    s->bicg_ready_nc = 0; s->cg_ready_ns = 0;
+    s->prepared.clear();
     FG_HIP_CHECK(hipMemsetAsync(s->flags, 0, sizeof(int32_t) * (size_t)B * s->grid.dims, st));
     FgDacc* acc = nullptr;
     if (rz_out) {
@@ -543,7 +535,7 @@ static int setup_advection(fg_handle s, const fg_real* dt_B, int for_scalar, int
     return fg_launch_adv_build(s, make_bounds(s, channel), a, (hipStream_t)stream);
 }
 
-static int advection_solve(fg_state* s, FgBicgArgs a, fg_solve_info* info, hipStream_t st, int for_scalar = 0, int channel = 0);
+static int advection_solve(fg_state* s, FgBicgArgs a, fg_solve_info* info, hipStream_t st, int for_scalar = 0, int channel = 0, bool* spec_ran = nullptr);
 
 extern "C" int fg_solve_advection(fg_handle s, int for_scalar, int channel, fg_real tol, int max_iterations,
                                   fg_solve_info* info_host, void* stream) {
@@ -582,7 +574,7 @@ extern "C" int fg_setup_pressure_rhs(fg_handle s, const fg_real* dt_B, void* str
     return fg_launch_div(s, make_bounds(s, 0), dt_B, s->hvec, s->div, st);
 }
 
-// k_h and the divergence kernel of corrector 0, launched by fg_jacobi_solve behind its check kernel (fg_state::jac_spec_fn)
+// k_h and the divergence kernel of corrector 0, launched by fg_jacobi_solve behind its check kernel (FgSpecHook)
 struct SpecH { fg_state* s; const fg_real* dt; const fg_step_options* opt; hipStream_t st; };
 static int spec_h(void* p) {
     const SpecH* c = static_cast<const SpecH*>(p);
@@ -592,19 +584,36 @@ static int spec_h(void* p) {
                          c->opt->pressure_method == FG_SOLVER_FDCG && s->fd_Qx != nullptr);
 }
 
-// the corrector of fg_piso_step in its unstored-pressure form (FgLazyRef), launched by fg_cg_solve behind k_fcg_check0 (fg_state::fcg_spec_fn)
-struct SpecCorrect { fg_state* s; const fg_real* dt; bool last; hipStream_t st; };
-static int spec_correct(void* p) {
-    const SpecCorrect* c = static_cast<const SpecCorrect*>(p);
-    fg_state* s = c->s;
-    const FgMeanRef mean = {s->fcg_xsum, s->info_dev, s->pressure, s->fcg_lazy, s->fcg_alpha};
-    const FgLazyRef lazy = {s->fcg_lazy, s->fcg_alpha, c->last ? s->p_result : nullptr};
-    return fg_launch_correct(s, c->dt, s->rA, s->hvec, s->fcg_lazy_z, s->vel_result, c->st, c->last ? s->velocity : nullptr, c->last ? &mean : nullptr, &lazy);
+// The corrector of fg_piso_step on what the pressure solve left behind (FgCgOutcome).  The last one also removes the mean and writes
+// the block fields (setPressureResult, CopyPressureResultToBlocks, CopyVelocityResultToBlocks: PISOtorch_simulation.py:1922-1925, 1953,
+// 1974): where the solver left sum(p) behind (fused CG, fg_fftcg.hip) it does both where it reads p for the gradient -- pressureResult
+// then keeps its constant, which nothing downstream sees (grad p; the next solve starts from zero or from it).  A solve that stored
+// no pressure: the corrector reads alpha z (FgLazyRef; the last one also stores pressureResult).
+static int launch_corrector(fg_state* s, const fg_real* dt, const FgCgOutcome& o, bool last, hipStream_t st) {
+    const bool mean_folded = last && o.mean_ready;
+    FG_REQUIRE(!o.lazy_z || !last || mean_folded, FG_ERR_UNSUPPORTED, "fg_piso_step: an unmaterialised pressure without its folded mean");
+    if (last && !mean_folded)
+        if (int rc = fg_launch_mean_sub(s, dt, s->p_result, s->pressure, st)) return rc;
+    const FgMeanRef mean = {s->fcg_xsum, s->info_dev, s->pressure, o.marks_valid ? s->fcg_lazy : nullptr, s->fcg_alpha};
+    const FgLazyRef lazy = {s->fcg_lazy, s->fcg_alpha, last ? s->p_result : nullptr};
+    const fg_real* p = o.lazy_z ? o.lazy_z : ((last && !mean_folded) ? s->pressure : s->p_result);
+    return fg_launch_correct(s, dt, s->rA, s->hvec, p, s->vel_result, st, last ? s->velocity : nullptr, mean_folded ? &mean : nullptr, o.lazy_z ? &lazy : nullptr);
 }
 
+// that corrector launched by fg_cg_solve behind k_fcg_check0 (FgCgSpec)
+struct SpecCorrect { fg_state* s; const fg_real* dt; bool last; hipStream_t st; };
+static int spec_correct(void* p, const FgCgOutcome& o) {
+    const SpecCorrect* c = static_cast<const SpecCorrect*>(p);
+    return launch_corrector(c->s, c->dt, o, c->last, c->st);
+}
+
+// finalize == false (the fused step): *out says what the corrector finds (launch_corrector), spec rides behind the first verdict
 static int solve_pressure(fg_state* s, const fg_real* dt, int method, fg_real tol, int max_iterations, int use_previous,
-                          fg_solve_info* info_host, hipStream_t st, bool finalize = true, int kind = 2) {
+                          fg_solve_info* info_host, hipStream_t st, bool finalize = true, int kind = 2, FgCgOutcome* out = nullptr,
+                          FgCgSpec spec = FgCgSpec{}) {
     int rc = FG_OK;
+    FgCgOutcome own;
+    if (!out) out = &own;
     if (method == FG_SOLVER_CG || method == FG_SOLVER_FDCG) {
         FgCgArgs a;
         a.rA = s->rA; a.b = s->div; a.x = s->p_result;
@@ -615,16 +624,14 @@ static int solve_pressure(fg_state* s, const fg_real* dt, int method, fg_real to
         a.kind = kind;
         a.check_every = a.precond ? 2 : 16;
         a.lazy_ok = finalize ? 0 : 1;      // (the fused step's correctors read the result through FgLazyRef)
+        a.spec = spec;
 #if !FG_F64
         if (s->ref64_outer > 0) a.lazy_ok = 0;      // (the refinement below starts from the STORED fp32 result)
 #endif
-        rc = fg_cg_solve(s, a, info_host, st);
+        rc = fg_cg_solve(s, a, info_host, st, out);
 #if !FG_F64
         // opt-in: fp64 residual, fp32 corrections (fg_refine64_pressure) -- the solve then ends on the fp64 residual's own verdict
-        if (s->ref64_outer > 0 && (rc == FG_OK || rc == FG_ERR_NOT_CONVERGED)) {
-            s->fcg_lazy_on = 0; s->fcg_check0_ran = 0; s->fcg_mean_ready = 0; s->fcg_spec_done = 0;      // (the result is rewritten in p_result)
-            rc = fg_refine64_pressure(s, a, info_host, st);
-        }
+        if (s->ref64_outer > 0 && (rc == FG_OK || rc == FG_ERR_NOT_CONVERGED)) rc = fg_refine64_pressure(s, a, info_host, st, out);
         // pressure solves run with returnBestResult: only a NON-FINITE solve counts as failed and is repeated in fp64
         // (solver_double_fallback, PISOtorch_diff.py:410-445)
         if (s->double_fallback && (rc == FG_ERR_NOT_FINITE || (s->ladder_force & 2))) {
@@ -632,8 +639,7 @@ static int solve_pressure(fg_state* s, const fg_real* dt, int method, fg_real to
             fg_solve_info* info = info_host;
             if (!info) { tmp.assign(s->info_pinned, s->info_pinned + s->grid.B); info = tmp.data(); }
             s->rung_count[2] += 1;
-            s->fcg_lazy_on = 0; s->fcg_check0_ran = 0; s->fcg_mean_ready = 0; s->fcg_spec_done = 0;      // (the repeat stores its result in p_result)
-            rc = fg_rung64_cg(s, a, info, (s->ladder_force & 2) != 0, st);
+            rc = fg_rung64_cg(s, a, info, (s->ladder_force & 2) != 0, st, out);
         }
 #endif
     } else {
@@ -695,7 +701,7 @@ static int max_iters(const fg_solve_info* info, int n) {
 // (preconditionBiCG), mode 2 repeats a solve that ended unconverged or non-finite from zero WITH the preconditioner
 // (BiCG_precondition_fallback) -- the reference's preconditioner is cuSPARSE ILU(0), here the y-line solve of fg_linepre.hip;
 // modes 4 / 5 are the same two rules with ILU(0) itself (fg_ilu0.hip), the only preconditioner of the fp64 build.
-static int advection_solve(fg_state* s, FgBicgArgs a, fg_solve_info* info, hipStream_t st, int for_scalar, int channel) {
+static int advection_solve(fg_state* s, FgBicgArgs a, fg_solve_info* info, hipStream_t st, int for_scalar, int channel, bool* spec_ran) {
     a.precond = (s->adv_precond == 1) ? 1 : (s->adv_precond == 3 ? 2 : (s->adv_precond == 4 ? 3 : 0));
     if (a.precond == 2 && !for_scalar && s->visc_field) a.precond = 0;   // the Helmholtz operator is built for ONE viscosity
     if (a.precond == 2) {   // Helmholtz (fast-diagonalisation) preconditioner: the diffusivity and wall treatment of THIS solve
@@ -709,7 +715,7 @@ static int advection_solve(fg_state* s, FgBicgArgs a, fg_solve_info* info, hipSt
     const int nsys = s->grid.B * a.nc;
     std::vector<fg_solve_info> info_own;
     if (!info) { info_own.resize(nsys); info = info_own.data(); }      // (the rungs below read and update the solve infos in place)
-    int rc = fg_bicgstab_solve(s, a, info, st);
+    int rc = fg_bicgstab_solve(s, a, info, st, spec_ran);
     bool failed = (rc == FG_ERR_NOT_CONVERGED || rc == FG_ERR_NOT_FINITE) || (s->ladder_force & 1);
 #if !FG_F64
     if (failed && s->double_fallback && rc != FG_ERR_HIP) {
@@ -789,16 +795,14 @@ extern "C" int fg_piso_step(fg_handle s, const fg_real* dt_B, const fg_step_opti
     fg_range_push("velocity_assembly_and_solve");
     struct PopOnce { bool armed = true; void fire() { if (armed) { fg_range_pop(); armed = false; } } ~PopOnce() { fire(); } } range_velocity;
     if (int rc = setup_advection(s, dt_B, 0, 0, stream, opt->buoyancy_axis, opt->buoyancy_factor)) return rc;
+    bool h_div_ran = false;      // k_h and the divergence kernel of corrector 0 already ran behind the sweeps' check kernel (spec_h)
     {
         FgBicgArgs a;
         a.diag = s->A; a.off = s->Coff; a.rhs = s->adv_rhs; a.x = s->vel_result; a.nc = d;
         a.dt = dt_B; a.tol = opt->advection_tol; a.max_iterations = opt->max_iterations; a.use_x0 = s->adv_from_result;
         SpecH spec_h_ctx = {s, dt_B, opt, st};
-        s->jac_spec_done = 0;
-        if (opt->corrector_steps > 0) { s->jac_spec_fn = spec_h; s->jac_spec_ctx = &spec_h_ctx; }
-        const int arc = soft(advection_solve(s, a, info.data(), st));
-        s->jac_spec_fn = nullptr; s->jac_spec_ctx = nullptr;
-        if (arc) return arc;
+        if (opt->corrector_steps > 0) a.spec = FgSpecHook{spec_h, &spec_h_ctx};
+        if (int rc = soft(advection_solve(s, a, info.data(), st, 0, 0, &h_div_ran))) return rc;
         stats[1] = max_iters(info.data(), B * d);
         s->ctr.add(1, info.data(), B * d);
     }
@@ -807,38 +811,20 @@ extern "C" int fg_piso_step(fg_handle s, const fg_real* dt_B, const fg_step_opti
     for (int c = 0; c < opt->corrector_steps; ++c) {
         FgRange range_corr(c == 0 ? "pressure_corrector_0" : "pressure_corrector_1+");
         const bool last = (c + 1 == opt->corrector_steps);
-        if (!(c == 0 && s->jac_spec_done)) {      // (corrector 0: these two may already run behind the sweeps' check kernel, spec_h)
+        if (!(c == 0 && h_div_ran)) {
             if (int rc = fg_launch_h(s, dt_B, s->vel_result, st)) return rc;
             if (int rc = fg_launch_div(s, make_bounds(s, 0), dt_B, s->hvec, s->div, st, !opt->pressure_warm_start,
                                        opt->pressure_method == FG_SOLVER_FDCG && s->fd_Qx != nullptr))
                 return rc;
         }
-        s->jac_spec_done = 0;
-        // The mean removal + block copy of the last corrector's pressure (setPressureResult, CopyPressureResultToBlocks: :1922-1925, 1953):
-        // when the solver left sum(p) behind (fused CG, fg_fftcg.hip) the corrector does both where it reads p for the gradient --
-        // pressureResult then keeps its constant, which nothing downstream sees (grad p; the next solve starts from zero or from it)
         SpecCorrect spec_ctx = {s, dt_B, last, st};
-        s->fcg_spec_fn = spec_correct; s->fcg_spec_ctx = &spec_ctx;
-        const int prc = soft(solve_pressure(s, dt_B, opt->pressure_method, opt->pressure_tol, opt->max_iterations,
-                                            opt->pressure_warm_start ? 1 : 0,
-                                            info.data(), st, false, c == 0 ? 0 : 1));
-        s->fcg_spec_fn = nullptr; s->fcg_spec_ctx = nullptr;
-        if (prc) return prc;
-        if (c < 2) { stats[2 + c] = max_iters(info.data(), B); s->ctr.add(2 + c, info.data(), B); }
-        const bool mean_folded = last && s->fcg_mean_ready;
-        if (last && !mean_folded)
-            if (int rc = fg_launch_mean_sub(s, dt_B, s->p_result, s->pressure, st)) return rc;
-        const FgMeanRef mean = {s->fcg_xsum, s->info_dev, s->pressure, s->fcg_check0_ran ? s->fcg_lazy : nullptr, s->fcg_alpha};
-        // the solve ended on the first iterate of every env and stored no pressure: the corrector reads alpha z (FgLazyRef; the last
-        // one also stores pressureResult)
-        const bool lazy_p = s->fcg_lazy_on && (!last || mean_folded);
-        FG_REQUIRE(!s->fcg_lazy_on || lazy_p, FG_ERR_UNSUPPORTED, "fg_piso_step: an unmaterialised pressure without its folded mean");
-        const FgLazyRef lazy = {s->fcg_lazy, s->fcg_alpha, last ? s->p_result : nullptr};
-        // the last corrector also writes the block velocity of active envs: CopyVelocityResultToBlocks (:1974)
-        if (s->fcg_spec_done && lazy_p) continue;      // (this very launch already ran behind the verdict kernel: spec_correct)
-        if (int rc = fg_launch_correct(s, dt_B, s->rA, s->hvec, lazy_p ? s->fcg_lazy_z : ((last && !mean_folded) ? s->pressure : s->p_result),
-                                       s->vel_result, st, last ? s->velocity : nullptr, mean_folded ? &mean : nullptr, lazy_p ? &lazy : nullptr))
+        FgCgOutcome outcome;
+        if (int rc = soft(solve_pressure(s, dt_B, opt->pressure_method, opt->pressure_tol, opt->max_iterations, opt->pressure_warm_start ? 1 : 0,
+                                         info.data(), st, false, c == 0 ? 0 : 1, &outcome, FgCgSpec{spec_correct, &spec_ctx})))
             return rc;
+        if (c < 2) { stats[2 + c] = max_iters(info.data(), B); s->ctr.add(2 + c, info.data(), B); }
+        if (!outcome.spec_done)      // (else this very launch already ran behind the verdict kernel: spec_correct)
+            if (int rc = launch_corrector(s, dt_B, outcome, last, st)) return rc;
     }
     if (opt->corrector_steps <= 0)
         if (int rc = fg_launch_copy_active(s, dt_B, s->vel_result, s->velocity, d, st)) return rc;

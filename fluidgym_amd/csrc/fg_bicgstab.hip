@@ -667,51 +667,51 @@ __global__ void k_bicg_check(FgDacc* __restrict__ acc, int32_t* __restrict__ fla
 
 static int bicgstab_krylov(fg_state* s, const FgBicgArgs& a, fg_solve_info* info_host, hipStream_t st, bool begun);
 
-int fg_bicgstab_solve(fg_state* s, const FgBicgArgs& a, fg_solve_info* info_host, hipStream_t st) {
+// the solve's device state: prepared by the k_adv_build that assembled this system (FgPrepared), by the caller (begun), or here
+static void bicg_begin(fg_state* s, const FgBicgArgs& a, hipStream_t st, bool begun = false) {
+    const int nsys = s->grid.B * a.nc;
+    const bool taken = s->prepared.take_bicg(a.nc, a.dt);
+    if (!(begun || taken))
+        hipLaunchKernelGGL(k_bicg_begin, dim3((nsys + 63) / 64), dim3(64), 0, st, a.dt, s->acc, s->scratch_B + 4 * s->grid.B, s->flags, s->info_dev, nsys, a.nc);
+}
+
 #if !FG_F64
-    // velocity systems of the uniform 2-D grids: Jacobi sweeps first (fg_jacobi.hip); what they do not settle goes to BiCGStab from a
-    // cleared start vector, with the solve state prepared afresh
+// what the sweeps did not settle goes to the Krylov iteration: as it stands where they were not tried (the prepared state is untouched),
+// from a cleared start vector with the solve state prepared afresh where they gave up
+static int after_sweeps(fg_state* s, const FgBicgArgs& a, fg_solve_info* info_host, hipStream_t st, FgSweepOutcome outcome) {
+    if (outcome == FG_SWEEP_SOLVED || outcome == FG_SWEEP_SOLVED_SPEC) { s->jac_solves += 1; return FG_OK; }
+    if (outcome == FG_SWEEP_NOT_TRIED) return bicgstab_krylov(s, a, info_host, st, true);
+    s->jac_fallbacks += 1;
+    FgBicgArgs a2 = a;
+    a2.use_x0 = 0;
+    return bicgstab_krylov(s, a2, info_host, st, false);
+}
+#endif
+
+int fg_bicgstab_solve(fg_state* s, const FgBicgArgs& a, fg_solve_info* info_host, hipStream_t st, bool* spec_ran) {
+    if (spec_ran) *spec_ran = false;
+#if !FG_F64
+    // velocity systems of the uniform 2-D grids: Jacobi sweeps first (fg_jacobi.hip)
     if (fg_jacobi_ok(s, a)) {
-        const int nsys = s->grid.B * a.nc;
-        const bool ready = s->bicg_ready_nc == a.nc && s->bicg_ready_dt == a.dt;
-        s->bicg_ready_nc = 0; s->cg_ready_ns = 0;
-        if (!ready)
-            hipLaunchKernelGGL(k_bicg_begin, dim3((nsys + 63) / 64), dim3(64), 0, st, a.dt, s->acc, s->scratch_B + 4 * s->grid.B, s->flags, s->info_dev, nsys, a.nc);
-        int outcome = 0;
+        bicg_begin(s, a, st);
+        FgSweepOutcome outcome;
         if (int rc = fg_jacobi_solve(s, a, info_host, st, &outcome)) return rc;
-        if (outcome == 5) {      // (kernels launched behind the check on speculation overwrote the solve's state: the solve again, without them)
+        if (outcome == FG_SWEEP_SPEC_MISSED) {
             s->jac_spec_missed += 1;
-            int (*const fn)(void*) = s->jac_spec_fn;
-            s->jac_spec_fn = nullptr;
-            hipLaunchKernelGGL(k_bicg_begin, dim3((nsys + 63) / 64), dim3(64), 0, st, a.dt, s->acc, s->scratch_B + 4 * s->grid.B, s->flags, s->info_dev, nsys, a.nc);
-            outcome = 0;
-            const int rc = fg_jacobi_solve(s, a, info_host, st, &outcome);
-            s->jac_spec_fn = fn;
-            if (rc) return rc;
+            FgBicgArgs plain = a;
+            plain.spec = FgSpecHook{};
+            bicg_begin(s, plain, st);
+            if (int rc = fg_jacobi_solve(s, plain, info_host, st, &outcome)) return rc;
         }
-        if (outcome == 1) { s->jac_solves += 1; return FG_OK; }
-        if (outcome == 0) return bicgstab_krylov(s, a, info_host, st, true);   // (not tried: the prepared state is untouched)
-        s->jac_fallbacks += 1;
-        FgBicgArgs a2 = a;
-        a2.use_x0 = 0;
-        return bicgstab_krylov(s, a2, info_host, st, false);
+        if (spec_ran) *spec_ran = (outcome == FG_SWEEP_SOLVED_SPEC);
+        return after_sweeps(s, a, info_host, st, outcome);
     }
-    // the Helmholtz-preconditioned family (wall-refined 2-D grids: RBC): line sweeps first (fg_linepre.hip); what they do not settle
-    // goes to the preconditioned BiCGStab from a cleared start vector, with the solve state prepared afresh
+    // the Helmholtz-preconditioned family (wall-refined 2-D grids: RBC): line sweeps first (fg_linepre.hip)
     if (fg_linesweep_ok(s, a)) {
-        const int nsys = s->grid.B * a.nc;
-        const bool ready = s->bicg_ready_nc == a.nc && s->bicg_ready_dt == a.dt;
-        s->bicg_ready_nc = 0; s->cg_ready_ns = 0;
-        if (!ready)
-            hipLaunchKernelGGL(k_bicg_begin, dim3((nsys + 63) / 64), dim3(64), 0, st, a.dt, s->acc, s->scratch_B + 4 * s->grid.B, s->flags, s->info_dev, nsys, a.nc);
-        int outcome = 0;
+        bicg_begin(s, a, st);
+        FgSweepOutcome outcome;
         if (int rc = fg_linesweep_solve(s, a, info_host, st, &outcome)) return rc;
-        if (outcome == 1) { s->jac_solves += 1; return FG_OK; }
-        if (outcome == 0) return bicgstab_krylov(s, a, info_host, st, true);
-        s->jac_fallbacks += 1;
-        FgBicgArgs a2 = a;
-        a2.use_x0 = 0;
-        return bicgstab_krylov(s, a2, info_host, st, false);
+        return after_sweeps(s, a, info_host, st, outcome);
     }
 #endif
     return bicgstab_krylov(s, a, info_host, st, false);
@@ -730,11 +730,7 @@ static int bicgstab_krylov(fg_state* s, const FgBicgArgs& a, fg_solve_info* info
         q.mp = s->w[5]; q.ms = s->w[6];   // free during a BiCGStab solve (the CG's z and second p buffer)
     }
     const dim3 sg((nsys + 63) / 64), sb(64);
-    {   // state already prepared by the k_adv_build that assembled this system (FgBicgBegin, fg_internal.h)?
-        const bool ready = begun || (s->bicg_ready_nc == a.nc && s->bicg_ready_dt == a.dt);
-        s->bicg_ready_nc = 0; s->cg_ready_ns = 0;
-        if (!ready) hipLaunchKernelGGL(k_bicg_begin, sg, sb, 0, st, a.dt, q.acc, q.sc, q.flags, q.info, nsys, a.nc);
-    }
+    bicg_begin(s, a, st, begun);
     if (a.precond == 2) {
         FG_REQUIRE(s->fd_lam != nullptr, FG_ERR_INVALID_ARG, "Helmholtz preconditioner requested but fg_set_fd_helmholtz was not called");
         if (int rc = fg_helm_factor(s, a.dt, a.nu, a.wall_lo, a.wall_hi, a.nc, st, a.kind)) return rc;

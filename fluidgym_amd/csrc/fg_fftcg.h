@@ -45,8 +45,9 @@ struct FcgDivArgs {
 #if !FG_F64
 int fg_fcg_div_fwd(fg_state* s, const FgBounds& bnd, const fg_real* dt, const fg_real* hvec, fg_real* div, int ns, hipStream_t st);
 bool fg_fcg_ok(const fg_state* s);     // the grid / preconditioner setup the fused kernels cover (and FG_CG_FUSED != 0)
-int fg_fcg_update_fwd(fg_state* s, const FcgVectors& v, int it, int first, int ns, hipStream_t st, const fg_real* r0 = nullptr);
+// marks_valid: k_fcg_check0 ran in this solve -- the update of iteration 0 then takes the short path for the envs it marked (FcgUpdArgs::lazy)
+int fg_fcg_update_fwd(fg_state* s, const FcgVectors& v, int it, int first, int ns, hipStream_t st, bool marks_valid, const fg_real* r0 = nullptr);
 int fg_fcg_inv_apply(fg_state* s, const FcgVectors& v, const fg_real* rA, int it, int ns, hipStream_t st, int extras = 0);
-// verdict on the FIRST iterate from the dot products of I'(0) (k_fcg_check0): flags / info / alpha / lazy marks
-int fg_fcg_check0(fg_state* s, fg_real tol, int ns, hipStream_t st, FgPollOut poll);
+// verdict on the FIRST iterate from the dot products of I'(0) (k_fcg_check0): flags / info / alpha / lazy marks (*marks_valid = true)
+int fg_fcg_check0(fg_state* s, fg_real tol, int ns, hipStream_t st, FgPollOut poll, bool* marks_valid);
 #endif

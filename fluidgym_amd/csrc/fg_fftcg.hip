@@ -495,11 +495,11 @@ bool fg_fcg_ok(const fg_state* s) {
            s->fcg_alpha != nullptr;
 }
 
-int fg_fcg_update_fwd(fg_state* s, const FcgVectors& v, int it, int first, int ns, hipStream_t st, const fg_real* r0) {
+int fg_fcg_update_fwd(fg_state* s, const FcgVectors& v, int it, int first, int ns, hipStream_t st, bool marks_valid, const fg_real* r0) {
     const FgGrid& G = s->grid;
     FcgUpdArgs a = {};
     a.r0 = r0; a.x_zero = r0 ? 1 : 0;
-    a.lazy = (it == 0 && s->fcg_check0_ran) ? s->fcg_lazy : nullptr;
+    a.lazy = (it == 0 && marks_valid) ? s->fcg_lazy : nullptr;
     a.z = v.z; a.w = v.w; a.p = v.p; a.s = v.s; a.x = v.x; a.r = v.r; a.t1 = v.t1;
     a.tw = s->fd_dct_tw; a.rot = s->fd_dct_rot; a.fs0 = s->fd_dct_fwd[0]; a.fs = s->fd_dct_fwd[1];
     a.flags = s->flags; a.acc = s->cg_acc; a.alpha = s->fcg_alpha; a.xsum = s->fcg_xsum; a.best = s->cg_best;
@@ -527,12 +527,12 @@ int fg_fcg_inv_apply(fg_state* s, const FcgVectors& v, const fg_real* rA, int it
     FG_HIP_CHECK(hipGetLastError());
     return FG_OK;
 }
-int fg_fcg_check0(fg_state* s, fg_real tol, int ns, hipStream_t st, FgPollOut poll) {
+int fg_fcg_check0(fg_state* s, fg_real tol, int ns, hipStream_t st, FgPollOut poll, bool* marks_valid) {
     const FgGrid& G = s->grid;
     hipLaunchKernelGGL(k_fcg_check0, dim3((G.B + CHECK_WAVES - 1) / CHECK_WAVES), dim3(64 * CHECK_WAVES), 0, st, s->cg_acc, s->flags, s->info_dev, s->info_pinned, s->fcg_alpha, s->fcg_lazy,
                        tol, G.n, G.B, ns, poll);
     FG_HIP_CHECK(hipGetLastError());
-    s->fcg_check0_ran = 1;
+    *marks_valid = true;
     return FG_OK;
 }
 // right-hand side + start of the solve + first forward transform (k_fcg_div_fwd): div, r = w[0], x = p_result, u = w[3], r.r in ring entry 0

@@ -690,6 +690,24 @@ struct FgCounters {
     }
 };
 
+// Solver state already prepared by the kernel launched just before a solve (k_adv_build: FgBicgBegin; k_h: FgCgBegin; the divergence
+// kernel: FgCgStart) -- the solve then skips its own begin launch.  One record: a producer replaces it, the next solve of either kind
+// takes it and leaves none.
+struct FgPrepared {
+    int bicg_nc; const fg_real* bicg_dt;          // BiCGStab: systems per env, activity mask
+    int cg_ns, cg_best; const fg_real* cg_dt;     // CG: accumulator slots, best-iterate tracking, activity mask
+    int cg_start;   // 1: the CG was also started from zero (r = b in w[0], x = 0 in p_result, r.r in ring entry 0); 2: and w[3] holds Qx^T r_0 (k_fcg_div_fwd)
+    void clear() { *this = FgPrepared{}; }
+    void set_bicg(int nc, const fg_real* dt) { clear(); bicg_nc = nc; bicg_dt = dt; }
+    void set_cg(int ns, int best, const fg_real* dt) { clear(); cg_ns = ns; cg_best = best; cg_dt = dt; }
+    bool cg_for(const fg_real* dt) const { return cg_ns > 0 && cg_dt == dt; }      // the divergence kernel may start this CG ...
+    void set_cg_start(int form) { cg_start = form; }                                 // ... and says so (0: it did not)
+    bool take_bicg(int nc, const fg_real* dt) { const bool ready = bicg_nc == nc && bicg_dt == dt; clear(); return ready; }
+    int take_cg(int ns, int best, const fg_real* dt) {      // -1: not prepared, else cg_start
+        const int got = (cg_ns == ns && cg_best == best && cg_dt == dt) ? cg_start : -1; clear(); return got;
+    }
+};
+
 struct fg_state {
     fg_config cfg;
     FgGrid grid;
@@ -745,26 +763,15 @@ struct fg_state {
     // with a fast x transform, FG_CG_FUSED=0 at fg_create keeps the five kernels; alpha_k per env and parity; sum(x_k) per env and parity
     int cg_fused, bicg_pfused; double* fcg_alpha; FgDacc* fcg_xsum;
     // First iterate of the fused CG left unmaterialised (fg_fftcg.hip, k_fcg_check0): fcg_lazy[b] = 1 for an env whose FIRST iterate
-    // from zero met the tolerance -- its result is x = alpha_0 z_0.  fcg_check0_ran: the marks belong to the last pressure solve;
-    // fcg_lazy_on: that solve ended with EVERY env so (or stopped at its start vector) and wrote no x at all: the corrector reads
-    // fcg_lazy_z scaled by fcg_alpha[2 b] instead (FgLazyRef).  fcg_first: 0 switches the whole scheme off (FG_FCG_FIRST=0).
-    int32_t* fcg_lazy; mutable int fcg_check0_ran, fcg_lazy_on; mutable const fg_real* fcg_lazy_z; int fcg_first;
-    // The corrector launched BEHIND k_fcg_check0, before the host knows the verdict (fg_piso_step sets the hook): when every env ends on
-    // its first iterate -- the common case -- the corrector has then already run while the host turned the poll around
-    // (fcg_spec_done); otherwise its output is overwritten by the corrector that follows the finished solve (same inputs: it reads
-    // h, 1/A and z / x, writes the velocity result and, in the last corrector, the block fields nothing reads in between).
-    int (*fcg_spec_fn)(void*); void* fcg_spec_ctx; mutable int fcg_spec_done; int fcg_spec;      // fcg_spec: FG_FCG_SPEC (default 1)
-    // The first kernels of the corrector -- k_h, the divergence kernel -- launched BEHIND the sweeps' check kernel, before the host
-    // knows the verdict (fg_piso_step sets the hook; on-chip form, one planned pass writing the result vector): they read what the
-    // sweeps left and write h, the right-hand side and the CG's start, so the velocity solve's own device state (flags, sums) is gone
-    // once they ran -- a verdict that does not end the solve there (0.6 % of the soak's solves: profiles/r05_soak_first_iterate.jsonl) sends the whole solve
-    // round again without the speculation (outcome 5 of fg_jacobi_solve, jac_spec_missed).  FG_JAC_SPEC=0 switches it off.
-    int (*jac_spec_fn)(void*); void* jac_spec_ctx; mutable int jac_spec_done; int jac_spec; long jac_spec_missed;
+    // from zero met the tolerance -- its result is x = alpha_0 z_0 (FgCgOutcome says whether the marks belong to a solve and whether
+    // any x was stored).  fcg_first: 0 switches the whole scheme off (FG_FCG_FIRST=0).
+    int32_t* fcg_lazy; int fcg_first;
+    int fcg_spec;      // FG_FCG_SPEC (default 1): the corrector launched behind k_fcg_check0 (FgCgSpec)
+    int jac_spec; long jac_spec_missed;      // FG_JAC_SPEC (default 1): k_h and the divergence kernel launched behind the sweeps' check kernel (FgSpecHook) | solves that went round again without them
     long jac_floor_released = 0;   // systems the streaming sweeps ended on the fp32-floor rule (measured residual above the tolerance): fg_config_dump
     int jac_prefactor;      // FG_JAC_PREFACTOR (default 1): fg_fd_rowmean_prefactor behind the sweeps' check kernel
     int jac_warm;      // the Jacobi sweeps of the velocity systems start from the block velocity: 1 always, 0 never (the BiCGStab start vector), -1 (default) on the grids where that saves a pass (fg_jacobi.hip: jac_warm_start)
-    mutable long fcg_unstored, fcg_first_polls;      // solves that stored no x | solves whose first iterate was polled (fg_config_dump)
-    mutable int fcg_mean_ready;   // the last pressure solve left sum(x) of its result in fcg_xsum[b][used_iterations & 1] (consumed by k_correct)
+    long fcg_unstored, fcg_first_polls;      // solves that stored no x | solves whose first iterate was polled (fg_config_dump)
     fg_real* line_inv; fg_real* line_cp;
     fg_real* ilu_d;               // [B,N] modified diagonal of the ILU(0) preconditioner (fg_ilu0.hip), built per solve
     // the reference's retry ladder on this path (fg_set_double_fallback, fg_ladder; fg_rung64.h): double_fallback = repeat a failed
@@ -818,13 +825,9 @@ struct fg_state {
     long jac_rA_epoch;      // rA_epoch at which rA = 1 / A was written for the velocity system in s->A (the streaming sweeps read it)
     FgCounters ctr;         // iterations per solve kind since the last reset (fg_solver_counters)
     const fg_real* cur_dt;  // dt_B of the last fg_setup_advection: activity mask of the stepwise entry points
-    // solver state already prepared by the kernel launched just before the solve (k_adv_build: FgBicgBegin, k_div: FgCgBegin) --
-    // the solve then skips its own begin launch.  Consumed (and the other one dropped) by the next solve of either kind.
     FgPoll poll;                  // host polls of this handle (fg_poll.hip)
     mutable int maxvel_clean;     // scratch_B rows 1-2 (CFL maximum + arrival counters) are zero: left so by the mirrored k_max_velocity
-    mutable int bicg_ready_nc; mutable const fg_real* bicg_ready_dt;
-    mutable int cg_ready_ns, cg_ready_best; mutable const fg_real* cg_ready_dt;
-    mutable int cg_start_ready;   // k_div also started the CG from zero (r = b in w[0], x = 0 in p_result, r.r in ring entry 0)
+    FgPrepared prepared;          // kept on the handle: the stepwise entry points (fg_setup_pressure_rhs, then fg_solve_pressure) hand it across calls
     size_t n_cells() const { return (size_t)grid.n; }
 };
 
@@ -903,12 +906,12 @@ struct FgAdvArgs {
     const fg_real* buoy_T; long buoy_stride; int buoy_axis; fg_real buoy_factor; fg_real* source_w;
     fg_real* row_part;       // optional (2-D, float4 lanes): per-tile row sums of 1/A, [B][ny][tiles_x] (row-mean preconditioner, fg_fdprecond.hip)
 };
-int fg_launch_adv_build(const fg_state* s, const FgBounds& bnd, const FgAdvArgs& a, hipStream_t st);
+int fg_launch_adv_build(fg_state* s, const FgBounds& bnd, const FgAdvArgs& a, hipStream_t st);      // (fg_state*: these three launches record what they prepared, FgPrepared)
 int fg_launch_wall_forcing(const fg_state* s, hipStream_t st);   // force_uniform from the wall-adjacent layers of s->velocity
 int fg_launch_sgs(const fg_state* s, const FgBounds& bnd, fg_real coefficient, fg_real* out, hipStream_t st);
 int fg_launch_pressure_setup(const fg_state* s, const fg_real* dt, hipStream_t st);  // rA = 1/A
-int fg_launch_h(const fg_state* s, const fg_real* dt, const fg_real* vel_result, hipStream_t st);
-int fg_launch_div(const fg_state* s, const FgBounds& bnd, const fg_real* dt, const fg_real* hvec, fg_real* div, hipStream_t st,
+int fg_launch_h(fg_state* s, const fg_real* dt, const fg_real* vel_result, hipStream_t st);
+int fg_launch_div(fg_state* s, const FgBounds& bnd, const fg_real* dt, const fg_real* hvec, fg_real* div, hipStream_t st,
                   bool cg_from_zero = false,    // true: the kernel also starts the pressure CG that follows from zero (FgCgStart, fg_cg.h)
                   bool fused_fwd = false);      // true (with cg_from_zero): the solve is the FD-preconditioned CG -- where the fused row kernels cover the grid, right-hand side, start and first forward transform are ONE launch (k_fcg_div_fwd)
 // mean (optional): the corrector also writes p - mean(p) of active envs to p_copy (the block pressure: setPressureResult +
@@ -950,6 +953,18 @@ int fg_poisson_jacobi_launch(const fg_state* s, const fg_real* rA, const fg_real
                              fg_real omega, hipStream_t st);
 int fg_poisson_rbgs_launch(const fg_state* s, const fg_real* rA, const fg_real* b, fg_real* x, fg_real omega, int color,
                            hipStream_t st);
+// What a pressure solve left behind.  The default is the plain case: the result is stored in x and nothing else holds.
+struct FgCgOutcome {
+    const fg_real* lazy_z = nullptr;   // != nullptr: every env ended on its first iterate from zero (or at its start vector) and NO x was stored -- env b's result is fcg_alpha[2 b] * lazy_z where fcg_lazy[b] == 1, zero elsewhere (FgLazyRef)
+    bool mean_ready = false;           // sum(x) of the result is in fcg_xsum[b][used_iterations & 1] (FgMeanRef)
+    bool marks_valid = false;          // fcg_lazy[] belongs to this solve (k_fcg_check0 ran)
+    bool spec_done = false;            // the corrector of FgCgSpec ran on this very result
+};
+// The corrector launched BEHIND k_fcg_check0, before the host knows the verdict: `fn` gets the outcome the solve will have if every
+// env ends on its first iterate -- the common case: the corrector has then already run while the host turned the poll around
+// (FgCgOutcome::spec_done); otherwise its output is overwritten by the corrector that follows the finished solve (same inputs: it reads
+// h, 1/A and z / x, writes the velocity result and, in the last corrector, the block fields nothing reads in between).
+struct FgCgSpec { int (*fn)(void* ctx, const FgCgOutcome& o) = nullptr; void* ctx = nullptr; };
 struct FgCgArgs {
     const fg_real* rA; const fg_real* b; fg_real* x;
     fg_real* r; fg_real* p; fg_real* Ap;
@@ -958,11 +973,17 @@ struct FgCgArgs {
     int check_every;
     int precond;   // 1: fast-diagonalisation preconditioned CG (needs fg_set_fd_preconditioner)
     int kind = 2;  // which poll predictor the solve reads and updates (fg_state::pred_cg)
-    int lazy_ok = 0;   // the caller reads the result through FgLazyRef when fg_state::fcg_lazy_on comes back set (the fused PISO step)
+    int lazy_ok = 0;   // the caller can read an unstored result through FgLazyRef (FgCgOutcome::lazy_z; the fused PISO step)
+    FgCgSpec spec;     // optional
 };
-int fg_cg_solve(fg_state* s, const FgCgArgs& a, fg_solve_info* info_host, hipStream_t st);
+int fg_cg_solve(fg_state* s, const FgCgArgs& a, fg_solve_info* info_host, hipStream_t st, FgCgOutcome* out = nullptr);
 
 // BiCGStab on the stencil-form advection matrix (fg_bicgstab.hip)
+// The first kernels of the corrector -- k_h, the divergence kernel -- launched BEHIND the sweeps' check kernel, before the host knows
+// the verdict (on-chip form, one planned pass writing the result vector): they read what the sweeps left and write h, the right-hand
+// side and the CG's start, so the velocity solve's own device state (flags, sums) is gone once they ran -- a verdict that does not
+// end the solve there (0.6 % of the soak's solves: profiles/r05_soak_first_iterate.jsonl) is FG_SWEEP_SPEC_MISSED.
+struct FgSpecHook { int (*fn)(void* ctx) = nullptr; void* ctx = nullptr; };
 struct FgBicgArgs {
     const fg_real* diag; const fg_real* off;  // [B,N], [B,2d,N]
     const fg_real* rhs; fg_real* x;           // [B,nc,N]
@@ -974,21 +995,29 @@ struct FgBicgArgs {
                        // separable Helmholtz operator I/dt - nu Laplacian (fast diagonalisation, fg_fd_helmholtz_apply)
     fg_real nu = 0; int wall_lo = 1, wall_hi = 1;   // precond == 2: diffusivity of this solve; the variable is prescribed at the -y / +y wall
     int kind = 1;      // which poll predictor the solve reads and updates (fg_state::pred_bicg): 0 scalar, 1 velocity
+    FgSpecHook spec;   // optional
 };
-int fg_bicgstab_solve(fg_state* s, const FgBicgArgs& a, fg_solve_info* info_host, hipStream_t st);
+// *spec_ran (optional): the kernels of a.spec ran on the result of this solve
+int fg_bicgstab_solve(fg_state* s, const FgBicgArgs& a, fg_solve_info* info_host, hipStream_t st, bool* spec_ran = nullptr);
 #if !FG_F64
-// stationary sweeps instead of the Krylov iteration where the rows are diagonally dominant (fg_jacobi.hip); *outcome: 0 not tried,
-// 1 solved, 2 given up -- then the caller runs BiCGStab from a cleared start vector behind a fresh k_bicg_begin
+// stationary sweeps instead of the Krylov iteration where the rows are diagonally dominant (fg_jacobi.hip)
+enum FgSweepOutcome {
+    FG_SWEEP_NOT_TRIED,     // the kind is backing off: the prepared solve state is untouched
+    FG_SWEEP_SOLVED,
+    FG_SWEEP_SOLVED_SPEC,   // solved, and the kernels of FgSpecHook ran on the result
+    FG_SWEEP_GAVE_UP,       // the caller runs its Krylov solver from a cleared start vector behind a fresh k_bicg_begin
+    FG_SWEEP_SPEC_MISSED,   // the kernels of FgSpecHook overwrote the state of a solve that was not over: the whole solve again, without them
+};
 bool fg_jacobi_ok(const fg_state* s, const FgBicgArgs& a);
 // line sweeps x <- (D + O_y)^-1 (b - O_x x) for the Helmholtz-preconditioned family (wall-refined 2-D grids: RBC); fg_linepre.hip, round 6
 bool fg_linesweep_ok(const fg_state* s, const FgBicgArgs& a);
-int fg_linesweep_solve(fg_state* s, const FgBicgArgs& a, fg_solve_info* info_host, hipStream_t st, int* outcome);
-int fg_jacobi_solve(fg_state* s, const FgBicgArgs& a, fg_solve_info* info_host, hipStream_t st, int* outcome);
+int fg_linesweep_solve(fg_state* s, const FgBicgArgs& a, fg_solve_info* info_host, hipStream_t st, FgSweepOutcome* outcome);
+int fg_jacobi_solve(fg_state* s, const FgBicgArgs& a, fg_solve_info* info_host, hipStream_t st, FgSweepOutcome* outcome);
 #endif
 // fp64 repeats of failed solves (fg_rung64.h; fp32 library only): every system of an env that has a failed one (BiCGStab: not
-// converged; CG: non-finite), info_host updated in place; returns the status of the repeated solves
+// converged; CG: non-finite), info_host updated in place; returns the status of the repeated solves (*out: the result is stored in a.x)
 int fg_rung64_bicgstab(fg_state* s, const FgBicgArgs& a, fg_solve_info* info_host, bool all_systems, hipStream_t st);
-int fg_rung64_cg(fg_state* s, const FgCgArgs& a, fg_solve_info* info_host, bool all_envs, hipStream_t st);
+int fg_rung64_cg(fg_state* s, const FgCgArgs& a, fg_solve_info* info_host, bool all_envs, hipStream_t st, FgCgOutcome* out);
 
 // z-marching 3-D variants (fg_poisson3d.hip)
 bool fg_zmarch_ok(const fg_state* s, int* zc_out);
@@ -1032,7 +1061,7 @@ struct FgCgLead;    // fg_cg.h
 int fg_fd_tridiag(fg_state* s, float* cur, hipStream_t st, const FgCgLead* lead, bool use_rowmean = false, const float* factor_from = nullptr, const float* factor_dt = nullptr);
 bool fg_fd_tridiag_can_factor(const fg_state* s);      // the tridiagonal launch can make the row-mean factors itself (round 6)   // the per-mode Thomas solve of fg_fd_apply alone (in place); use_rowmean: the per-env factors of fg_fd_rowmean_factor
 bool fg_fd_rowmean_ok(const fg_state* s);
-int fg_refine64_pressure(fg_state* s, const FgCgArgs& a0, fg_solve_info* info_host, hipStream_t st);   // fg_poisson.hip (fp32 library only)
+int fg_refine64_pressure(fg_state* s, const FgCgArgs& a0, fg_solve_info* info_host, hipStream_t st, FgCgOutcome* out);   // fg_poisson.hip (fp32 library only)
 int fg_fd_rowmean_factor(fg_state* s, const float* rA, const float* dt, hipStream_t st, const float* row_part = nullptr, int tiles_x = 0);
 // the factors for the CURRENT 1/A field ahead of the pressure solves that will want them (fg_cg_solve then finds them made): launched
 // behind a polled kernel, the factorisation -- 14 us, latency-sized, independent of the velocity solve -- runs while the host turns the

@@ -580,15 +580,13 @@ bool fg_jacobi_ok(const fg_state* s, const FgBicgArgs& a) {
     return jac_onchip_ok(s, a) || jac_stream_ok(s, a);
 }
 
-static int jacobi_stream_solve(fg_state* s, const FgBicgArgs& a, fg_solve_info* info_host, hipStream_t st, int* outcome);
+static int jacobi_stream_solve(fg_state* s, const FgBicgArgs& a, fg_solve_info* info_host, hipStream_t st, FgSweepOutcome* outcome);
 
-// *outcome: 0 = not tried (the kind is backing off: the prepared solve state is untouched), 1 = solved here, 2 = tried and given up --
-// the caller then runs BiCGStab from a cleared start vector behind a fresh k_bicg_begin
-int fg_jacobi_solve(fg_state* s, const FgBicgArgs& a, fg_solve_info* info_host, hipStream_t st, int* outcome) {
-    *outcome = 0;
+int fg_jacobi_solve(fg_state* s, const FgBicgArgs& a, fg_solve_info* info_host, hipStream_t st, FgSweepOutcome* outcome) {
+    *outcome = FG_SWEEP_NOT_TRIED;
     FgJacHist& H = s->jac_hist[a.kind & 3];
     if (H.skip > 0) { --H.skip; return FG_OK; }
-    *outcome = 2;
+    *outcome = FG_SWEEP_GAVE_UP;
     if (!jac_onchip_ok(s, a)) return jacobi_stream_solve(s, a, info_host, st, outcome);
     const FgGrid& G = s->grid;
     const int B = G.B, n = G.n, nsys = 2 * B;
@@ -637,8 +635,8 @@ int fg_jacobi_solve(fg_state* s, const FgBicgArgs& a, fg_solve_info* info_host, 
         // (something for the GPU to do while the host turns the poll around: the pressure preconditioner's factors for this 1/A)
         if (a.diag == s->A && s->jac_prefactor) if (int rc = fg_fd_rowmean_prefactor(s, a.dt, st)) return rc;
         // (and the corrector's first kernels, when this check is expected to end the solve with the iterate in the result vector)
-        if (!spec_tried && s->jac_spec && s->jac_spec_fn && P == 1 && passes == 1 && last_parity == 0 && a.diag == s->A) {
-            if (int rc = s->jac_spec_fn(s->jac_spec_ctx)) return rc;
+        if (!spec_tried && s->jac_spec && a.spec.fn && P == 1 && passes == 1 && last_parity == 0 && a.diag == s->A) {
+            if (int rc = a.spec.fn(a.spec.ctx)) return rc;
             spec = true;
         }
         spec_tried = true;
@@ -691,7 +689,7 @@ int fg_jacobi_solve(fg_state* s, const FgBicgArgs& a, fg_solve_info* info_host, 
         if (all && !failed) { ok = true; break; }
         if (spec) {      // the speculated kernels ran on an iterate that is not the result and reset this solve's device state: once more, without
             if (int prc = fg_prof_collect(s, st)) return prc;
-            *outcome = 5;
+            *outcome = FG_SWEEP_SPEC_MISSED;
             return FG_OK;
         }
         if (failed) break;
@@ -715,10 +713,7 @@ int fg_jacobi_solve(fg_state* s, const FgBicgArgs& a, fg_solve_info* info_host, 
         const int used = s->info_pinned[2 * b].used_iterations + 1;
         if (used > 0) { settle |= (((used / S - 1) & 1) != last_parity) ? 1 : 0; used_max = used > used_max ? used : used_max; }
     }
-    if (spec) {
-        if (settle) { fg_set_error("fg_jacobi_solve: speculated corrector kernels with an iterate outside the result vector"); return FG_ERR_HIP; }
-        s->jac_spec_done = 1;
-    }
+    if (spec && settle) { fg_set_error("fg_jacobi_solve: speculated corrector kernels with an iterate outside the result vector"); return FG_ERR_HIP; }
     if (settle)
         hipLaunchKernelGGL(k_jac_settle, dim3(32, B), dim3(256), 0, st, (const float*)work, a.x, (const fg_solve_info*)s->info_dev, S, last_parity, 2 * n);
     H.fails = 0;
@@ -727,7 +722,7 @@ int fg_jacobi_solve(fg_state* s, const FgBicgArgs& a, fg_solve_info* info_host, 
         if (info_host) info_host[i] = s->info_pinned[i];
     FG_HIP_CHECK(hipGetLastError());
     fg_htrace("jac_return");
-    *outcome = 1;
+    *outcome = spec ? FG_SWEEP_SOLVED_SPEC : FG_SWEEP_SOLVED;
     return FG_OK;
 }
 
@@ -736,7 +731,7 @@ int fg_jacobi_solve(fg_state* s, const FgBicgArgs& a, fg_solve_info* info_host, 
 // history only decides where the first poll sits, so the iterate does not depend on it.  Every odd sweep from the fourth on sums the
 // residual of the iterate it started from (a check reads the last two: the contraction per sweep for the host); sweep k writes
 // the buffer that makes every check point end in the result vector.
-static int jacobi_stream_solve(fg_state* s, const FgBicgArgs& a, fg_solve_info* info_host, hipStream_t st, int* outcome) {
+static int jacobi_stream_solve(fg_state* s, const FgBicgArgs& a, fg_solve_info* info_host, hipStream_t st, FgSweepOutcome* outcome) {
     // (a check judges the iterate its last sweep STARTED from, so odd counts -- 5, 7, ... -- from a zero start, where sweep 0 may write the
     //  result vector; a start from the result vector has to write the work buffer first: even counts)
     // (from the block velocity -- jac_warm_start -- nothing but the measuring sweeps bounds the first check: 3, 5, ...)
@@ -824,7 +819,7 @@ static int jacobi_stream_solve(fg_state* s, const FgBicgArgs& a, fg_solve_info* 
     if (int prc = fg_prof_collect(s, st)) return prc;
     if (!ok) {
         H.fails += 1; H.skip = H.fails > 6 ? 512 : (4 << H.fails); H.sweeps = 0;
-        return FG_OK;      // *outcome stays 2: BiCGStab from a cleared start vector
+        return FG_OK;      // (*outcome stays FG_SWEEP_GAVE_UP)
     }
     int used_max = 0;
     for (int i = 0; i < nsys; ++i) {
@@ -834,7 +829,7 @@ static int jacobi_stream_solve(fg_state* s, const FgBicgArgs& a, fg_solve_info* 
         if (s->info_pinned[i].converged && s->info_pinned[i].used_iterations >= 0 && s->info_pinned[i].final_residual >= a.tol) s->jac_floor_released += 1;
     }
     H.fails = 0; H.sweeps = used_max > 0 ? used_max : FIRST;
-    *outcome = 1;
+    *outcome = FG_SWEEP_SOLVED;
     return FG_OK;
 }
 #endif

@@ -797,19 +797,18 @@ int fg_line_apply(fg_state* s, const float* diag, const float* off, int nc, cons
     return FG_OK;
 }
 
-// ---- line sweeps: driver.  *outcome: 0 not tried (the kind is backing off), 1 solved, 2 given up (the caller runs its Krylov solver
-// from a cleared start vector behind a fresh k_bicg_begin).  Check points at FIXED sweep counts (6, 8, ... 20) with the verdict on the
+// ---- line sweeps: driver (*outcome: FgSweepOutcome, fg_internal.h).  Check points at FIXED sweep counts (6, 8, ... 20) with the verdict on the
 // device, per system; the host's give-up rule reads the residuals the FIRST two measuring sweeps left (sweeps 3 and 5), so which
 // solver runs is a function of the system, not of where the previous solve of the kind made this one poll first.
 bool fg_linesweep_ok(const fg_state* s, const FgBicgArgs& a) {
     return s->adv_linesweep && a.precond == 2 && s->grid.dims == 2 && s->grid.nz == 1 && a.nc <= 2 && s->jac_prev != nullptr && (s->grid.nx & 3) == 0 &&
            line_lds_bytes(s) <= 160 * 1024;
 }
-int fg_linesweep_solve(fg_state* s, const FgBicgArgs& a, fg_solve_info* info_host, hipStream_t st, int* outcome) {
-    *outcome = 0;
+int fg_linesweep_solve(fg_state* s, const FgBicgArgs& a, fg_solve_info* info_host, hipStream_t st, FgSweepOutcome* outcome) {
+    *outcome = FG_SWEEP_NOT_TRIED;
     FgJacHist& H = s->jac_hist[a.kind & 3];
     if (H.skip > 0) { --H.skip; return FG_OK; }
-    *outcome = 2;
+    *outcome = FG_SWEEP_GAVE_UP;
     if (!line_use_lds(s)) return FG_OK;
     if (int rc = fg_line_alloc(s)) return rc;
     constexpr int FIRST = 6, STEP = 2, CHECKS = 8;
@@ -882,6 +881,6 @@ int fg_linesweep_solve(fg_state* s, const FgBicgArgs& a, fg_solve_info* info_hos
         if (info_host) info_host[i] = s->info_pinned[i];
     }
     H.fails = 0; H.sweeps = used_max > 0 ? used_max : FIRST;
-    *outcome = 1;
+    *outcome = FG_SWEEP_SOLVED;
     return FG_OK;
 }

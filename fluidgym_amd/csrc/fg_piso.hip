@@ -899,13 +899,13 @@ inline dim3 stride_grid(const fg_state* s, long per_env_elems) {
 }  // namespace
 
 
-int fg_launch_adv_build(const fg_state* s, const FgBounds& bnd, const FgAdvArgs& a_in, hipStream_t st) {
+int fg_launch_adv_build(fg_state* s, const FgBounds& bnd, const FgAdvArgs& a_in, hipStream_t st) {
     // the state of the BiCGStab solve that follows is prepared by this launch (FgBicgBegin, fg_internal.h; fg_bicgstab_solve skips its
     // k_bicg_begin when the record matches its own arguments)
     FgAdvArgs a = a_in;
     a.begin.acc = s->acc; a.begin.sc = s->scratch_B + 4 * s->grid.B; a.begin.flags = s->flags; a.begin.info = s->info_dev;
     a.begin.nc = a.for_scalar ? 1 : s->grid.dims;
-    s->bicg_ready_nc = a.begin.nc; s->bicg_ready_dt = a.dt; s->cg_ready_ns = 0;
+    s->prepared.set_bicg(a.begin.nc, a.dt);
     // live profile: u (d) + the matrix (1 + 2 d) + the right-hand sides (d) written, u and the source read: 44 B per cell in 2-D, 56 in 3-D
     const double nd = (double)s->grid.n;
     const int slot = fg_prof_slot(s, FG_PK_ADV_BUILD, nullptr, s->grid.B, (s->grid.dims == 3 ? 56.0 : 44.0) * nd, 30.0 * nd, st);
@@ -1034,14 +1034,14 @@ int fg_launch_pressure_setup(const fg_state* s, const fg_real* dt, hipStream_t s
     return FG_OK;
 }
 
-int fg_launch_h(const fg_state* s, const fg_real* dt, const fg_real* vel_result, hipStream_t st) {
+int fg_launch_h(fg_state* s, const fg_real* dt, const fg_real* vel_result, hipStream_t st) {
     // the state of the pressure CG that follows is prepared by this launch (FgCgBegin, fg_cg.h; fg_cg_solve skips its k_cg_begin when
     // the record matches its own arguments)
     fg_htrace("h_launch_in");
     FgCgBegin begin;
     begin.acc = s->cg_acc; begin.flags = s->flags; begin.info = s->info_dev; begin.mean_sums = s->acc; begin.best = s->cg_best;
     begin.track_best = s->cg_return_best; begin.ns = fg_cg_slots(s); begin.xsum = s->fcg_xsum;
-    s->cg_ready_ns = begin.ns; s->cg_ready_best = begin.track_best; s->cg_ready_dt = dt; s->bicg_ready_nc = 0; s->cg_start_ready = 0;
+    s->prepared.set_cg(begin.ns, begin.track_best, dt);
     const int slot_h = fg_prof_slot(s, FG_PK_H, nullptr, s->grid.B, (s->grid.dims == 3 ? 68.0 : 52.0) * (double)s->grid.n, 6.0 * s->grid.dims * s->grid.dims * (double)s->grid.n, st);
     FG_DISPATCH(s, {
         const FgLaunch L = fg_launch_geometry<DIMS, VEC>(s->grid);
@@ -1053,24 +1053,24 @@ int fg_launch_h(const fg_state* s, const fg_real* dt, const fg_real* vel_result,
     return FG_OK;
 }
 
-int fg_launch_div(const fg_state* s, const FgBounds& bnd, const fg_real* dt, const fg_real* hvec, fg_real* div,
+int fg_launch_div(fg_state* s, const FgBounds& bnd, const fg_real* dt, const fg_real* hvec, fg_real* div,
                   hipStream_t st, bool cg_from_zero, bool fused_fwd) {
     // cg_from_zero: the pressure CG on this right-hand side starts from the zero vector and its state was prepared by the k_h in
     // front of this launch -- then this kernel also starts it (FgCgStart: r = b into w[0], x = 0 into p_result, r.r) and fg_cg_solve
     // finds the record and skips k_cg_residual
     FgCgStart start = {nullptr, nullptr, nullptr, 1};
-    s->cg_start_ready = 0;
-    if (cg_from_zero && dt != nullptr && s->cg_ready_ns > 0 && s->cg_ready_dt == dt && div == s->div) {
+    s->prepared.set_cg_start(0);
+    if (cg_from_zero && dt != nullptr && s->prepared.cg_for(dt) && div == s->div) {
 #if !FG_F64
         if (fused_fwd && fg_fcg_ok(s)) {
             // fused CG on a fast-transform grid: one row kernel writes the right-hand side, starts the solve AND transforms r_0
             // (k_fcg_div_fwd, fg_fftcg.hip); fg_cg_solve finds the record (2) and goes straight to the tridiagonal solve
-            s->cg_start_ready = 2;
-            return fg_fcg_div_fwd(const_cast<fg_state*>(s), bnd, dt, hvec, div, s->cg_ready_ns, st);
+            s->prepared.set_cg_start(2);
+            return fg_fcg_div_fwd(s, bnd, dt, hvec, div, s->prepared.cg_ns, st);
         }
 #endif
-        start.acc = s->cg_acc; start.r = s->w[0]; start.x = s->p_result; start.ns = s->cg_ready_ns;
-        s->cg_start_ready = 1;
+        start.acc = s->cg_acc; start.r = s->w[0]; start.x = s->p_result; start.ns = s->prepared.cg_ns;
+        s->prepared.set_cg_start(1);
     }
     const int slot_d = fg_prof_slot(s, FG_PK_DIV, nullptr, s->grid.B, 28.0 * (double)s->grid.n, 4.0 * s->grid.dims * (double)s->grid.n, st);
     FG_DISPATCH(s, {

@@ -399,7 +399,6 @@ int fg_poisson_rbgs_launch(const fg_state* s, const fg_real* rA, const fg_real* 
     return FG_OK;
 }
 
-// Host driver of the batched CG.  p is double-buffered: a.p is buffer 0, s->w[6] buffer 1.
 int fg_fd_rowmean_prefactor(fg_state* s, const fg_real* dt, hipStream_t st) {
 #if !FG_F64
     if (!(s->fd_Qx && fg_fcg_ok(s) && fg_fd_rowmean_ok(s)) || s->fd_row_epoch == s->rA_epoch || dt == nullptr) return FG_OK;
@@ -421,189 +420,201 @@ int fg_cg_slots(const fg_state* s) {   // ~cg_wgs_per_slot workgroups per accumu
     return ns;
 }
 
-int fg_cg_solve(fg_state* s, const FgCgArgs& a, fg_solve_info* info_host, hipStream_t st) {
-    const int B = s->grid.B, n = s->grid.n;
-    const dim3 sg(B), sb(64);
-    fg_real* pbuf[2] = {a.p, s->w[6]};
-    int tiles_per_env = 1;
-    FG_DISPATCH(s, { tiles_per_env = fg_launch_geometry<DIMS, VEC>(s->grid).tiles; });
-    int zc = 0;
-    const bool zmarch = fg_zmarch_ok(s, &zc);
-    const int ns = fg_cg_slots(s);
-    (void)tiles_per_env;
+namespace {
+// what the parts of fg_cg_solve share
+struct CgRun {
+    int ns, nb, check_every, next_poll;
+    fg_real* zvec;
+    FgDacc* mean_sums;      // != nullptr: sum(x) rides in the update kernels
+    FgCgJudge judge;
+    bool fused;
     bool start_ready = false;      // k_div started this solve (FgCgStart): no k_cg_residual launch
-    bool start_fwd = false;
-    {   // state already prepared by the k_div that built this right-hand side (FgCgBegin, fg_cg.h)?
-        const bool ready = s->cg_ready_ns == ns && s->cg_ready_best == s->cg_return_best && s->cg_ready_dt == a.dt;
-        start_ready = ready && s->cg_start_ready && !a.use_x0 && a.b == s->div && a.r == s->w[0] && a.x == s->p_result;
-        start_fwd = start_ready && s->cg_start_ready == 2;      // ... and w[3] holds Qx^T r_0 (k_fcg_div_fwd)
-        (void)start_fwd;
-        s->cg_ready_ns = 0; s->bicg_ready_nc = 0; s->cg_start_ready = 0;
-        if (!ready) {
+    bool start_fwd = false;        // ... and w[3] holds Qx^T r_0 (k_fcg_div_fwd)
+    bool done = false, info_fresh = false;
+};
+}  // namespace
+
+// begin: the solve's device state (prepared by the kernels in front of it, FgPrepared, or here), the first residual, z_0 of the classic form
+static int cg_begin(fg_state* s, const FgCgArgs& a, CgRun& c, hipStream_t st) {
+    const int B = s->grid.B, n = s->grid.n;
+    const int ns = c.ns = fg_cg_slots(s);
+    {
+        const int prep = s->prepared.take_cg(ns, s->cg_return_best, a.dt);
+        c.start_ready = prep > 0 && !a.use_x0 && a.b == s->div && a.r == s->w[0] && a.x == s->p_result;
+        c.start_fwd = c.start_ready && prep == 2;
+        if (prep < 0) {
             FgCgBegin q;
             q.acc = s->cg_acc; q.flags = s->flags; q.info = s->info_dev; q.mean_sums = s->acc; q.best = s->cg_best;
             q.track_best = s->cg_return_best; q.ns = ns; q.xsum = s->fcg_xsum;
-            hipLaunchKernelGGL(k_cg_begin, sg, sb, 0, st, a.dt, q, B);
+            hipLaunchKernelGGL(k_cg_begin, dim3(B), dim3(64), 0, st, a.dt, q, B);
         }
     }
-    if (!start_ready)
+    if (!c.start_ready)
     FG_DISPATCH(s, {
         const FgLaunch L = fg_launch_geometry<DIMS, VEC>(s->grid);
         hipLaunchKernelGGL((k_cg_residual<DIMS, VEC>), L.grid, dim3(FG_BLOCK), 0, st, s->grid, a.rA, a.b, a.x, a.r,
                            s->cg_acc, s->flags, a.use_x0, 0, ns, L.tiles_x, L.tiles_y, L.tiles);
     });
-    const int check_every = a.check_every > 0 ? a.check_every : 16;
-    const int nb = a.precond ? 5 : 0;
-    const int acc_stride = FG_CG_NAMES * FG_CG_SLOTS;
-    fg_real* zvec = a.precond ? s->w[5] : a.r;
-    FgCgJudge judge;
-    judge.acc = s->cg_acc; judge.flags = s->flags; judge.info = s->info_dev; judge.tol = a.tol; judge.it = -1; judge.n = n; judge.ns = ns;
-    s->fcg_mean_ready = 0;
-    s->fcg_check0_ran = 0; s->fcg_lazy_on = 0; s->fcg_spec_done = 0;
+    c.check_every = a.check_every > 0 ? a.check_every : 16;
+    c.nb = a.precond ? 5 : 0;
+    c.zvec = a.precond ? s->w[5] : a.r;
+    c.judge.acc = s->cg_acc; c.judge.flags = s->flags; c.judge.info = s->info_dev; c.judge.tol = a.tol; c.judge.it = -1; c.judge.n = n; c.judge.ns = ns;
 #if !FG_F64
-    const bool fused = a.precond && s->fd_Qx && fg_fcg_ok(s);
+    c.fused = a.precond && s->fd_Qx && fg_fcg_ok(s);
 #else
-    const bool fused = false;
+    c.fused = false;
 #endif
-    if (a.precond && !fused) {
+    if (a.precond && !c.fused) {
         if (!s->fd_Qx) { fg_set_error("preconditioned CG requested but fg_set_fd_preconditioner was not called"); return FG_ERR_INVALID_ARG; }
         // z0 = M^-1 r0, r0.z0; the residual check of x0 (flags for already-converged envs) is taken by the first kernel of the
         // application (FgCgJudge, fg_cg.h) -- as is the one after every iteration below: no k_cg_check launch outside the polls
-        judge.it = -1;
-        if (int rc = fg_fd_apply(s, a.r, zvec, s->cg_acc + (size_t)(nb + 0) * FG_CG_SLOTS, acc_stride, ns, B, st, &judge)) return rc;
+        if (int rc = fg_fd_apply(s, a.r, c.zvec, s->cg_acc + (size_t)(c.nb + 0) * FG_CG_SLOTS, FG_CG_NAMES * FG_CG_SLOTS, ns, B, st, &c.judge)) return rc;
     }
-    bool done = false, info_fresh = false;
-    int active_est = (B + 3) / 4;  // envs expected to still iterate after the first iteration, refreshed by every poll
-    int next_poll = a.precond ? (s->pred_cg[a.kind & 3] + 1 > 1 ? s->pred_cg[a.kind & 3] + 1 : 1) : check_every;
+    c.next_poll = a.precond ? (s->pred_cg[a.kind & 3] + 1 > 1 ? s->pred_cg[a.kind & 3] + 1 : 1) : c.check_every;
     // sum(x) rides in the update kernels when the solve starts from zero inside the PISO step (a.x = pressureResult): the mean removal
-    // then needs no pass of its own (fcg_mean_ready, consumed by fg_piso_step's last corrector)
-    FgDacc* mean_sums = (!a.use_x0 && a.x == s->p_result && s->fcg_xsum) ? s->fcg_xsum : nullptr;
-    int it = 0;
+    // then needs no pass of its own (FgCgOutcome::mean_ready, consumed by fg_piso_step's last corrector)
+    c.mean_sums = (!a.use_x0 && a.x == s->p_result && s->fcg_xsum) ? s->fcg_xsum : nullptr;
+    return FG_OK;
+}
+
 #if !FG_F64
-    if (fused) {
-        // Three launches per iteration (fg_fftcg.hip): F'(it) = vector updates + forward transform, L = verdict + per-mode Thomas solve,
-        // I'(it + 1) = inverse transform + operator + dot products.  Polls sit behind F' exactly where they sat behind k_cg_update.
-        FcgVectors v;
-        v.x = a.x; v.r = a.r; v.t1 = s->w[3]; v.z = zvec; v.w = s->w[4]; v.p = a.p; v.s = a.Ap;
-        FgCgLead lead;
-        lead.best = s->cg_best;
-        // preconditioner of this solve: the row-mean operator (per-env factors, made once per 1/A field: both correctors of a PISO
-        // step share them) where it applies, the grid's A = 1 operator otherwise
-        const bool rowm = fg_fd_rowmean_ok(s);
-        const float* factor_from = nullptr;      // != nullptr: the first tridiagonal launch of this solve makes the factors (round 6)
-        if (rowm && !(a.rA == s->rA && s->fd_row_epoch == s->rA_epoch)) {
-            const bool parts = a.rA == s->rA && s->fd_row_part && s->fd_row_part_epoch == s->rA_epoch;      // the assembly left the row sums
-            if (parts && fg_fd_tridiag_can_factor(s)) factor_from = s->fd_row_part;
-            else if (int rc = fg_fd_rowmean_factor(s, a.rA, a.dt, st, parts ? s->fd_row_part : nullptr, (s->grid.nx + 63) / 64)) return rc;
-            s->fd_row_epoch = (a.rA == s->rA) ? s->rA_epoch : -1;
+// Three launches per iteration (fg_fftcg.hip): F'(it) = vector updates + forward transform, L = verdict + per-mode Thomas solve,
+// I'(it + 1) = inverse transform + operator + dot products.  Polls sit behind F' exactly where they sat behind k_cg_update.
+static int cg_iterate_fused(fg_state* s, const FgCgArgs& a, CgRun& c, FgCgOutcome& o, hipStream_t st) {
+    const int B = s->grid.B, n = s->grid.n, ns = c.ns;
+    FgCgJudge& judge = c.judge;
+    FcgVectors v;
+    v.x = a.x; v.r = a.r; v.t1 = s->w[3]; v.z = c.zvec; v.w = s->w[4]; v.p = a.p; v.s = a.Ap;
+    FgCgLead lead;
+    lead.best = s->cg_best;
+    // preconditioner of this solve: the row-mean operator (per-env factors, made once per 1/A field: both correctors of a PISO
+    // step share them) where it applies, the grid's A = 1 operator otherwise
+    const bool rowm = fg_fd_rowmean_ok(s);
+    const float* factor_from = nullptr;      // != nullptr: the first tridiagonal launch of this solve makes the factors (round 6)
+    if (rowm && !(a.rA == s->rA && s->fd_row_epoch == s->rA_epoch)) {
+        const bool parts = a.rA == s->rA && s->fd_row_part && s->fd_row_part_epoch == s->rA_epoch;      // the assembly left the row sums
+        if (parts && fg_fd_tridiag_can_factor(s)) factor_from = s->fd_row_part;
+        else if (int rc = fg_fd_rowmean_factor(s, a.rA, a.dt, st, parts ? s->fd_row_part : nullptr, (s->grid.nx + 63) / 64)) return rc;
+        s->fd_row_epoch = (a.rA == s->rA) ? s->rA_epoch : -1;
+    }
+    judge.it = -1;
+    if (!c.start_fwd)      // (k_fcg_div_fwd already transformed r_0: the verdict on x_0 is the tridiagonal kernel's alone)
+        if (int rc = fg_fd_dct_forward(s, a.r, v.t1, st, 0, &judge)) return rc;      // u = Qx^T r_0 (the verdict on x_0 rides here)
+    lead.judge = judge;
+    if (int rc = fg_fd_tridiag(s, v.t1, st, &lead, rowm, factor_from, a.dt)) return rc;
+    // a solve started by k_fcg_div_fwd never stored r_0 = b and x_0 = 0: until the first update has written r and x, r is the
+    // right-hand side itself and x is known
+    const fg_real* r0 = c.start_fwd ? a.b : nullptr;
+    {
+        FcgVectors v0 = v;
+        if (r0) v0.r = const_cast<fg_real*>(r0);      // (read only by the inverse kernel)
+        if (int rc = fg_fcg_inv_apply(s, v0, a.rA, 0, ns, st, s->fcg_first)) return rc;
+    }
+    if (s->fcg_first && a.max_iterations >= 1) {
+        // C(0): the first iterate is judged from I'(0)'s dot products (k_fcg_check0).  Polled when the previous solve of this kind
+        // ended after one iteration: if every env ends here nothing is left to do but write x_1 = alpha z -- or not even that
+        // (lazy_ok: the corrector reads alpha z itself)
+        const bool poll0 = c.next_poll <= 1;
+        const FgPollOut po = poll0 ? fg_poll_next(&s->poll) : FgPollOut{nullptr, 0};
+        if (poll0) fg_prof_prefetch(s, st);
+        if (int rc = fg_fcg_check0(s, a.tol, ns, st, po, &o.marks_valid)) return rc;
+        bool spec = false;
+        if (poll0 && s->fcg_spec && a.spec.fn && a.lazy_ok && r0 && c.mean_sums) {
+            // the corrector in its unstored-pressure form, behind the verdict kernel: it runs while the host waits (FgCgSpec)
+            FgCgOutcome ahead;
+            ahead.lazy_z = v.z; ahead.mean_ready = true; ahead.marks_valid = true;
+            if (int rc = a.spec.fn(a.spec.ctx, ahead)) return rc;
+            spec = true;
         }
-        judge.it = -1;
-        if (!(start_ready && start_fwd))      // (k_fcg_div_fwd already transformed r_0: the verdict on x_0 is the tridiagonal kernel's alone)
-            if (int rc = fg_fd_dct_forward(s, a.r, v.t1, st, 0, &judge)) return rc;      // u = Qx^T r_0 (the verdict on x_0 rides here)
-        lead.judge = judge;
-        if (int rc = fg_fd_tridiag(s, v.t1, st, &lead, rowm, factor_from, a.dt)) return rc;
-        // a solve started by k_fcg_div_fwd never stored r_0 = b and x_0 = 0: until the first update has written r and x, r is the
-        // right-hand side itself and x is known
-        const fg_real* r0 = (start_ready && start_fwd) ? a.b : nullptr;
-        {
-            FcgVectors v0 = v;
-            if (r0) v0.r = const_cast<fg_real*>(r0);      // (read only by the inverse kernel)
-            if (int rc = fg_fcg_inv_apply(s, v0, a.rA, 0, ns, st, s->fcg_first)) return rc;
-        }
-        if (s->fcg_first && a.max_iterations >= 1) {
-            // C(0): the first iterate is judged from I'(0)'s dot products (k_fcg_check0).  Polled when the previous solve of this kind
-            // ended after one iteration: if every env ends here nothing is left to do but write x_1 = alpha z -- or not even that
-            // (lazy_ok: the corrector reads alpha z itself)
-            const bool poll0 = next_poll <= 1;
-            const FgPollOut po = poll0 ? fg_poll_next(&s->poll) : FgPollOut{nullptr, 0};
-            if (poll0) fg_prof_prefetch(s, st);
-            if (int rc = fg_fcg_check0(s, a.tol, ns, st, po)) return rc;
-            bool spec = false;
-            if (poll0 && s->fcg_spec && s->fcg_spec_fn && a.lazy_ok && r0 && mean_sums) {
-                // the corrector in its unstored-pressure form, behind the verdict kernel: it runs while the host waits (fg_internal.h)
-                s->fcg_lazy_z = v.z;
-                if (int rc = s->fcg_spec_fn(s->fcg_spec_ctx)) return rc;
-                spec = true;
+        if (poll0) {
+            fg_htrace("cg_check_launched");
+            if (int rc = fg_poll_wait_infos(&s->poll, po, 0, B, s->info_pinned, st)) return rc;
+            fg_htrace("cg_poll_done");
+            c.info_fresh = true;
+            s->fcg_first_polls += 1;
+            bool all = true, all_ok = true;
+            for (int b = 0; b < B; ++b) {
+                all = all && (s->info_pinned[b].converged || !s->info_pinned[b].is_finite);
+                all_ok = all_ok && s->info_pinned[b].converged && s->info_pinned[b].is_finite;
             }
-            if (poll0) {
-                fg_htrace("cg_check_launched");
-                if (int rc = fg_poll_wait_infos(&s->poll, po, 0, B, s->info_pinned, st)) return rc;
-                fg_htrace("cg_poll_done");
-                info_fresh = true;
-                s->fcg_first_polls += 1;
-                bool all = true, all_ok = true;
-                for (int b = 0; b < B; ++b) {
-                    all = all && (s->info_pinned[b].converged || !s->info_pinned[b].is_finite);
-                    all_ok = all_ok && s->info_pinned[b].converged && s->info_pinned[b].is_finite;
-                }
-                if (all) {
-                    if (a.lazy_ok && r0 && all_ok && mean_sums) {
-                        s->fcg_lazy_on = 1; s->fcg_lazy_z = v.z; s->fcg_unstored += 1; s->fcg_spec_done = spec ? 1 : 0;
-                    } else {
-                        if (int rc = fg_fcg_update_fwd(s, v, 0, 1, ns, st, r0)) return rc;      // (every env takes the short path)
-                    }
-                    done = true;
+            if (all) {
+                if (a.lazy_ok && r0 && all_ok && c.mean_sums) {
+                    o.lazy_z = v.z; s->fcg_unstored += 1; o.spec_done = spec;
                 } else {
-                    next_poll = 2;
+                    if (int rc = fg_fcg_update_fwd(s, v, 0, 1, ns, st, o.marks_valid, r0)) return rc;      // (every env takes the short path)
                 }
+                c.done = true;
+            } else {
+                c.next_poll = 2;
             }
         }
-        int first = 1;
-        // restart period of THIS recurrence: s = P p is carried by a recurrence of its own here (s = w + beta s), so r and the true
-        // residual drift apart faster than in the classic form once a solve stagnates at fp32 round-off (a solve asked for more than
-        // fp32 can give then "improves" only in its recurrence: the best-iterate bookkeeping kept an iterate whose true residual was
-        // 1.7e-4 where the classic form keeps 6e-5, tests/test_gpu_parity.py::test_fd_preconditioner_fast_cosine_transform).  The
-        // true residual is therefore recomputed every ten iterations at the latest; solves of the envs take one to three.
-        const int fused_reset = (a.reset_steps > 0 && a.reset_steps < 10) ? a.reset_steps : 10;
-        for (; it < a.max_iterations && !done; ++it) {
-            if (int rc = fg_fcg_update_fwd(s, v, it, first, ns, st, it == 0 ? r0 : nullptr)) return rc;      // (first is 1 again after a restart: x and r exist by then)
-            if (first) {      // p_it = z_it, s_it = w_it: the buffers change roles instead of being copied
-                fg_real* t = v.p; v.p = v.z; v.z = t;
-                t = v.s; v.s = v.w; v.w = t;
-                first = 0;
-            }
-            const bool poll = (it + 1 >= next_poll || it + 1 == a.max_iterations);
-            if (poll) {
-                next_poll = it + 1 + check_every;
-                const int final_pass = (it + 1 == a.max_iterations);
-                fg_prof_prefetch(s, st);
-                const FgPollOut po = fg_poll_next(&s->poll);
-                hipLaunchKernelGGL(k_cg_check, dim3((B + CG_CHECK_WAVES - 1) / CG_CHECK_WAVES), dim3(64 * CG_CHECK_WAVES), 0, st, s->cg_acc, s->flags, s->info_dev, s->info_pinned, a.tol, it,
-                                   n, B, final_pass, ns, po);
-                fg_htrace("cg_check_launched");
-                if (int rc = fg_poll_wait_infos(&s->poll, po, 0, B, s->info_pinned, st)) return rc;
-                fg_htrace("cg_poll_done");
-                info_fresh = true;
-                done = true;
-                for (int b = 0; b < B; ++b) done = done && (s->info_pinned[b].converged || !s->info_pinned[b].is_finite);
-                if (done) break;
-            }
-            if (it + 1 < a.max_iterations) {
-                judge.it = it;
-                if ((it + 2) % fused_reset == 0) {
-                    // residual restart (cg_solver_kernel.cu:281-302): r = b - P x, then the recurrence starts over (beta = 0)
-                    hipLaunchKernelGGL(k_zero_name, sg, sb, 0, st, s->cg_acc, (it + 1) % 3, B);
-                    FG_DISPATCH(s, {
-                        const FgLaunch L = fg_launch_geometry<DIMS, VEC>(s->grid);
-                        hipLaunchKernelGGL((k_cg_residual<DIMS, VEC>), L.grid, dim3(FG_BLOCK), 0, st, s->grid, a.rA, a.b, a.x,
-                                           a.r, s->cg_acc, s->flags, 1, (it + 1) % 3, ns, L.tiles_x, L.tiles_y, L.tiles);
-                    });
-                    if (int rc = fg_fd_dct_forward(s, a.r, v.t1, st, 0, nullptr)) return rc;
-                    first = 1;
-                }
-                lead.judge = judge;
-                if (int rc = fg_fd_tridiag(s, v.t1, st, &lead, rowm)) return rc;
-                if (int rc = fg_fcg_inv_apply(s, v, a.rA, it + 1, ns, st)) return rc;
-            }
+    }
+    int first = 1;
+    // restart period of THIS recurrence: s = P p is carried by a recurrence of its own here (s = w + beta s), so r and the true
+    // residual drift apart faster than in the classic form once a solve stagnates at fp32 round-off (a solve asked for more than
+    // fp32 can give then "improves" only in its recurrence: the best-iterate bookkeeping kept an iterate whose true residual was
+    // 1.7e-4 where the classic form keeps 6e-5, tests/test_gpu_parity.py::test_fd_preconditioner_fast_cosine_transform).  The
+    // true residual is therefore recomputed every ten iterations at the latest; solves of the envs take one to three.
+    const int fused_reset = (a.reset_steps > 0 && a.reset_steps < 10) ? a.reset_steps : 10;
+    for (int it = 0; it < a.max_iterations && !c.done; ++it) {
+        if (int rc = fg_fcg_update_fwd(s, v, it, first, ns, st, o.marks_valid, it == 0 ? r0 : nullptr)) return rc;      // (first is 1 again after a restart: x and r exist by then)
+        if (first) {      // p_it = z_it, s_it = w_it: the buffers change roles instead of being copied
+            fg_real* t = v.p; v.p = v.z; v.z = t;
+            t = v.s; v.s = v.w; v.w = t;
+            first = 0;
         }
-        s->fcg_mean_ready = a.use_x0 ? 0 : 1;     // (sum(x) of a solve that takes no iteration is only known for x_0 = 0)
-    } else
+        const bool poll = (it + 1 >= c.next_poll || it + 1 == a.max_iterations);
+        if (poll) {
+            c.next_poll = it + 1 + c.check_every;
+            const int final_pass = (it + 1 == a.max_iterations);
+            fg_prof_prefetch(s, st);
+            const FgPollOut po = fg_poll_next(&s->poll);
+            hipLaunchKernelGGL(k_cg_check, dim3((B + CG_CHECK_WAVES - 1) / CG_CHECK_WAVES), dim3(64 * CG_CHECK_WAVES), 0, st, s->cg_acc, s->flags, s->info_dev, s->info_pinned, a.tol, it,
+                               n, B, final_pass, ns, po);
+            fg_htrace("cg_check_launched");
+            if (int rc = fg_poll_wait_infos(&s->poll, po, 0, B, s->info_pinned, st)) return rc;
+            fg_htrace("cg_poll_done");
+            c.info_fresh = true;
+            c.done = true;
+            for (int b = 0; b < B; ++b) c.done = c.done && (s->info_pinned[b].converged || !s->info_pinned[b].is_finite);
+            if (c.done) break;
+        }
+        if (it + 1 < a.max_iterations) {
+            judge.it = it;
+            if ((it + 2) % fused_reset == 0) {
+                // residual restart (cg_solver_kernel.cu:281-302): r = b - P x, then the recurrence starts over (beta = 0)
+                hipLaunchKernelGGL(k_zero_name, dim3(B), dim3(64), 0, st, s->cg_acc, (it + 1) % 3, B);
+                FG_DISPATCH(s, {
+                    const FgLaunch L = fg_launch_geometry<DIMS, VEC>(s->grid);
+                    hipLaunchKernelGGL((k_cg_residual<DIMS, VEC>), L.grid, dim3(FG_BLOCK), 0, st, s->grid, a.rA, a.b, a.x,
+                                       a.r, s->cg_acc, s->flags, 1, (it + 1) % 3, ns, L.tiles_x, L.tiles_y, L.tiles);
+                });
+                if (int rc = fg_fd_dct_forward(s, a.r, v.t1, st, 0, nullptr)) return rc;
+                first = 1;
+            }
+            lead.judge = judge;
+            if (int rc = fg_fd_tridiag(s, v.t1, st, &lead, rowm)) return rc;
+            if (int rc = fg_fcg_inv_apply(s, v, a.rA, it + 1, ns, st)) return rc;
+        }
+    }
+    o.mean_ready = !a.use_x0;     // (sum(x) of a solve that takes no iteration is only known for x_0 = 0)
+    return FG_OK;
+}
 #endif
-    for (; it < a.max_iterations && !done; ++it) {
+
+// the classic iteration: k_cg_ap + k_cg_update, with the preconditioner's kernels between the iterations.  p is double-buffered: a.p
+// is buffer 0, s->w[6] buffer 1.
+static int cg_iterate_classic(fg_state* s, const FgCgArgs& a, CgRun& c, FgCgOutcome& o, hipStream_t st) {
+    const int B = s->grid.B, n = s->grid.n, ns = c.ns, nb = c.nb;
+    fg_real* pbuf[2] = {a.p, s->w[6]};
+    int zc = 0;
+    const bool zmarch = fg_zmarch_ok(s, &zc);
+    int active_est = (B + 3) / 4;  // envs expected to still iterate after the first iteration, refreshed by every poll
+    for (int it = 0; it < a.max_iterations && !c.done; ++it) {
         int first = (it == 0);
         if (a.reset_steps > 0 && it > 0 && (it + 1) % a.reset_steps == 0) {
             // residual restart (cg_solver_kernel.cu:281-302): r = b - P x, p = r
-            hipLaunchKernelGGL(k_zero_name, sg, sb, 0, st, s->cg_acc, it % 3, B);
+            hipLaunchKernelGGL(k_zero_name, dim3(B), dim3(64), 0, st, s->cg_acc, it % 3, B);
             FG_DISPATCH(s, {
                 const FgLaunch L = fg_launch_geometry<DIMS, VEC>(s->grid);
                 hipLaunchKernelGGL((k_cg_residual<DIMS, VEC>), L.grid, dim3(FG_BLOCK), 0, st, s->grid, a.rA, a.b, a.x,
@@ -619,13 +630,13 @@ int fg_cg_solve(fg_state* s, const FgCgArgs& a, fg_solve_info* info_host, hipStr
         const int slot_ap = fg_prof_slot(s, FG_PK_CG_AP, FG_PROF_SELF, B, (double)n * (first ? 16.0 : 20.0),
                                          (double)n * (4.0 * s->grid.dims + 5.0), st);
         if (zmarch) {
-            if (int rc = fg_zmarch_cg_ap(s, a.rA, zvec, p_in, p_out, a.Ap, s->cg_acc, s->flags, s->info_dev, slot_ap,
+            if (int rc = fg_zmarch_cg_ap(s, a.rA, c.zvec, p_in, p_out, a.Ap, s->cg_acc, s->flags, s->info_dev, slot_ap,
                                          a.tol, it, first, ns, nb, zc, st))
                 return rc;
         } else {
             FG_DISPATCH(s, {
                 const FgLaunch L = fg_launch_geometry<DIMS, VEC>(s->grid);
-                FG_LAUNCH_P(s, slot_ap, (k_cg_ap<DIMS, VEC>), L.grid, dim3(FG_BLOCK), 0, st, s->grid, a.rA, zvec, p_in,
+                FG_LAUNCH_P(s, slot_ap, (k_cg_ap<DIMS, VEC>), L.grid, dim3(FG_BLOCK), 0, st, s->grid, a.rA, c.zvec, p_in,
                             p_out, a.Ap, s->cg_acc, s->flags, s->info_dev,
                             slot_ap >= 0 ? s->prof.active_dev + slot_ap : nullptr, s->cg_best, a.tol, it, first, ns,
                             nb, L.tiles_x, L.tiles_y, L.tiles);
@@ -635,10 +646,10 @@ int fg_cg_solve(fg_state* s, const FgCgArgs& a, fg_solve_info* info_host, hipStr
         FG_DISPATCH(s, {
             const FgLaunch L = fg_launch_geometry<DIMS, VEC>(s->grid);
             FG_LAUNCH_P(s, slot_up, (k_cg_update<DIMS, VEC>), L.grid, dim3(FG_BLOCK), 0, st, s->grid, p_out, a.Ap, a.x,
-                        a.r, s->cg_acc, s->flags, s->cg_best, a.tol, it, ns, nb, mean_sums, L.tiles_x, L.tiles_y, L.tiles);
+                        a.r, s->cg_acc, s->flags, s->cg_best, a.tol, it, ns, nb, c.mean_sums, L.tiles_x, L.tiles_y, L.tiles);
         });
-        const bool poll = (it + 1 >= next_poll || it + 1 == a.max_iterations);
-        if (poll) next_poll = it + 1 + check_every;
+        const bool poll = (it + 1 >= c.next_poll || it + 1 == a.max_iterations);
+        if (poll) c.next_poll = it + 1 + c.check_every;
         if (poll) {
             const int final_pass = (it + 1 == a.max_iterations);
             fg_prof_prefetch(s, st);       // (in front of the polled kernel: its completion then covers the copy)
@@ -651,26 +662,32 @@ int fg_cg_solve(fg_state* s, const FgCgArgs& a, fg_solve_info* info_host, hipStr
             // finished, so they usually end the solve, and three kernels of M^-1 that would find every env converged
             // cost more than the idle round trip of a poll that does not.
             if (int rc = fg_poll_wait_infos(&s->poll, po, 0, B, s->info_pinned, st)) return rc;
-            info_fresh = true;
-            done = true;
+            c.info_fresh = true;
+            c.done = true;
             active_est = 0;
             for (int b = 0; b < B; ++b) {
                 const bool fin = s->info_pinned[b].converged || !s->info_pinned[b].is_finite;
-                done = done && fin;
+                c.done = c.done && fin;
                 active_est += !fin;
             }
             if (active_est < 1) active_est = 1;
-            if (done) break;
+            if (c.done) break;
         }
         if (a.precond && it + 1 < a.max_iterations) {
             // z = M^-1 r and r.z of the next iteration (envs that just converged are skipped via flags)
-            judge.it = it;
-            if (int rc = fg_fd_apply(s, a.r, zvec, s->cg_acc + (size_t)(nb + (it + 1) % 3) * FG_CG_SLOTS, acc_stride, ns, active_est, st, &judge))
+            c.judge.it = it;
+            if (int rc = fg_fd_apply(s, a.r, c.zvec, s->cg_acc + (size_t)(nb + (it + 1) % 3) * FG_CG_SLOTS, FG_CG_NAMES * FG_CG_SLOTS, ns, active_est, st, &c.judge))
                 return rc;
         }
     }
-    if (!fused && mean_sums) s->fcg_mean_ready = 1;      // (a residual restart recomputes r only: the sums of x stay valid)
-    if (!info_fresh) {
+    if (c.mean_sums) o.mean_ready = true;      // (a residual restart recomputes r only: the sums of x stay valid)
+    return FG_OK;
+}
+
+// finish: info read-back, best-iterate restore, predictor update, status
+static int cg_finish(fg_state* s, const FgCgArgs& a, const CgRun& c, FgCgOutcome& o, fg_solve_info* info_host, hipStream_t st) {
+    const int B = s->grid.B, n = s->grid.n;
+    if (!c.info_fresh) {
         FG_HIP_CHECK(hipMemcpyAsync(s->info_pinned, s->info_dev, sizeof(fg_solve_info) * B, hipMemcpyDeviceToHost, st));
         FG_HIP_CHECK(hipStreamSynchronize(st));
     }
@@ -678,7 +695,7 @@ int fg_cg_solve(fg_state* s, const FgCgArgs& a, fg_solve_info* info_host, hipStr
     bool failed = false;
     for (int b = 0; b < B; ++b) failed = failed || !s->info_pinned[b].converged;
     if (failed) {  // rare path: hand back the best iterate instead of the last one (results land in the pinned mirror)
-        s->fcg_mean_ready = 0;     // (x may be replaced: its sum is no longer the one the update kernels left)
+        o.mean_ready = false;     // (x may be replaced: its sum is no longer the one the update kernels left)
         hipLaunchKernelGGL(k_cg_restore_best, dim3(32, B), dim3(FG_BLOCK), 0, st, a.x, s->info_dev, s->info_pinned, s->cg_best, n);
         FG_HIP_CHECK(hipStreamSynchronize(st));
     }
@@ -694,6 +711,21 @@ int fg_cg_solve(fg_state* s, const FgCgArgs& a, fg_solve_info* info_host, hipStr
         else if (!s->info_pinned[b].converged && rc == FG_OK) rc = FG_ERR_NOT_CONVERGED;
     }
     FG_HIP_CHECK(hipGetLastError());
+    return rc;
+}
+
+// Host driver of the batched CG
+int fg_cg_solve(fg_state* s, const FgCgArgs& a, fg_solve_info* info_host, hipStream_t st, FgCgOutcome* out) {
+    CgRun c;
+    FgCgOutcome o;
+    if (int rc = cg_begin(s, a, c, st)) return rc;
+#if !FG_F64
+    if (c.fused) { if (int rc = cg_iterate_fused(s, a, c, o, st)) return rc; }
+    else
+#endif
+    if (int rc = cg_iterate_classic(s, a, c, o, st)) return rc;
+    const int rc = cg_finish(s, a, c, o, info_host, st);
+    if (out) *out = o;
     return rc;
 }
 
@@ -718,7 +750,7 @@ __global__ __launch_bounds__(FG_BLOCK) void k64_papply(FgGrid g, const float* __
 }
 }  // namespace
 
-int fg_rung64_cg(fg_state* s, const FgCgArgs& a, fg_solve_info* info, bool all_envs, hipStream_t st) {
+int fg_rung64_cg(fg_state* s, const FgCgArgs& a, fg_solve_info* info, bool all_envs, hipStream_t st, FgCgOutcome* out) {
     R64 w;
     if (int rc = w.init(s, st)) return rc;
     const int B = s->grid.B, n = s->grid.n, d = s->grid.dims;
@@ -770,6 +802,7 @@ int fg_rung64_cg(fg_state* s, const FgCgArgs& a, fg_solve_info* info, bool all_e
     }
     FG_HIP_CHECK(hipStreamSynchronize(st));
     FG_HIP_CHECK(hipGetLastError());
+    *out = FgCgOutcome{};      // (stored in a.x, nothing folded)
     return rc_all;
 }
 
@@ -789,7 +822,7 @@ __global__ void k64_fill(double* __restrict__ y, double v, int n) {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) y[i] = v;
 }
 }  // namespace
-int fg_refine64_pressure(fg_state* s, const FgCgArgs& a0, fg_solve_info* info_host, hipStream_t st) {
+int fg_refine64_pressure(fg_state* s, const FgCgArgs& a0, fg_solve_info* info_host, hipStream_t st, FgCgOutcome* out) {
     R64 w;
     if (int rc = w.init(s, st)) return rc;
     const int B = s->grid.B, n = s->grid.n, d = s->grid.dims;
@@ -865,6 +898,7 @@ int fg_refine64_pressure(fg_state* s, const FgCgArgs& a0, fg_solve_info* info_ho
     }
     FG_HIP_CHECK(hipStreamSynchronize(st));
     FG_HIP_CHECK(hipGetLastError());
+    *out = FgCgOutcome{};      // (stored in a.x, nothing folded)
     return rc_all;
 }
 #endif

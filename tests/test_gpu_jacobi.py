@@ -357,8 +357,8 @@ def test_corrector_kernels_launched_behind_the_sweeps_check(monkeypatch):
 
 
 def test_speculation_never_changes_bits_over_a_long_randomised_trajectory(monkeypatch):
-    """VERDICT r5 (weak 11): kernels launched behind a verdict the host has not seen (``jac_spec_fn``: the corrector's first kernels
-    behind the sweeps' check; ``fcg_spec_fn``: the corrector behind the first-iterate verdict) -- 200 PISO steps with tolerances
+    """VERDICT r5 (weak 11): kernels launched behind a verdict the host has not seen (``FgSpecHook``: the corrector's first kernels
+    behind the sweeps' check; ``FgCgSpec``: the corrector behind the first-iterate verdict) -- 200 PISO steps with tolerances
     drawn per step so that about one velocity solve in ten needs a second pass the handle did not plan (a miss: the solve runs again
     without the speculation) and about one first iterate in ten is rejected, compared with FG_JAC_SPEC=0 FG_FCG_SPEC=0: every
     field bit for bit at ten points of the trajectory and at its end, the same iteration counts step by step."""
