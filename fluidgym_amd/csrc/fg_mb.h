@@ -18,9 +18,11 @@
 
 // mb_real: the scalar type of the multi-block translation units -- fields, tables, recurrence scalars, C ABI (the public header
 // declares the same entry points with fg_real): float in libfluidgym_hip.so, double in the fp64 build (libfluidgym_hip_f64.so,
-// -DFG_REAL_DOUBLE).  What is written for 32-bit words -- the four-cells-per-thread kernels (float4), the on-chip CG, the multilevel
-// preconditioner: fg_f32 -- stays compiled and is switched off at run time in that build (fg_mb_create / fg_mb_finalize /
-// fg_mb_set_multilevel).  (Until round 4 the fp64 build renamed the keyword `float` for these files.)
+// -DFG_REAL_DOUBLE).  What is written for 32-bit words -- the four-cells-per-thread kernels (float4), the on-chip / L2 / cluster CG
+// and the restrictions fused into the float4 BiCGStab kernels: fg_f32 -- stays compiled and is switched off at run time in that
+// build (fg_mb_create / fg_mb_finalize / mb_bicgstab).  The multilevel preconditioner in kernel form (k_ml_*) and the preconditioned
+// CG on it (k_mbc_*_pre) are written in mb_real and serve both builds; fg_mb_set_multilevel installs the tables in either.
+// (Until round 4 the fp64 build renamed the keyword `float` for these files.)
 typedef float fg_f32;
 #ifdef FG_REAL_DOUBLE
 typedef double mb_real;
@@ -136,6 +138,9 @@ struct fg_mb_state {
     // work arrays of the kernel form (mb_ml_apply): aggregate sums [B][n4], coarse solution [B][n8], 1 / scale [B], M p and M s [B][N]
     mb_real *ml_r4 = nullptr, *ml_z8 = nullptr, *ml_scale = nullptr, *ml_mp = nullptr, *ml_ms = nullptr;
     uint16_t* ml_p8c = nullptr;   // the 8 x 8 aggregate of every CELL (parent4[a4[i]]): one table level less in the prolongation
+    mb_real *ml_cnt4 = nullptr, *ml_g8 = nullptr;   // cells per 4 x 4 aggregate [n4]; A8^+ (cells per 8 x 8 aggregate) [n8]: M (r - c 1) from M's sums of r (k_ml_prolong_cg)
+    int dbg_pcg_kernel = 0;       // FG_MB_PCG_KERNEL=1 (fp32 build): the preconditioned pressure CG in kernel form instead of the on-chip / cluster kernels (the fp64 build's form)
+    long long ml_cg_solves = 0;   // pressure CG solves that ran the kernel-form preconditioned loop (fg_mb_config_dump)
     mb_real* ml_r4c = nullptr; uint32_t* ml_pos4 = nullptr;   // r4 once more, ordered by parent: [B][n8][4] (absent children stay 0), and the slot of every aggregate in it
     mb_real* Poff4 = nullptr;    // [B][N][4] pressure off-diagonals interleaved per cell (2-D), written by k_mb_pmatrix next to Poff
     // ILU(0) of the velocity matrix as the right preconditioner of the preconditioned rung (mb_ilu_*, fg_mb_step.hip): level
@@ -199,7 +204,7 @@ struct fg_mb_state {
     int dbg_ml_cap = 200;   // FG_MB_ML_TRY_CAP: iteration cap of a multilevel-preconditioned pressure BiCGStab attempt (tests: a tiny cap makes every attempt fail)
     int dbg_fuse_st = 2;   // FG_MB_BICG_FUSE: 0 five BiCGStab kernels, 1 s / t fused (k_mbb_st), 2 also p / v (k_mbb_pv; default)
     int dbg_ml_fuse = 1;   // FG_MB_ML_FUSE: multilevel BiCGStab forms p / s inside the restriction -- 0 never, 1 up to 32 systems (default), 2 always
-    int dbg_ml_sb = 0;     // FG_MB_ML_SB: systems per workgroup of k_ml_coarse (4 / 8; 0 = 8 from 32 systems on)
+    int dbg_ml_sb = 0;     // systems per workgroup of k_ml_coarse (2 / 4 / 8; 0 = by the rule of mb_ml_restrict_coarse); no longer read from the environment
     int dbg_pred = 1;      // FG_MB_PRED=0: first convergence poll after two iterations instead of where the previous solve finished
     // per-env outcome of the last fg_mb_piso_step / fg_mb_single_step: 0 ok, 1 a solve ended unconverged (best iterate used),
     // 2 a solve was non-finite: that env's step was NOT committed (state as before the step), the other envs completed

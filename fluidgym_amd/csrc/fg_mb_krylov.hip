@@ -652,7 +652,19 @@ struct MlDev {
     // its r8 is one coalesced 16-byte load instead of a child table followed by four gathers
     const uint32_t* pos4; mb_real* r4c;
     const uint16_t* p8c;   // parent4[a4[i]] per cell
+    // M applied to r - c 1 without a pass over r: cells per 4 x 4 aggregate, and A8^+ (cells per 8 x 8 aggregate) (k_ml_prolong_cg)
+    const mb_real* cnt4; const mb_real* g8;
 };
+// four consecutive words of mb_real as one load (16 bytes in the fp32 build, 32 in the fp64 build)
+struct alignas(4 * sizeof(mb_real)) MlReal4 { mb_real x, y, z, w; };
+// 1 / d for the Jacobi term: v_rcp_f32 in the fp32 build (a preconditioner needs no IEEE division), a division in doubles
+__device__ __forceinline__ mb_real ml_rcp(mb_real d) {
+#if FG_MB_F64
+    return 1.0 / d;
+#else
+    return __builtin_amdgcn_rcpf(d);
+#endif
+}
 // 1 / s per env: trace(S_geom) / trace(P_env); one workgroup per env
 __global__ __launch_bounds__(1024) void k_ml_scale(const mb_real* __restrict__ diag, int N, mb_real geom_diag_sum, mb_real* __restrict__ scale_inv) {
     const int b = blockIdx.x;
@@ -787,11 +799,11 @@ __global__ __launch_bounds__(ML_ROWS * ML_CG) void k_ml_coarse(MlDev M, int nc, 
     if (!any) return;
 #pragma unroll
     for (int k = 0; k < SB; ++k) {
-        const float4* r4c = reinterpret_cast<const float4*>(M.r4c + (size_t)(on[k] ? ML_SYSK(k) : 0) * 4 * M.n8);
+        const MlReal4* r4c = reinterpret_cast<const MlReal4*>(M.r4c + (size_t)(on[k] ? ML_SYSK(k) : 0) * 4 * M.n8);
         for (int g = threadIdx.x; g < M.n8; g += ML_ROWS * ML_CG) {
             mb_real sum = 0.f;
             if (on[k]) {
-                const float4 c = r4c[g];               // the (at most four) children in child order, absent ones 0
+                const MlReal4 c = r4c[g];              // the (at most four) children in child order, absent ones 0
                 sum = ((c.x + c.y) + c.z) + c.w;
             }
             l_r8[k * n8p + g] = sum;
@@ -840,7 +852,7 @@ __global__ __launch_bounds__(FG_BLOCK) void k_ml_prolong(MlDev M, const mb_real*
     const int b = sys / nc;
     const unsigned a = M.a4[i];
     const mb_real half_s = 0.5f * M.scale_inv[b];
-    out[(size_t)sys * N + i] = in[(size_t)sys * N + i] * __builtin_amdgcn_rcpf(diag[(size_t)b * N + i]) +
+    out[(size_t)sys * N + i] = in[(size_t)sys * N + i] * ml_rcp(diag[(size_t)b * N + i]) +
                                half_s * M.rd4[a] * M.r4[(size_t)sys * M.n4 + a] + M.z8[(size_t)sys * M.n8 + M.p8c[i]];
 }
 
@@ -1057,6 +1069,111 @@ __global__ __launch_bounds__(FG_BLOCK) void k_mbc_update4(int N, MbSolve q, cons
     { const int sl[2] = {C_RHO + (it + 1) % 3, C_SUM + (it + 1) % 3}; const mb_real vv[2] = {part, psum}; const bool on[2] = {true, (bool)project_mean}; mb_acc_tail<2>(a, sl, vv, on); }
 }
 
+// ---- the same CG with the multilevel preconditioner in kernel form (the recurrence of k_mbc_onchip's PRE branch, restated in NumPy as
+// tests/test_multilevel_precond.py::_pcg):  z = M (r - mean r),  rz = (r - mean r) . z,  p = (z - mean z) + (rz / rz_prev) p,
+// alpha = rz / p.Ap,  criterion RMS(r - mean r).  Five launches per iteration, in this order:
+//   k_ml_restrict, k_ml_coarse   the aggregate sums of the RAW residual and the coarse solve on them (mb_ml_apply's own kernels)
+//   k_ml_prolong_cg              z, with the mean of r taken out by linearity (MlDev::cnt4 / g8: no pass over r for it), and the
+//                                sums r.z and sum z in the same pass
+//   k_mbc_ap_pre                 p of the cell and of its neighbours on the fly from z and the other p buffer, v = A p, p.Ap
+//   k_mbc_update_pre             x += alpha p, r -= alpha v, |r|^2 and sum r of the next iteration
+// accumulators next to the plain recurrence's (C_RHO ring, C_PAP pair, C_SUM ring): C_RZ pair 5, 7 (r.z of iteration it in slot
+// 5 + 2 (it & 1), the other one is rz_prev) and C_ZS 11 (sum z); each is cleared by k_mbc_update_pre, after its last reader and before the
+// next prolongation adds to it.  Every sum is a fixed-order workgroup tree into FgDacc: replays repeat bit for bit.
+constexpr int C_RZ = 5, C_ZS = 11;   // (slot 6 is A_RR: k_mbs_init adds |r|^2 there)
+__global__ __launch_bounds__(FG_BLOCK) void k_ml_prolong_cg(MlDev M, MbSolve q, int N, int it_arg, int project_mean, mb_real* __restrict__ z) {
+    const int i = blockIdx.x * FG_BLOCK + threadIdx.x, sys = blockIdx.y;   // (pressure systems: nc == 1, system = env)
+    __shared__ mb_real lds[8];
+    if (flag_ld(q.flags + sys) != 0) return;
+    const int it = it_arg >= 0 ? it_arg : q.it_ctr[0];
+    FgDacc* a = q.acc + (size_t)sys * MB_ACC;
+    const mb_real rm = project_mean ? (mb_real)acc_ld(a + (C_SUM + it % 3)) * mb_rsqrt((mb_real)N) : (mb_real)0;   // mean of r (yp = 1 / sqrt(N))
+    mb_real part[2] = {0.f, 0.f};
+    if (i < N) {
+        const unsigned ag = M.a4[i], pg = M.p8c[i];
+        const mb_real sinv = M.scale_inv[sys];
+        const mb_real rt = q.r[(size_t)sys * N + i] - rm;
+        const mb_real zi = rt * ml_rcp(q.diag[(size_t)sys * N + i]) +
+                           (mb_real)0.5 * sinv * M.rd4[ag] * (M.r4[(size_t)sys * M.n4 + ag] - rm * M.cnt4[ag]) +
+                           (M.z8[(size_t)sys * M.n8 + pg] - rm * sinv * M.g8[pg]);
+        z[(size_t)sys * N + i] = zi;
+        part[0] = rt * zi; part[1] = zi;
+    }
+    mb_block_sums<2>(part, lds);
+    { const int sl[2] = {C_RZ + 2 * (it & 1), C_ZS}; const bool on[2] = {true, true}; mb_acc_tail<2>(a, sl, part, on); }
+}
+template <int DIMS>
+__global__ __launch_bounds__(FG_BLOCK) void k_mbc_ap_pre(MbDev D, MbSolve q, mb_real* __restrict__ pA, mb_real* __restrict__ pB, const mb_real* __restrict__ z,
+                                                          int it_arg, int project_mean) {
+    MB_SYS
+    const int it = it_arg >= 0 ? it_arg : q.it_ctr[0];
+    if (leader && sys == 0) q.it_ctr[1] = it + 1;
+    const mb_real* p_old = (it & 1) ? pA : pB;
+    mb_real* p_new = (it & 1) ? pB : pA;
+    if (flag_ld(q.flags + (sys)) != 0) return;
+    const double sum_r = project_mean ? acc_ld(a + (C_SUM + it % 3)) : 0.0;
+    const double rho = acc_ld(a + (C_RHO + it % 3)) - sum_r * sum_r;   // |r - mean r|^2
+    const mb_real crit = mb_rms(rho, N);
+    if (!(crit >= q.tol)) { if (leader) mb_mark(q, sys, crit, it); return; }
+    const bool fresh = (it == q.it_ctr[2]);  // first iteration after the start or a restart: p = z
+    const mb_real beta = fresh ? (mb_real)0 : (mb_real)(acc_ld(a + (C_RZ + 2 * (it & 1))) / acc_ld(a + (C_RZ + 2 * ((it + 1) & 1))));
+    const mb_real zbar = project_mean ? (mb_real)(acc_ld(a + C_ZS) / (double)N) : (mb_real)0;
+    if (leader) {
+        q.info[sys].final_residual = crit; q.info[sys].used_iterations = it;
+        acc_st(a + (C_RHO + (it + 1) % 3), 0.0);  // accumulated by k_mbc_update_pre of this iteration; nobody reads it here
+        acc_st(a + (C_SUM + (it + 1) % 3), 0.0);
+        if (q.best_x && (it == 0 || crit < 0.5f * sc_ld(q.sc + (sys * 2)) || (crit < q.accept_factor * q.tol && crit < sc_ld(q.sc + (sys * 2))))) {
+            sc_st(q.sc + (sys * 2), crit); q.best_it[sys] = it;
+        }
+    }
+    mb_real part = 0.f;
+    if (valid) {
+        constexpr int F = 2 * DIMS;
+        const mb_real* zz = z + vb;
+        const mb_real* po = p_old + vb;
+        auto dir = [&](int c) { return fresh ? zz[c] - zbar : (zz[c] - zbar) + beta * po[c]; };
+        const mb_real pi = dir(i);
+        mb_real y = q.diag[(size_t)b * N + i] * pi;
+#pragma unroll
+        for (int f = 0; f < F; ++f) {
+            const int n = D.nbr[(size_t)f * N + i];
+            if (n >= 0) y += q.off[((size_t)b * F + f) * N + i] * dir(n);
+        }
+        p_new[vb + i] = pi;
+        q.v[vb + i] = y;
+        part = pi * y;
+    }
+    part = mb_block_sum(part, lds);
+    if (threadIdx.x == 0) acc_add(a + C_PAP + (it & 1), (double)part);
+}
+template <int DIMS>
+__global__ __launch_bounds__(FG_BLOCK) void k_mbc_update_pre(MbDev D, MbSolve q, const mb_real* __restrict__ pA, const mb_real* __restrict__ pB,
+                                                              int it_arg, int project_mean) {
+    MB_SYS
+    const int it = it_arg >= 0 ? it_arg : q.it_ctr[1] - 1;
+    if (leader && sys == 0) q.it_ctr[0] = it + 1;
+    const mb_real* p = (it & 1) ? pB : pA;
+    if (flag_ld(q.flags + (sys)) != 0) return;
+    const mb_real alpha = (mb_real)(acc_ld(a + (C_RZ + 2 * (it & 1))) / acc_ld(a + (C_PAP + (it & 1))));
+    if (leader) {   // idle until the next iteration's kernels add to them; none is read in this launch
+        acc_st(a + (C_PAP + ((it + 1) & 1)), 0.0);
+        acc_st(a + (C_RZ + 2 * ((it + 1) & 1)), 0.0);
+        acc_st(a + C_ZS, 0.0);
+    }
+    mb_real part = 0.f, psum = 0.f;
+    if (valid) {
+        if (q.best_x && q.best_it[sys] == it) q.best_x[vb + i] = q.x[vb + i];
+        q.x[vb + i] += alpha * p[vb + i];
+        const mb_real r = q.r[vb + i] - alpha * q.v[vb + i];
+        q.r[vb + i] = r;
+        part = r * r;
+        psum = r * D.yproj[i];
+    }
+    part = mb_block_sum(part, lds);
+    if (project_mean) psum = mb_block_sum(psum, lds);
+    { const int sl[2] = {C_RHO + (it + 1) % 3, C_SUM + (it + 1) % 3}; const mb_real vv[2] = {part, psum}; const bool on[2] = {true, (bool)project_mean}; mb_acc_tail<2>(a, sl, vv, on); }
+}
+
 // restart of the CG recurrence (the reference recomputes r = b - A x and resets p = r every residualResetSteps = 100
 // iterations, cg_solver_kernel.cu:281-300): slots of iteration `it` are cleared by k_mbc_clear, then refilled here
 __global__ void k_mbc_clear(MbSolve q, int nsys, int it) {
@@ -1067,6 +1184,9 @@ __global__ void k_mbc_clear(MbSolve q, int nsys, int it) {
     acc_st(q.acc + ((size_t)s * MB_ACC + C_SUM + it % 3), 0.0);
     acc_st(q.acc + ((size_t)s * MB_ACC + C_PAP), 0.0);      // both idle between iterations; a recovered system left NaN here
     acc_st(q.acc + ((size_t)s * MB_ACC + C_PAP + 1), 0.0);
+    acc_st(q.acc + ((size_t)s * MB_ACC + C_RZ), 0.0);       // (the preconditioned recurrence's r.z pair and sum z: idle here, too)
+    acc_st(q.acc + ((size_t)s * MB_ACC + C_RZ + 2), 0.0);
+    acc_st(q.acc + ((size_t)s * MB_ACC + C_ZS), 0.0);
 }
 // a system whose recurrence broke down (p.Pp <= 0 or overflow on the non-symmetric matrix: flag 2) goes back to its kept
 // iterate and rejoins the iteration at the restart that follows
@@ -1340,6 +1460,7 @@ MlDev mb_ml_dev(const fg_mb_state* s) {
     M.a4 = s->ml_a4; M.parent4 = s->ml_parent4; M.rect4 = s->ml_rect4; M.child8 = s->ml_child8; M.rd4 = s->ml_d4g; M.aci8 = s->ml_aci8;
     M.n4 = s->ml_n4; M.n8 = s->ml_n8; M.ld8 = (s->ml_n8 + 3) & ~3;
     M.r4 = s->ml_r4; M.z8 = s->ml_z8; M.scale_inv = s->ml_scale; M.pos4 = s->ml_pos4; M.r4c = s->ml_r4c; M.p8c = s->ml_p8c;
+    M.cnt4 = s->ml_cnt4; M.g8 = s->ml_g8;
     return M;
 }
 // fused = 0: z = M in.  1 / 2: `in` is q.p / q.r and its update (k_mbb_p4 / k_mbb_s4) happens inside the restriction
@@ -1349,8 +1470,8 @@ void mb_ml_scale(fg_mb_state* s, const mb_real* diag, hipStream_t st) {
     hipLaunchKernelGGL(k_ml_scale, dim3(s->B), dim3(1024), 0, st, diag, s->N, s->ml_geom_diag_sum, s->ml_scale);
 }
 
-void mb_ml_apply(fg_mb_state* s, const MbSolve& q, const mb_real* in, mb_real* out, hipStream_t st, int fused, int it) {
-    const MlDev M = mb_ml_dev(s);
+// the first two launches of an application: aggregate sums of `in` (or of the p / s formed on the way, fused = 1 / 2) and the coarse solve
+static void mb_ml_restrict_coarse(fg_mb_state* s, const MbSolve& q, const MlDev& M, const mb_real* in, hipStream_t st, int fused, int it) {
     const int nsys = q.sys_map ? q.n_map : s->B * q.nc, n = s->N;    // (systems of the launch: compacted when only a few still iterate)
     const dim3 rgrid4((4 * M.n4 + FG_BLOCK - 1) / FG_BLOCK, nsys);   // four threads per aggregate
     if (fused == 1) { MB_DISPATCH(s, hipLaunchKernelGGL(k_ml_restrict_p<DIMS>, rgrid4, dim3(FG_BLOCK), 0, st, s->dev, q, M, it);); }
@@ -1358,15 +1479,28 @@ void mb_ml_apply(fg_mb_state* s, const MbSolve& q, const mb_real* in, mb_real* o
     else
     hipLaunchKernelGGL(k_ml_restrict, rgrid4, dim3(FG_BLOCK), 0, st, M, in, n, (const int32_t*)q.flags, q.sys_map);
     {
-        // systems per workgroup: 8 when that still leaves >= 2 workgroups per CU-pair of work (>= 32 systems) and the LDS fits 64 KB
+        // systems per workgroup: 8 when that still leaves >= 2 workgroups per CU-pair of work (>= 32 systems) and the LDS fits 64 KB.
+        // In doubles the words are twice as wide: the partial sums of the eight-system form alone ([ML_CG][8][ML_ROWS]) are 64 KB, so
+        // that form does not exist in the fp64 build -- 32 systems and more run four per workgroup there and stream A8^+ twice as
+        // often as the fp32 build -- and meshes of more than 1024 coarse aggregates step down to 2 (48 KB at ML_N8_MAX = 2048)
+        // instead of asking for more than the default 64 KB of a workgroup
         const int n8p = (M.n8 + 3) & ~3;
-        const auto words = [&](int sb) { return (sb * n8p > 4 * sb * ML_ROWS ? sb * n8p : 4 * sb * ML_ROWS) + ML_CG * sb * ML_ROWS; };
-        const int want = s->dbg_ml_sb ? s->dbg_ml_sb : (nsys >= 32 ? 8 : 4);
-        if (want == 8 && words(8) * 4 <= 64 * 1024)
-            hipLaunchKernelGGL(k_ml_coarse<8>, dim3((M.n8 + ML_ROWS - 1) / ML_ROWS, (nsys + 7) / 8), dim3(ML_ROWS * ML_CG), (size_t)words(8) * 4, st, M, q.nc, nsys, (const int32_t*)q.flags, n8p, q.sys_map);
-        else
-            hipLaunchKernelGGL(k_ml_coarse<4>, dim3((M.n8 + ML_ROWS - 1) / ML_ROWS, (nsys + 3) / 4), dim3(ML_ROWS * ML_CG), (size_t)words(4) * 4, st, M, q.nc, nsys, (const int32_t*)q.flags, n8p, q.sys_map);
+        const auto bytes = [&](int sb) { return (size_t)((sb * n8p > 4 * sb * ML_ROWS ? sb * n8p : 4 * sb * ML_ROWS) + ML_CG * sb * ML_ROWS) * sizeof(mb_real); };
+        int sb = s->dbg_ml_sb ? s->dbg_ml_sb : (nsys >= 32 ? 8 : 4);
+        if (sb == 8 && bytes(8) > 64 * 1024) sb = 4;
+        if (FG_MB_F64 && sb == 4 && bytes(4) > 64 * 1024) sb = 2;
+        static_assert((2 * ML_N8_MAX + ML_CG * 2 * ML_ROWS) * sizeof(double) <= 64 * 1024, "two systems per workgroup fit at the largest coarse level");
+#define ML_COARSE(SB_) hipLaunchKernelGGL(k_ml_coarse<SB_>, dim3((M.n8 + ML_ROWS - 1) / ML_ROWS, (nsys + SB_ - 1) / SB_), dim3(ML_ROWS * ML_CG), bytes(SB_), st, M, q.nc, nsys, (const int32_t*)q.flags, n8p, q.sys_map)
+        if (sb == 8) ML_COARSE(8);
+        else if (sb == 2) ML_COARSE(2);
+        else ML_COARSE(4);
+#undef ML_COARSE
     }
+}
+void mb_ml_apply(fg_mb_state* s, const MbSolve& q, const mb_real* in, mb_real* out, hipStream_t st, int fused, int it) {
+    const MlDev M = mb_ml_dev(s);
+    const int nsys = q.sys_map ? q.n_map : s->B * q.nc, n = s->N;
+    mb_ml_restrict_coarse(s, q, M, in, st, fused, it);
     hipLaunchKernelGGL(k_ml_prolong, dim3((n + FG_BLOCK - 1) / FG_BLOCK, nsys), dim3(FG_BLOCK), 0, st, M, in, q.diag, n, q.nc, (const int32_t*)q.flags, out, q.sys_map);
 }
 
@@ -1464,7 +1598,7 @@ int mb_bicgstab(fg_mb_state* s, const mb_real* dt, const mb_real* diag, const mb
     // while the launches are latency-sized (Airfoil2D x 16: 32.3-33.9 -> 34.7-34.8 env-steps/s; rocprofv3: p + restriction 10.1 -> 7.3 us, s + restriction
     // 10.4 -> 7.1 us with four threads per aggregate) and not once they carry bytes (x 64: 16.0 -> 17.4 us, 15.2 -> 14.3 us).  So: up to 32 systems.
     // FG_MB_ML_FUSE=0 never, 2 always.
-    const bool ml_fused = ml && !ilu && (s->dbg_ml_fuse == 2 || (s->dbg_ml_fuse == 1 && nsys <= 32));
+    const bool ml_fused = ml && !ilu && !FG_MB_F64 && (s->dbg_ml_fuse == 2 || (s->dbg_ml_fuse == 1 && nsys <= 32));   // (k_ml_restrict_p / _s: fp32 words)
     if (fused_st) q.sbuf = s->w[5];
     const bool verify = ml || refine;
     int verify_rounds = 0;
@@ -1878,7 +2012,12 @@ int mb_pressure_bicgstab(fg_mb_state* s, const mb_real* dt, mb_real tol, int max
 int mb_cg(fg_mb_state* s, const mb_real* dt, const mb_real* diag, const mb_real* off, const mb_real* rhs, mb_real* x, mb_real tol,
           int max_iterations, int use_x0, int project_mean, mb_real stall_accept, int* max_it, hipStream_t st) {
     const int nsys = s->B, n = s->N;
-    {
+    // the multilevel preconditioner in kernel form (k_ml_prolong_cg / k_mbc_ap_pre / k_mbc_update_pre): what the fp64 build runs once
+    // the tables are installed, and in the fp32 build the debug form FG_MB_PCG_KERNEL=1 of the on-chip / cluster kernels' recurrence.
+    // Pressure systems of 2-D meshes; the residual projected onto the complement of the constant, or not at all
+    const bool pre = (FG_MB_F64 || s->dbg_pcg_kernel) && s->ml_on && s->ml_a4 != nullptr && s->ml_mp != nullptr && s->d == 2 &&
+                     diag == s->Pdiag && (!project_mean || s->yproj_const);
+    if (!pre) {
         const int pm = project_mean ? (s->yproj_const ? 1 : 2) : 0;
         if (mb_cluster_ok(s, pm, diag, off)) {
             bool fell_back = false;
@@ -1896,6 +2035,8 @@ int mb_cg(fg_mb_state* s, const mb_real* dt, const mb_real* diag, const mb_real*
     const dim3 grid4((n / 4 + FG_BLOCK - 1) / FG_BLOCK, nsys);
     hipLaunchKernelGGL(k_mbs_begin, sg, sb, 0, st, dt, q, nsys);
     MB_DISPATCH(s, hipLaunchKernelGGL(k_mbs_init<DIMS>, grid, blk, 0, st, s->dev, q, use_x0, project_mean ? C_SUM : -1, 0););
+    const MlDev ML = mb_ml_dev(s);
+    if (pre) { mb_ml_scale(s, diag, st); s->ml_cg_solves += 1; }
     bool done = false;
     // CG_CHUNK iterations + the convergence check are one hipGraph: at 14 k cells x 64 envs a kernel runs 5-10 us, about
     // what the host needs to enqueue it, so the loop was launch-bound.  The kernels take their iteration index from a
@@ -1924,7 +2065,13 @@ int mb_cg(fg_mb_state* s, const mb_real* dt, const mb_real* diag, const mb_real*
     const int pm_mode = project_mean ? (s->yproj_const ? 1 : 2) : 0;
     auto enqueue_chunk = [&](bool sample, FgPollOut po) {   // po: sequence words of the poll that follows ({nullptr, 0} inside a captured graph)
         MB_DISPATCH_PM(s, pm_mode, {
-            for (int k = 0; k < CG_CHUNK; ++k) {
+            for (int k = 0; k < CG_CHUNK && pre; ++k) {   // z = M (r - mean r) in s->ml_mp, then the two recurrence kernels on it
+                mb_ml_restrict_coarse(s, q, ML, q.r, st, 0, 0);
+                hipLaunchKernelGGL(k_ml_prolong_cg, grid, blk, 0, st, ML, q, n, -1, project_mean, s->ml_mp);
+                hipLaunchKernelGGL(k_mbc_ap_pre<DIMS>, grid, blk, 0, st, s->dev, q, s->w[1], s->w[2], (const mb_real*)s->ml_mp, -1, project_mean);
+                hipLaunchKernelGGL(k_mbc_update_pre<DIMS>, grid, blk, 0, st, s->dev, q, (const mb_real*)s->w[1], (const mb_real*)s->w[2], -1, project_mean);
+            }
+            for (int k = 0; k < CG_CHUNK && !pre; ++k) {
                 const bool ev = sample && k == 0 && s->prof_used + 2 <= 32;
                 const int e0 = s->prof_used;
                 if (ev) {
@@ -1961,7 +2108,7 @@ int mb_cg(fg_mb_state* s, const mb_real* dt, const mb_real* diag, const mb_real*
     if (use_graph) {
         MbGraphKey key;
         memset(&key, 0, sizeof(key));
-        key.q = q; key.vec4 = vec4; key.project_mean = pm_mode; key.stream = st;
+        key.q = q; key.vec4 = (vec4 ? 1 : 0) | (pre ? 2 : 0); key.project_mean = pm_mode; key.stream = st;
         static_assert(sizeof(MbGraphKey) <= sizeof(s->cg_graph_key_storage), "graph key storage too small");
         MbGraphKey& stored = *reinterpret_cast<MbGraphKey*>(s->cg_graph_key_storage);
         if (!s->cg_graph_exec || memcmp(&key, &stored, sizeof(key)) != 0) {

@@ -490,11 +490,12 @@ extern "C" int fg_mb_create(int32_t dims, int32_t batch, int32_t device, fg_mb_h
         e = getenv("FG_MB_CL_MAXCL"); s->cl_max_clusters = e ? atoi(e) : 0;
         e = getenv("FG_MB_CLUSTER"); s->cl_mode = e ? atoi(e) : 1;   // 0 never, 1 meshes beyond 8 k cells (default), 2 every mesh its tables fit
         e = getenv("FG_MB_RUNG_ILU"); s->dbg_rung_ilu = (e && e[0] == '0') ? 0 : 1;
+        e = getenv("FG_MB_PCG_KERNEL"); s->dbg_pcg_kernel = (e && e[0] == '1') ? 1 : 0;
         e = getenv("FG_MB_OC_VARIANT"); s->oc_variant = e ? atoi(e) : 0;   // bit 0: no compiler fences in the stencil pass; bit 1: split [F][N] coefficient layout
     }
 #if FG_MB_F64
-    // the fp64 build runs the one-cell-per-thread kernels: the four-cell forms (float4), the on-chip CG and the multilevel
-    // preconditioner are written for 32-bit words (fg_mb.h)
+    // the fp64 build runs the one-cell-per-thread kernels: the four-cell forms (float4) and the on-chip / cluster CG are written for
+    // 32-bit words (fg_mb.h); the multilevel preconditioner runs in kernel form there once fg_mb_set_multilevel has installed it
     s->dbg_vec_mask = 0; s->dbg_scalar_cg = 1; s->onchip_mode = 0; s->dbg_oc_agg = 0; s->cl_mode = 0;
 #endif
     *out = s;
@@ -507,11 +508,12 @@ extern "C" int fg_mb_config_dump(fg_mb_handle s, char* buf, int n) {
     const int len = snprintf(tmp, sizeof(tmp),
         "{\"FG_MB_BICG_VEC4\": %d, \"FG_MB_SCALAR_CG\": %d, \"FG_MB_BICG_FUSE\": %d, \"FG_MB_PRED\": %d, \"FG_MB_ML_FUSE\": %d, \"FG_MB_ML_SB\": %d, "
         "\"FG_MB_ML_TRY_CAP\": %d, \"FG_MB_ML_WARMUP\": %d, \"FG_MB_GRAPH\": %d, \"FG_MB_TRACE\": %d, \"FG_MB_COMPACT\": %d, \"FG_MB_OC_RTG_NT\": %d, "
-        "\"FG_MB_ONCHIP\": %d, \"FG_MB_OC_AGG\": %d, \"FG_MB_RUNG_ILU\": %d, \"FG_MB_OC_VARIANT\": %d, \"FG_MB_CLUSTER\": %d, "
+        "\"FG_MB_ONCHIP\": %d, \"FG_MB_OC_AGG\": %d, \"FG_MB_RUNG_ILU\": %d, \"FG_MB_OC_VARIANT\": %d, \"FG_MB_CLUSTER\": %d, \"FG_MB_PCG_KERNEL\": %d, \"multilevel_on\": %d, \"multilevel_cg_solves\": %lld, "
         "\"cluster_on\": %d, \"cluster_members_per_thread\": %d, \"cluster_threads\": %d, \"cluster_halo_max\": %d, \"cluster_solves\": %lld, \"cluster_fallbacks\": %lld, \"cluster_jacobi_solves\": %lld}",
         (int)s->dbg_vec_mask, (int)s->dbg_scalar_cg, (int)s->dbg_fuse_st, (int)s->dbg_pred, (int)s->dbg_ml_fuse, (int)s->dbg_ml_sb, (int)s->dbg_ml_cap,
         (int)s->dbg_ml_warmup, (int)s->dbg_graph, (int)s->dbg_trace, (int)s->dbg_compact, (int)s->oc_rtg_nt, (int)s->onchip_mode, (int)s->dbg_oc_agg,
-        (int)s->dbg_rung_ilu, (int)s->oc_variant, (int)s->cl_mode, (int)(mb_cluster_wanted(s) ? 1 : 0), (int)s->cl_cpt, (int)s->cl_nt, (int)s->cl_n_halo_max,
+        (int)s->dbg_rung_ilu, (int)s->oc_variant, (int)s->cl_mode, (int)s->dbg_pcg_kernel, (int)((s->ml_on && s->ml_a4 != nullptr) ? 1 : 0), s->ml_cg_solves,
+        (int)(mb_cluster_wanted(s) ? 1 : 0), (int)s->cl_cpt, (int)s->cl_nt, (int)s->cl_n_halo_max,
         s->cl_solves, s->cl_fallbacks, s->cl_jacobi_solves);
     if (len >= n) return len + 1;
     memcpy(buf, tmp, (size_t)len + 1);
@@ -942,13 +944,14 @@ extern "C" int fg_mb_solver_counters(fg_mb_handle s, int64_t* out13, int32_t res
     return FG_OK;
 }
 
-// Tables of the multilevel preconditioner of the on-chip pressure CG (built on the host from the geometry-only pressure matrix,
-// simulation/multiblock.py::set_pressure_multilevel); a4 / parent4 as int32 on the host, stored as 16-bit on the device.
+// Tables of the multilevel preconditioner of the pressure solves (built on the host from the geometry-only pressure matrix,
+// simulation/multiblock.py::set_pressure_multilevel); a4 / parent4 as int32 on the host, stored as 16-bit on the device.  Both
+// builds: the fp64 build installs what the kernel form needs (mb_ml_apply, the preconditioned loop of mb_cg) and leaves out the
+// layouts of the fp32 on-chip and cluster kernels.
 extern "C" int fg_mb_set_multilevel(fg_mb_handle s, int32_t n4, int32_t n8, const int32_t* a4_host, const int32_t* parent4_host,
                                     const int32_t* rect4_host, const mb_real* d4g_host, const mb_real* aci8_host, mb_real geom_diag_sum,
                                     int32_t enable) {
     FG_REQUIRE(s && s->finalized && !s->host_only, FG_ERR_INVALID_ARG, "fg_mb_set_multilevel: domain not finalized (or host-only)");
-    FG_REQUIRE(!FG_MB_F64, FG_ERR_UNSUPPORTED, "fg_mb_set_multilevel: the multilevel preconditioner is not part of the fp64 build (plain recurrences there)");
     if (!a4_host) { s->ml_on = enable && s->ml_a4 != nullptr; return FG_OK; }   // switch only
     FG_REQUIRE(s->d == 2 && n4 > 0 && n4 < 65535 && n8 > 0 && n8 <= ML_N8_MAX && parent4_host && rect4_host && d4g_host && aci8_host &&
                    geom_diag_sum != 0.f,
@@ -996,6 +999,8 @@ extern "C" int fg_mb_set_multilevel(fg_mb_handle s, int32_t n4, int32_t n8, cons
         if (int rc = mb_alloc(s, &s->ml_z8, (size_t)s->B * c8)) return rc;
         if (int rc = mb_alloc(s, &s->ml_r4c, (size_t)s->B * 4 * c8)) return rc;
         if (int rc = mb_alloc(s, &s->ml_pos4, (size_t)c4)) return rc;
+        if (int rc = mb_alloc(s, &s->ml_cnt4, (size_t)c4)) return rc;
+        if (int rc = mb_alloc(s, &s->ml_g8, (size_t)c8)) return rc;
         if (!s->ml_scale) {
             if (int rc = mb_alloc(s, &s->ml_scale, (size_t)s->B)) return rc;
             if (int rc = mb_alloc(s, &s->ml_mp, (size_t)s->B * s->N)) return rc;
@@ -1022,9 +1027,26 @@ extern "C" int fg_mb_set_multilevel(fg_mb_handle s, int32_t n4, int32_t n8, cons
         for (int c = 0; c < n8; ++c) padded[(size_t)r * ld + c] = aci8_host[(size_t)r * n8 + c];
     FG_HIP_CHECK(hipMemcpy(s->ml_d4g, rd4.data(), sizeof(mb_real) * n4, hipMemcpyHostToDevice));
     FG_HIP_CHECK(hipMemcpy(s->ml_aci8, padded.data(), sizeof(mb_real) * padded.size(), hipMemcpyHostToDevice));
+    {
+        // what M does to the constant, for the preconditioned CG's mean removal: cells per 4 x 4 aggregate, and A8^+ applied to the
+        // cells per 8 x 8 aggregate (summed in doubles)
+        std::vector<mb_real> cnt4(n4), g8(n8);
+        std::vector<double> cnt8(n8, 0.0);
+        for (int a = 0; a < n4; ++a) { const double c = (double)rect4_host[4 * a + 1] * (double)rect4_host[4 * a + 2]; cnt4[a] = (mb_real)c; cnt8[p4[a]] += c; }
+        for (int r = 0; r < n8; ++r) {
+            double acc = 0.0;
+            for (int c = 0; c < n8; ++c) acc += (double)aci8_host[(size_t)r * n8 + c] * cnt8[c];
+            g8[r] = (mb_real)acc;
+        }
+        FG_HIP_CHECK(hipMemcpy(s->ml_cnt4, cnt4.data(), sizeof(mb_real) * n4, hipMemcpyHostToDevice));
+        FG_HIP_CHECK(hipMemcpy(s->ml_g8, g8.data(), sizeof(mb_real) * n8, hipMemcpyHostToDevice));
+    }
     s->ml_n4 = n4; s->ml_n8 = n8; s->ml_geom_diag_sum = geom_diag_sum; s->ml_on = enable != 0;
-    // ---- aggregate-owned layout of the on-chip CG (fg_mb.h): thread 4 A + c owns child c of 8 x 8 aggregate A
+    // a captured CG chunk (mb_cg, FG_MB_GRAPH) has the table and work-array pointers baked in: it is rebuilt after a new install
+    if (s->cg_graph_exec) { (void)hipGraphExecDestroy(s->cg_graph_exec); s->cg_graph_exec = nullptr; }
     s->oc_agg = false;
+    if (FG_MB_F64) return FG_OK;   // the slot-ordered and cluster layouts below belong to the fp32 on-chip / cluster kernels
+    // ---- aggregate-owned layout of the on-chip CG (fg_mb.h): thread 4 A + c owns child c of 8 x 8 aggregate A
     bool fits = s->d == 2 && s->nbr16 != nullptr && 4 * n8 <= 1024 && s->N <= fg_mb_state::OC_SLOTS;
     for (int a = 0; a < n4 && fits; ++a) fits = rect4_host[4 * a + 1] * rect4_host[4 * a + 2] <= 16;
     if (fits) {
@@ -1133,6 +1155,27 @@ extern "C" int fg_mb_multilevel_apply(fg_mb_handle s, const mb_real* r_BN, mb_re
     mb_ml_scale(s, s->Pdiag, st);
     mb_ml_apply(s, q, r_BN, z_BN, st);
     FG_HIP_CHECK(hipStreamSynchronize(st));
+    return FG_OK;
+}
+
+// One pressure CG solve (mb_cg, from zero) of the systems currently held in the pressure buffers -- matrix in FG_MB_BUF_P_DIAG / _P_OFF,
+// right-hand side in FG_MB_BUF_DIV -- under whatever fg_mb_set_multilevel has switched on: iterations, verdict and final RMS residual
+// per env.  Test entry of the preconditioned recurrence against its CPU replay (tests/test_gpu_mb_f64_multilevel.py), not on any step
+// path; an unconverged or non-finite solve is reported through the outputs, not as an error.
+extern "C" int fg_mb_debug_pressure_cg(fg_mb_handle s, mb_real tol, int32_t max_iterations, int32_t project_mean, int32_t* iterations_B,
+                                       int32_t* converged_B, double* residual_B, void* stream) {
+    FG_REQUIRE(s && s->finalized && !s->host_only && max_iterations > 0 && iterations_B && converged_B && residual_B, FG_ERR_INVALID_ARG,
+               "fg_mb_debug_pressure_cg: bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    int m = 0;
+    const int rc = mb_cg(s, nullptr, s->Pdiag, s->Poff, s->div, s->pres, tol, max_iterations, 0, project_mean, 0.f, &m, st);
+    if (rc != FG_OK && rc != FG_ERR_NOT_CONVERGED && rc != FG_ERR_NOT_FINITE) return rc;
+    FG_HIP_CHECK(hipStreamSynchronize(st));
+    for (int b = 0; b < s->B; ++b) {
+        iterations_B[b] = s->info_pinned[b].used_iterations;
+        converged_B[b] = (s->info_pinned[b].converged && s->info_pinned[b].is_finite) ? 1 : 0;
+        residual_B[b] = (double)s->info_pinned[b].final_residual;
+    }
     return FG_OK;
 }
 

@@ -185,7 +185,13 @@ class AirfoilEnvBase(CylinderEnvBase):
         # attempts are capped and verified on the true residual, one that fails is repeated with the plain recurrence and makes
         # the domain back off exponentially (3x fewer pressure iterations; the stiff start-up solves are the ones that fail)
         # policy pressure_multilevel_bicgstab (default on since the reductions are order-independent: policy.py)
-        self._multilevel = dom.set_pressure_multilevel() if (self._ndims == 2 and get_solver_policy()["pressure_multilevel_bicgstab"]) else None
+        # (a float64 env: only with policy pressure_multilevel_fp64, then with the unfused apply of the fp64 build)
+        self._multilevel = None
+        if self._ndims == 2 and get_solver_policy()["pressure_multilevel_bicgstab"]:
+            if self._dtype == torch.float64 and get_solver_policy()["pressure_multilevel_fp64"]:
+                self._multilevel = dom.set_pressure_multilevel(fp64=True)
+            else:
+                self._multilevel = dom.set_pressure_multilevel()
         return dom
 
     def _get_simulation(self, domain, prep_fn):

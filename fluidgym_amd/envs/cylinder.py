@@ -164,8 +164,13 @@ class CylinderEnvBase(FluidEnv):
             self._sensors = self._resampler.sensor_gather(self._sensor_locations.T)
         self._deflation_cos = dom.set_pressure_deflation() if self._pressure_deflation else 1.0
         from ..simulation.policy import get_solver_policy
-        self._multilevel = dom.set_pressure_multilevel() if (get_solver_policy()["pressure_multilevel"] and not self._pressure_deflation
-                                                              and not self._pressure_use_bicg) else None
+        self._multilevel = None
+        if get_solver_policy()["pressure_multilevel"] and not self._pressure_deflation and not self._pressure_use_bicg:
+            # a float64 env keeps the plain recurrence unless policy pressure_multilevel_fp64 asks for the kernel form (policy.py)
+            if self._dtype == torch.float64 and get_solver_policy()["pressure_multilevel_fp64"]:
+                self._multilevel = dom.set_pressure_multilevel(fp64=True)
+            else:
+                self._multilevel = dom.set_pressure_multilevel()
         self._initial_boundary = dom.boundary_velocity.clone()  # inflow / outflow profile, walls at rest
         self._last_control = torch.zeros(self._num_envs, self._n_controls, device=dom.device, dtype=self._dtype)
 

@@ -455,7 +455,7 @@ class MultiBlockDomain:
             rows.append(np.nonzero(ok)[0]); cols.append(nbr[f][ok]); vals.append(off[f][ok])
         return sp.csr_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=(N, N))
 
-    def set_pressure_multilevel(self, enable: bool = True) -> Optional[dict]:
+    def set_pressure_multilevel(self, enable: bool = True, *, fp64: bool = False) -> Optional[dict]:
         """Build and install the additive multilevel preconditioner of the on-chip pressure CG (``fg_mb_set_multilevel``): Jacobi on
         the cells + half-weighted Jacobi on 4 x 4 aggregates + the exact (pseudo-)inverse on 8 x 8 aggregates, aggregates being
         tiles inside the blocks (:func:`multilevel_tables`).  Everything comes from the symmetric part ``S`` of the pressure matrix
@@ -466,8 +466,13 @@ class MultiBlockDomain:
         CG (meshes up to 16 k cells, 2048 / 512 aggregates: its LDS budget) applies it inside the persistent kernel; the pressure
         BiCGStab of larger 2-D meshes (Airfoil2D: 46.7 k cells) takes it as a right preconditioner in kernel form (three launches
         per application, csrc/fg_mb_step.hip::mb_ml_apply), up to 2048 coarse aggregates.  Returns the aggregate counts, or None
-        when the mesh does not qualify (3-D, or too many aggregates; nothing is installed)."""
-        if self.dims != 2 or self.dtype != torch.float32:   # (the fp64 build runs the plain recurrences)
+        when the mesh does not qualify (3-D, or too many aggregates; nothing is installed).
+
+        A float64 domain keeps its plain recurrences (and returns None) unless ``fp64=True``: then the tables are built from the
+        fp64 unit pressure matrix and installed as doubles, the pressure CG runs the preconditioned recurrence in kernel form
+        (``csrc/fg_mb_krylov.hip::mb_cg``: restrict / coarse / prolong + two recurrence kernels per iteration) and the pressure
+        BiCGStab tries the right preconditioner with the unfused apply.  ``enable=False`` switches either build back."""
+        if self.dims != 2 or (self.dtype != torch.float32 and enable and not fp64):
             return None
         if not enable:
             L.check(self.lib.fg_mb_set_multilevel(self.handle, 0, 0, None, None, None, None, None, 0.0, 0))
@@ -476,9 +481,9 @@ class MultiBlockDomain:
         tab = multilevel_tables(P, [(b.size[0], b.size[1], b.cell_offset) for b in self.blocks], max_n4=65534, max_n8=2048)
         if tab is None:
             return None
-        i32, f32 = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float)
+        i32, f32 = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(self._cf)   # (tables in the library's scalar type)
         a4_32, p4_32 = np.ascontiguousarray(tab["a4"], np.int32), np.ascontiguousarray(tab["parent4"], np.int32)
-        d4_32, aci_32 = np.ascontiguousarray(tab["d4"], np.float32), np.ascontiguousarray(tab["aci8"], np.float32)
+        d4_32, aci_32 = np.ascontiguousarray(tab["d4"], self._np), np.ascontiguousarray(tab["aci8"], self._np)
         rect_32 = np.ascontiguousarray(tab["rect4"], np.int32)
         L.check(self.lib.fg_mb_set_multilevel(self.handle, tab["n4"], tab["n8"], a4_32.ctypes.data_as(i32), p4_32.ctypes.data_as(i32),
                                               rect_32.ctypes.data_as(i32), d4_32.ctypes.data_as(f32), aci_32.ctypes.data_as(f32),
@@ -527,6 +532,16 @@ class MultiBlockDomain:
         st = torch.cuda.current_stream(self.device).cuda_stream
         L.check(self.lib.fg_mb_multilevel_apply(self.handle, ctypes.c_void_p(r.data_ptr()), ctypes.c_void_p(z.data_ptr()), ctypes.c_void_p(st)))
         return z
+
+    def debug_pressure_cg(self, tol: float, max_iterations: int, project_mean: bool = True) -> dict:
+        """One pressure CG solve from zero of the systems held in the pressure buffers (``fg_mb_debug_pressure_cg``; tests): per env
+        the iterations, whether it converged, and the final RMS residual."""
+        its, conv = (ctypes.c_int32 * self.batch)(), (ctypes.c_int32 * self.batch)()
+        res = (ctypes.c_double * self.batch)()
+        st = torch.cuda.current_stream(self.device).cuda_stream
+        L.check(self.lib.fg_mb_debug_pressure_cg(self.handle, float(tol), int(max_iterations), int(bool(project_mean)), its, conv, res,
+                                                 ctypes.c_void_p(st)), lib=self.lib)
+        return {"iterations": list(its), "converged": [bool(c) for c in conv], "residual": list(res)}
 
     def set_pressure_deflation(self) -> float:
         """Keep the pressure-CG residuals orthogonal to the LEFT near-null vector of the pressure matrix instead of the

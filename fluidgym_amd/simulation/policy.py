@@ -34,6 +34,13 @@ benchmark line can say which mode it ran in:
     (``profiles/airfoil_trial_study.py``, ``profiles/r03_airfoil_trial_study.jsonl``: 4 runs x 4 envs x 3 env steps after 40
     development steps), so it is the default.  ``False`` gives the plain refined recurrence.
 
+``pressure_multilevel_fp64`` (default False)
+    The same preconditioner for ``dtype=torch.float64`` envs of the cylinder and airfoil families on 2-D meshes, where
+    ``pressure_multilevel`` / ``pressure_multilevel_bicgstab`` are honoured: the fp64 build applies it in kernel form -- the
+    pressure CG as a preconditioned recurrence of five launches per iteration, the pressure BiCGStab as the capped trial with the
+    unfused apply (``MultiBlockDomain.set_pressure_multilevel(fp64=True)``).  Same systems, same tolerances, the fp32 envs'
+    Krylov trajectory instead of the plain recurrences.  Off by default: a float64 env that does not ask for it runs what it ran.
+
 ``advection_line_preconditioner`` (default False)
     Single-block path: on grids refined towards a y wall (largest / smallest y width >= 3: the RBC and TCF families) every
     advection-diffusion BiCGStab is right-preconditioned by the tridiagonal part of its matrix along y (``csrc/fg_linepre.hip``)
@@ -103,8 +110,8 @@ benchmark line can say which mode it ran in:
     launches and two host reads per correction: not a fast path.
 
 Set with :func:`set_solver_policy` or the environment variables ``FLUIDGYM_AMD_PRESSURE_WARM_START`` / ``FLUIDGYM_AMD_ADVECTION_WARM_START`` /
-``FLUIDGYM_AMD_PRESSURE_STALL_ACCEPT`` / ``FLUIDGYM_AMD_PRESSURE_MULTILEVEL`` / ``FLUIDGYM_AMD_ADVECTION_LINE_PRECONDITIONER`` / ``FLUIDGYM_AMD_PRESSURE_MULTILEVEL_BICGSTAB`` (read once
-at import).
+``FLUIDGYM_AMD_PRESSURE_STALL_ACCEPT`` / ``FLUIDGYM_AMD_PRESSURE_MULTILEVEL`` / ``FLUIDGYM_AMD_ADVECTION_LINE_PRECONDITIONER`` / ``FLUIDGYM_AMD_PRESSURE_MULTILEVEL_BICGSTAB`` / ``FLUIDGYM_AMD_PRESSURE_MULTILEVEL_FP64``
+(read once at import).
 """
 from __future__ import annotations
 
@@ -123,6 +130,7 @@ _POLICY: Dict[str, Any] = {
     "native_wall_forcing": os.environ.get("FLUIDGYM_AMD_NATIVE_WALL_FORCING", "1") not in ("0", "", "false", "False"),
     "advection_jacobi": os.environ.get("FLUIDGYM_AMD_ADVECTION_JACOBI", "1") not in ("0", "", "false", "False"),
     "pressure_multilevel_bicgstab": os.environ.get("FLUIDGYM_AMD_PRESSURE_MULTILEVEL_BICGSTAB", "1") not in ("0", "", "false", "False"),
+    "pressure_multilevel_fp64": os.environ.get("FLUIDGYM_AMD_PRESSURE_MULTILEVEL_FP64", "0") not in ("0", "", "false", "False"),
     "pressure_refinement": int(os.environ.get("FLUIDGYM_AMD_PRESSURE_REFINEMENT", "0") or 0),
 }
 

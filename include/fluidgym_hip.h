@@ -641,7 +641,10 @@ int fg_mb_advection_jacobi_counts(fg_mb_handle h, int64_t* out2);
  * (k_mbc_onchip; up to 16 k cells, n4 <= 2048, n8 <= 512) applies it inside the persistent kernel, the pressure BiCGStab of any
  * mesh takes it as right preconditioner in kernel form (three launches per application).  a4 == NULL only switches it on / off
  * (enable).  The reference's CG / BiCGStab run without one (cg_solver_kernel.cu; its ILU0 is the fallback rung only); converged
- * answers agree to the solver tolerance, iteration counts drop 3-9x. */
+ * answers agree to the solver tolerance, iteration counts drop 3-9x.
+ * Both builds: in the fp64 build (fg_real = double) the tables arrive as doubles, the layouts of the fp32 on-chip / cluster kernels
+ * are left out, the pressure CG applies the preconditioner in kernel form (five launches per iteration, mb_cg) and the pressure
+ * BiCGStab takes the unfused apply. */
 int fg_mb_set_multilevel(fg_mb_handle h, int32_t n4, int32_t n8, const int32_t* a4_host, const int32_t* parent4_host,
                          const int32_t* rect4_host /* [n4][4]: first cell, width, height, row stride */, const fg_real* d4g_host,
                          const fg_real* aci8_host, fg_real geom_diag_sum, int32_t enable);
@@ -654,6 +657,11 @@ int fg_mb_debug_bicgstab(fg_mb_handle h, fg_real tol, int32_t max_iterations, in
 /* z = M r [B,N] with the kernel form of the multilevel preconditioner on the pressure matrix currently assembled (unit test of
  * the three kernels behind the preconditioned pressure BiCGStab; synchronises). */
 int fg_mb_multilevel_apply(fg_mb_handle h, const fg_real* r_BN, fg_real* z_BN, void* stream);
+/* One pressure CG solve, from zero, of the systems held in the pressure buffers (FG_MB_BUF_P_DIAG / _P_OFF, right-hand side
+ * FG_MB_BUF_DIV) under whatever fg_mb_set_multilevel has switched on; per env: iterations, converged (and finite), final RMS residual.
+ * Test entry (synchronises), both builds; an unconverged solve is reported through the outputs, not as an error. */
+int fg_mb_debug_pressure_cg(fg_mb_handle h, fg_real tol, int32_t max_iterations, int32_t project_mean, int32_t* iterations_B,
+                            int32_t* converged_B, double* residual_B, void* stream);
 /* z = U^-1 L^-1 r [B,d,N] with ILU(0) of the velocity matrix assembled by the last step: the preconditioner of the multi-block
  * BiCG_precondition_fallback rung (cuSPARSE ILU(0) in the reference, bicgstab_solver_kernel.cu:191-226; level-scheduled on the
  * mesh's neighbour table here).  Test entry (synchronises); FG_ERR_UNSUPPORTED in the fp64 build and on meshes in which a cell
