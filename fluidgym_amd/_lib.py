@@ -146,6 +146,8 @@ SIGNATURES = {
     "fg_bind": (c_int, [c_void_p, c_int, c_void_p]),
     "fg_set_viscosity": (c_int, [c_void_p, c_float]),
     "fg_set_scalar_viscosity": (c_int, [c_void_p, c_int, c_float]),
+    "fg_set_viscosity_batch": (c_int, [c_void_p, c_void_p]),
+    "fg_set_scalar_viscosity_batch": (c_int, [c_void_p, c_int, c_void_p]),
     "fg_set_fd_preconditioner": (c_int, [c_void_p] + [POINTER(c_float)] * 7),
     "fg_max_velocity": (c_int, [c_void_p, c_void_p, c_void_p]),
     "fg_set_fd_fast_transform": (c_int, [c_void_p, c_int, c_float]),
@@ -190,6 +192,7 @@ SIGNATURES = {
     "fg_mb_debug_ilu_apply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "fg_mb_debug_pressure_cg": (c_int, [c_void_p, c_float, c_int32, c_int32, POINTER(c_int32), POINTER(c_int32), POINTER(ctypes.c_double), c_void_p]),
     "fg_mb_wall_forces": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_float, c_float, c_void_p, c_void_p]),
+    "fg_mb_wall_forces_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_float, c_float, c_void_p, c_void_p, c_void_p]),
     "fg_mb_debug_bicgstab": (c_int, [c_void_p, c_float, c_int32, c_int32, POINTER(c_int64), POINTER(ctypes.c_double), POINTER(c_float), c_void_p]),
     "fg_dacc_host_sum": (c_int, [POINTER(ctypes.c_double), c_int64, ctypes.c_double, POINTER(ctypes.c_double)]),
     "fg_dacc_device_sum": (c_int, [POINTER(ctypes.c_double), c_int64, ctypes.c_double, c_int32, POINTER(ctypes.c_double), c_void_p]),
@@ -208,6 +211,8 @@ SIGNATURES = {
     "fg_envglue_jet_schedule": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "fg_envglue_channel_observe": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_void_p,
                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fg_envglue_channel_observe_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_float, c_void_p,
+                                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fg_mb_create": (c_int, [c_int32, c_int32, c_int32, POINTER(c_void_p)]),
     "fg_mb_destroy": (c_int, [c_void_p]),
     "fg_config_dump": (c_int, [c_void_p, ctypes.c_char_p, c_int]),
@@ -224,6 +229,7 @@ SIGNATURES = {
     "fg_mb_get_neighbors": (c_int, [c_void_p, POINTER(c_int32)]),
     "fg_mb_bind": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fg_mb_set_viscosity": (c_int, [c_void_p, c_float]),
+    "fg_mb_set_viscosity_batch": (c_int, [c_void_p, c_void_p]),
     "fg_mb_piso_step": (c_int, [c_void_p, c_void_p, POINTER(FgMbStepOptions), POINTER(c_int32), c_void_p]),
     "fg_mb_max_velocity": (c_int, [c_void_p, POINTER(c_float), c_void_p]),
     "fg_mb_set_residual_projection": (c_int, [c_void_p, POINTER(c_float)]),

@@ -224,6 +224,20 @@ extern "C" int fg_set_scalar_viscosity(fg_handle s, int ch, fg_real v) {
     s->scalar_viscosity_set = true;
     return FG_OK;
 }
+// per-env arrays: borrowed like dt_B, read by the kernels at launch (the values may be rewritten between steps); a factorisation made
+// ahead for other values is dropped here, and fg_piso_step never carries one across steps
+extern "C" int fg_set_viscosity_batch(fg_handle s, const fg_real* nu_B) {
+    FG_REQUIRE(s, FG_ERR_INVALID_ARG, "null handle");
+    s->viscosity_B = nu_B;
+    s->helm_pre_mask = 0;
+    return FG_OK;
+}
+extern "C" int fg_set_scalar_viscosity_batch(fg_handle s, int ch, const fg_real* k_B) {
+    FG_REQUIRE(s && ch >= 0 && ch < FG_MAX_SCALARS, FG_ERR_INVALID_ARG, "bad channel");
+    s->scalar_viscosity_B[ch] = k_B;
+    s->helm_pre_mask = 0;
+    return FG_OK;
+}
 
 extern "C" int fg_set_fd_preconditioner(fg_handle s, const float* Qx, const float* QxT, const float* Qz, const float* QzT,
                                         const float* lower, const float* inv, const float* cp) {
@@ -344,7 +358,7 @@ extern "C" int fg_debug_apply_preconditioner(fg_handle s, int mode, int nc, cons
         // the velocity system's operator (both y walls prescribed), factorised and applied as the Helmholtz-preconditioned BiCGStab does
         FG_REQUIRE(s->fd_lam != nullptr, FG_ERR_UNSUPPORTED, "fg_debug_apply_preconditioner: mode 3 needs fg_set_fd_helmholtz (fp32 build)");
         FG_REQUIRE(s->adv_last_dt != nullptr, FG_ERR_INVALID_ARG, "fg_debug_apply_preconditioner: mode 3 needs a velocity fg_setup_advection first");
-        if (int rc = fg_helm_factor(s, s->adv_last_dt, s->viscosity, 1, 1, nc, st)) return rc;
+        if (int rc = fg_helm_factor(s, s->adv_last_dt, fg_nu(s), 1, 1, nc, st)) return rc;
         if (int rc = fg_fd_helmholtz_apply(s, nc, r, z, st)) return rc;
     } else if (mode == 4) {
         if (int rc = fg_ilu_alloc(s)) return rc;
@@ -505,7 +519,7 @@ static int setup_advection(fg_handle s, const fg_real* dt_B, int for_scalar, int
         a.scal = s->scalar + (size_t)channel * s->grid.n;
         a.scal_env_stride = (long)s->cfg.n_scalars * s->grid.n;
         // getViscosity(domain, forPassiveScalar, ch) (PISO_multiblock_cuda_kernel.cu:1803-1815)
-        a.nu = s->scalar_viscosity_set ? s->scalar_viscosity[channel] : s->viscosity;
+        a.nu = fg_nu(s, 1, channel);
     } else {
         a.source = s->velocity_source;
         // wall-stress forcing (fg_set_wall_stress_forcing; the env's PRE hook, tcf_env.py / grid.py:147-176): recomputed from u^n for
@@ -515,7 +529,7 @@ static int setup_advection(fg_handle s, const fg_real* dt_B, int for_scalar, int
             if (int rc = fg_launch_wall_forcing(s, (hipStream_t)stream)) return rc;
         a.force = s->wall_forcing_axis >= 0 ? s->force_uniform : nullptr;
         a.visc = s->visc_field;
-        a.nu = s->viscosity;
+        a.nu = fg_nu(s);
         a.rA = s->rA;
         s->adv_last_dt = dt_B;
         s->rA_epoch++;
@@ -705,7 +719,7 @@ static int advection_solve(fg_state* s, FgBicgArgs a, fg_solve_info* info, hipSt
     a.precond = (s->adv_precond == 1) ? 1 : (s->adv_precond == 3 ? 2 : (s->adv_precond == 4 ? 3 : 0));
     if (a.precond == 2 && !for_scalar && s->visc_field) a.precond = 0;   // the Helmholtz operator is built for ONE viscosity
     if (a.precond == 2) {   // Helmholtz (fast-diagonalisation) preconditioner: the diffusivity and wall treatment of THIS solve
-        a.nu = for_scalar ? (s->scalar_viscosity_set ? s->scalar_viscosity[channel] : s->viscosity) : s->viscosity;
+        a.nu = fg_nu(s, for_scalar, channel);
         a.wall_lo = for_scalar ? (s->cfg.scalar_bc[2][channel] == FG_DIRICHLET) : 1;
         a.wall_hi = for_scalar ? (s->cfg.scalar_bc[3][channel] == FG_DIRICHLET) : 1;
     }
@@ -747,6 +761,9 @@ extern "C" int fg_piso_step(fg_handle s, const fg_real* dt_B, const fg_step_opti
     const int B = s->grid.B, d = s->grid.dims;
     std::vector<fg_solve_info> info((size_t)B * d);
     int32_t stats[4] = {-1, -1, -1, -1};
+    // a Helmholtz factor set made ahead (fg_helm_factor_pair below) serves the solves of THIS step only: a per-env array rewritten in
+    // place keeps its address, so a record left unconsumed must not outlive the step
+    struct DropHelmRecord { fg_state* s; ~DropHelmRecord() { s->helm_pre_mask = 0; } } drop_helm_record{s};
     int status = FG_OK;
     auto soft = [&](int rc) {  // non-convergence is reported, not fatal (pressure_return_best_result=True)
         if (rc == FG_ERR_NOT_CONVERGED) { status = rc; return FG_OK; }
@@ -760,7 +777,7 @@ extern "C" int fg_piso_step(fg_handle s, const fg_real* dt_B, const fg_step_opti
     //  sweeps hand over makes its own, fg_helm_factor)
     const bool sweeps_first = s->adv_linesweep && s->grid.dims == 2 && s->jac_hist[0].skip == 0 && s->jac_hist[1].skip == 0;
     if (scalar && s->cfg.n_scalars == 1 && s->adv_precond == 3 && s->fd_lam && !s->visc_field && !sweeps_first) {
-        const float nu2[2] = {s->scalar_viscosity_set ? s->scalar_viscosity[0] : s->viscosity, s->viscosity};
+        const FgNu nu2[2] = {fg_nu(s, 1, 0), fg_nu(s)};
         const int wlo[2] = {s->cfg.scalar_bc[2][0] == FG_DIRICHLET, 1}, whi[2] = {s->cfg.scalar_bc[3][0] == FG_DIRICHLET, 1};
         if (int rc = fg_helm_factor_pair(s, dt_B, nu2, wlo, whi, st)) return rc;
     }

@@ -45,10 +45,10 @@ __device__ __forceinline__ double wave_sum(double v) {
 }
 
 // one workgroup per env: cross = mean(v^2), shear = scale * (mean_x u[y=0] + mean_x u[y=Y-1]), reward = -(shear + penalty * cross),
-// obs_u[b][s][c] = u[b][c][sensor s], obs_p[b][s] = p[b][sensor s]
+// obs_u[b][s][c] = u[b][c][sensor s], obs_p[b][s] = p[b][sensor s]; scale_B (optional, [B]): env b's own shear scale (per-env viscosity)
 __global__ __launch_bounds__(256) void k_channel_observe(const float* __restrict__ u, const float* __restrict__ p,
                                                           const int64_t* __restrict__ sensor, int S, int Y, int X, float shear_scale,
-                                                          float penalty, float* __restrict__ obs_u, float* __restrict__ obs_p,
+                                                          const float* __restrict__ scale_B, float penalty, float* __restrict__ obs_u, float* __restrict__ obs_p,
                                                           float* __restrict__ cross, float* __restrict__ shear,
                                                           float* __restrict__ reward) {
     __shared__ double red[3][4];
@@ -76,7 +76,7 @@ __global__ __launch_bounds__(256) void k_channel_observe(const float* __restrict
         const double c = ((red[0][0] + red[0][1]) + (red[0][2] + red[0][3])) / (double)cells;
         const double l = ((red[1][0] + red[1][1]) + (red[1][2] + red[1][3])) / (double)X;
         const double h = ((red[2][0] + red[2][1]) + (red[2][2] + red[2][3])) / (double)X;
-        const float cf = (float)c, sf = shear_scale * (float)(l + h);
+        const float cf = (float)c, sf = (scale_B ? scale_B[b] : shear_scale) * (float)(l + h);
         cross[b] = cf;
         shear[b] = sf;
         reward[b] = -(sf + penalty * cf);
@@ -103,7 +103,20 @@ extern "C" int fg_envglue_channel_observe(const float* velocity, const float* pr
                    ny > 1 && nx > 0 && nx % 4 == 0,
                FG_ERR_INVALID_ARG, "fg_envglue_channel_observe: bad argument (nx must be a multiple of 4)");
     hipLaunchKernelGGL(k_channel_observe, dim3(batch), dim3(256), 0, (hipStream_t)stream, velocity, pressure, sensor, n_sensors, ny, nx,
-                       shear_scale, penalty, obs_velocity, obs_pressure, cross, shear, reward);
+                       shear_scale, (const float*)nullptr, penalty, obs_velocity, obs_pressure, cross, shear, reward);
+    FG_HIP_CHECK(hipGetLastError());
+    return FG_OK;
+}
+
+extern "C" int fg_envglue_channel_observe_batch(const float* velocity, const float* pressure, const int64_t* sensor, int32_t n_sensors,
+                                                int32_t batch, int32_t ny, int32_t nx, const float* shear_scale_B, float penalty,
+                                                float* obs_velocity, float* obs_pressure, float* cross, float* shear, float* reward,
+                                                void* stream) {
+    FG_REQUIRE(velocity && pressure && sensor && shear_scale_B && obs_velocity && obs_pressure && cross && shear && reward && n_sensors > 0 &&
+                   batch > 0 && ny > 1 && nx > 0 && nx % 4 == 0,
+               FG_ERR_INVALID_ARG, "fg_envglue_channel_observe_batch: bad argument (nx must be a multiple of 4)");
+    hipLaunchKernelGGL(k_channel_observe, dim3(batch), dim3(256), 0, (hipStream_t)stream, velocity, pressure, sensor, n_sensors, ny, nx,
+                       0.f, shear_scale_B, penalty, obs_velocity, obs_pressure, cross, shear, reward);
     FG_HIP_CHECK(hipGetLastError());
     return FG_OK;
 }

@@ -24,7 +24,7 @@ int fg_line_alloc(fg_state*) {
 }
 int fg_helm_alloc(fg_state*) { return FG_ERR_UNSUPPORTED; }
 // (fg_ilu_*: fg_ilu0.hip -- ILU(0) runs in doubles, the preconditioner of the fp64 build's advection-diffusion rungs)
-int fg_helm_factor(fg_state*, const fg_real*, fg_real, int, int, int, hipStream_t, int) { return FG_ERR_UNSUPPORTED; }
+int fg_helm_factor(fg_state*, const fg_real*, FgNu, int, int, int, hipStream_t, int) { return FG_ERR_UNSUPPORTED; }
 int fg_fd_helmholtz_apply(fg_state*, int, const fg_real*, fg_real*, hipStream_t) { return FG_ERR_UNSUPPORTED; }
 int fg_line_factor(fg_state*, const fg_real*, const fg_real*, int, hipStream_t) { return FG_ERR_UNSUPPORTED; }
 int fg_line_apply(fg_state*, const fg_real*, const fg_real*, int, const fg_real*, fg_real*, hipStream_t) { return FG_ERR_UNSUPPORTED; }

@@ -708,13 +708,26 @@ struct FgPrepared {
     }
 };
 
+// A diffusivity as the kernels take it: one value for the batch, or a device array [B] read as per_env[b] where it is installed
+// (fg_set_viscosity_batch / fg_set_scalar_viscosity_batch) -- a wave-uniform load per workgroup, the arithmetic behind it unchanged.
+struct FgNu {
+    fg_real v = 0; const fg_real* per_env = nullptr;
+#ifdef __HIPCC__
+    __device__ __forceinline__ fg_real at(int b) const { return per_env ? per_env[b] : v; }
+#endif
+    bool same(const FgNu& o) const { return v == o.v && per_env == o.per_env; }
+};
+
 struct fg_state {
     fg_config cfg;
     FgGrid grid;
     int vec;  // 4 if nx % 4 == 0 else 1
+    // read through fg_nu() below, nowhere else: per-env arrays (borrowed device [B], nullptr = the scalar) sit next to the scalars
     fg_real viscosity;
     fg_real scalar_viscosity[FG_MAX_SCALARS];
     bool scalar_viscosity_set;
+    const fg_real* viscosity_B;
+    const fg_real* scalar_viscosity_B[FG_MAX_SCALARS];
     // metrics (owned)
     fg_real* d_h[3];
     fg_real* d_rh[3];
@@ -792,7 +805,7 @@ struct fg_state {
     float* helm_lower_row; float helm_rs; int helm_cb, helm_rowform_off, helm_cb_pref;
     // second factor set + the record of a factorisation made ahead of the solves (fg_helm_factor_pair): which sets are valid, for which
     // dt array / diffusivity / wall conditions; helm_set = the set the last fg_helm_factor selected for fg_helm_apply
-    float* line_inv2; float* line_cp2; float* helm_lower_row2; int helm_pre_mask; const fg_real* helm_pre_dt; float helm_pre_nu[2]; int helm_pre_walls[2][2]; int helm_set;
+    float* line_inv2; float* line_cp2; float* helm_lower_row2; int helm_pre_mask; const fg_real* helm_pre_dt; FgNu helm_pre_nu[2]; int helm_pre_walls[2][2]; int helm_set;
     int tridiag_cb;               // FG_TRIDIAG_CB at fg_create: 64 keeps 64-column workgroups in k_tridiag_y_lds (default: 32 where they divide)
     // x axis marked as a cosine-transform axis (uniform width, FIXED ends): fg_fdfft.hip replaces the two x GEMMs
     int fd_dct_x; float2* fd_dct_tw; float2* fd_dct_rot; float fd_dct_fwd[2]; float fd_dct_inv[2];
@@ -830,6 +843,15 @@ struct fg_state {
     FgPrepared prepared;          // kept on the handle: the stepwise entry points (fg_setup_pressure_rhs, then fg_solve_pressure) hand it across calls
     size_t n_cells() const { return (size_t)grid.n; }
 };
+// THE reader of the handle's viscosity and scalar diffusivities (getViscosity(domain, forPassiveScalar, ch),
+// PISO_multiblock_cuda_kernel.cu:1803-1815): a channel's own array, else its scalar once any channel was set, else the velocity's
+inline FgNu fg_nu(const fg_state* s, int for_scalar = 0, int channel = 0) {
+    FgNu n;
+    if (for_scalar && s->scalar_viscosity_B[channel]) { n.v = s->scalar_viscosity[channel]; n.per_env = s->scalar_viscosity_B[channel]; }
+    else if (for_scalar && s->scalar_viscosity_set) n.v = s->scalar_viscosity[channel];
+    else { n.v = s->viscosity; n.per_env = s->viscosity_B; }
+    return n;
+}
 
 void fg_set_error(const std::string& msg);
 // argument / state check of an extern "C" entry point: record the message for fg_last_error() and return the status
@@ -893,7 +915,7 @@ struct FgAdvArgs {
     const fg_real* source;   // velocity source [B,d,N] or nullptr
     const fg_real* force;    // uniform body force per env [B,d] or nullptr (fg_set_wall_stress_forcing): added like a source of that value
     const fg_real* dt;       // [B]
-    fg_real nu;              // viscosity (or scalar diffusivity)
+    FgNu nu;                 // viscosity (or scalar diffusivity): the batch's value or a per-env array
     const fg_real* visc;     // optional per-cell viscosity [B,N] of the velocity system (Block.setViscosity: SGS models); nullptr = nu
     int for_scalar;
     int channel, n_scalars;
@@ -993,7 +1015,7 @@ struct FgBicgArgs {
     int precond = 0;   // 3: by ILU(0) of the matrix (fg_ilu0.hip, the reference's preconditioner);
                        // 1: right-preconditioned by the y-line solve of fg_linepre.hip (v = C M^-1 p, t = C M^-1 s); 2: by the
                        // separable Helmholtz operator I/dt - nu Laplacian (fast diagonalisation, fg_fd_helmholtz_apply)
-    fg_real nu = 0; int wall_lo = 1, wall_hi = 1;   // precond == 2: diffusivity of this solve; the variable is prescribed at the -y / +y wall
+    FgNu nu; int wall_lo = 1, wall_hi = 1;          // precond == 2: diffusivity of this solve; the variable is prescribed at the -y / +y wall
     int kind = 1;      // which poll predictor the solve reads and updates (fg_state::pred_bicg): 0 scalar, 1 velocity
     FgSpecHook spec;   // optional
 };
@@ -1075,8 +1097,8 @@ int fg_ilu_alloc(fg_state* s);
 int fg_ilu_factor(fg_state* s, const fg_real* diag, const fg_real* off, hipStream_t st);
 int fg_ilu_apply(fg_state* s, const fg_real* diag, const fg_real* off, int nc, const fg_real* r, fg_real* z, hipStream_t st);
 int fg_helm_alloc(fg_state* s);
-int fg_helm_factor(fg_state* s, const fg_real* dt, fg_real nu, int wall_lo, int wall_hi, int nc, hipStream_t st, int kind = -1);
-int fg_helm_factor_pair(fg_state* s, const float* dt, const float nu[2], const int wall_lo[2], const int wall_hi[2], hipStream_t st);
+int fg_helm_factor(fg_state* s, const fg_real* dt, FgNu nu, int wall_lo, int wall_hi, int nc, hipStream_t st, int kind = -1);
+int fg_helm_factor_pair(fg_state* s, const float* dt, const FgNu nu[2], const int wall_lo[2], const int wall_hi[2], hipStream_t st);
 int fg_helm_apply(fg_state* s, int nc, const float* r, float* z, hipStream_t st);   // z = M^-1 r with the factors of the last fg_helm_factor (r == z allowed)
 // z = M^-1 r with M the separable Helmholtz operator factorised by fg_helm_factor: basis change along x (and z), tridiagonal solve
 // along y per mode and env, basis change back (fg_fdprecond.hip)

@@ -426,13 +426,14 @@ __global__ __launch_bounds__(256) void k_line_apply_y_stream(LineArgs a, const f
 // s = hx hz (the library's eigenvectors are H-orthonormal: Q^T H Q = I, so Q T^-1 Q^T r carries a factor 1/(hx hz)).  A FIXED y
 // face contributes the one-sided coefficient 2 / hy_j^2 when the variable is prescribed there (velocity; Dirichlet scalar) and
 // nothing for a Neumann scalar -- exactly the diffusion part of k_adv_build's matrix (PISO_multiblock_cuda_kernel.cu:3616-3880).
-__global__ __launch_bounds__(256) void k_helm_coeffs(FgGrid g, const float* __restrict__ dt, const float* __restrict__ lam, float nu,
+__global__ __launch_bounds__(256) void k_helm_coeffs(FgGrid g, const float* __restrict__ dt, const float* __restrict__ lam, FgNu nu_in,
                                                       int wall_lo, int wall_hi, float* __restrict__ diag, float* __restrict__ lower,
                                                       float* __restrict__ upper) {
     const int b = blockIdx.y;
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= g.n || !(dt[b] > 0.f)) return;
     const int a = idx % g.nx, j = (idx / g.nx) % g.ny, c = idx / (g.nx * g.ny);
+    const float nu = nu_in.at(b);
     const float rs = g.rh[0][0] * (g.dims == 3 ? g.rh[2][0] : 1.f);   // uniform transform axes
     // face coefficient = mean of the two cells' alpha = J / h^2 (getLaplaceCoefficientOrthogonal, K.cu:1224-1239), over the cell volume
     const float ry = g.rh[1][j];
@@ -454,13 +455,13 @@ __global__ __launch_bounds__(256) void k_helm_coeffs(FgGrid g, const float* __re
 // 48 KB, three workgroups per CU, every workgroup of the launch resident at once.
 struct HelmArgs {
     const float* dt; const float* lam; const float* rhy;     // [B] | [nx] eigenvalues of the periodic x operator | 1 / hy [ny]
-    float nu, rs; int wall_lo, wall_hi;
+    FgNu nu; float rs; int wall_lo, wall_hi;                  // diffusivity: the batch's value or per env
     float* inv; float* cp; float* lower_row;                  // [B][N] | [B][N] | [B][ny]
     int nx, ny, nc;
     const int32_t* flags;                                     // nullptr (factorisation ahead of the solves): every env with dt > 0
     // second parameter set (blockIdx.z == 1 of the factorisation): the scalar and the velocity system of a PISO step differ in their
     // diffusivity and wall condition only, so both factorisations are ONE launch at the start of the step (fg_helm_factor_pair)
-    float nu2; int wall_lo2, wall_hi2; float* inv2; float* cp2; float* lower_row2;
+    FgNu nu2; int wall_lo2, wall_hi2; float* inv2; float* cp2; float* lower_row2;
 };
 __device__ __forceinline__ void helm_row(const HelmArgs& a, int j, float& lo, float& hi) {
     // face coefficient = mean of the two cells' alpha = J / h^2 (getLaplaceCoefficientOrthogonal, K.cu:1224-1239), over the cell volume;
@@ -483,19 +484,20 @@ __global__ __launch_bounds__(64) void k_helm_factor_y(HelmArgs a) {
     const int col = blockIdx.x * 64 + threadIdx.x;
     if (!any || !(a.dt[b] > 0.f)) return;
     const int nyp = (a.ny + 7) & ~7;
+    const float nu = a.nu.at(b);
     for (int j = threadIdx.x; j < nyp; j += 64) {
         if (j < a.ny) {
             float lo, hi;
             helm_row(a, j, lo, hi);
-            const float l = j > 0 ? -a.nu * lo * a.rs : 0.f;
+            const float l = j > 0 ? -nu * lo * a.rs : 0.f;
             sl[j] = l;
-            su[j] = j < a.ny - 1 ? -a.nu * hi * a.rs : 0.f;
-            sb[j] = a.nu * (lo + hi);
+            su[j] = j < a.ny - 1 ? -nu * hi * a.rs : 0.f;
+            sb[j] = nu * (lo + hi);
             if (blockIdx.x == 0) a.lower_row[b * a.ny + j] = l;
         } else { sl[j] = 0.f; su[j] = 0.f; sb[j] = 0.f; }      // padding rows (never stored)
     }
     __syncthreads();
-    const float sig = 1.f / a.dt[b] - a.nu * a.lam[col];       // (nx is a multiple of 64: every lane owns a mode)
+    const float sig = 1.f / a.dt[b] - nu * a.lam[col];         // (nx is a multiple of 64: every lane owns a mode)
     const size_t N = (size_t)a.nx * a.ny;
     float* __restrict__ iv = a.inv + (size_t)b * N + col;
     float* __restrict__ cp = a.cp + (size_t)b * N + col;
@@ -712,7 +714,7 @@ static int helm_cb(const fg_state* s) {      // columns per workgroup of the app
 
 // both factorisations of a PISO step with a passive scalar (set 0: scalar, set 1: velocity) in one launch, ahead of the solves;
 // fg_helm_factor then finds the record and launches nothing.  Row form only (returns FG_OK without a record otherwise).
-int fg_helm_factor_pair(fg_state* s, const float* dt, const float nu[2], const int wall_lo[2], const int wall_hi[2], hipStream_t st) {
+int fg_helm_factor_pair(fg_state* s, const float* dt, const FgNu nu[2], const int wall_lo[2], const int wall_hi[2], hipStream_t st) {
     s->helm_pre_mask = 0;
     if (!helm_cb(s) || !s->line_inv2) return FG_OK;
     HelmArgs a = {};
@@ -728,10 +730,10 @@ int fg_helm_factor_pair(fg_state* s, const float* dt, const float nu[2], const i
 
 // coefficients + Thomas factorisation of the Helmholtz preconditioner for this solve (dt per env, nu of the solve); kind = the
 // factor set a record of fg_helm_factor_pair may already hold (0 scalar, 1 velocity)
-int fg_helm_factor(fg_state* s, const float* dt, float nu, int wall_lo, int wall_hi, int nc, hipStream_t st, int kind) {
+int fg_helm_factor(fg_state* s, const float* dt, FgNu nu, int wall_lo, int wall_hi, int nc, hipStream_t st, int kind) {
     s->helm_cb = helm_cb(s);
     s->helm_set = 0;
-    if (s->helm_cb && kind >= 0 && kind < 2 && ((s->helm_pre_mask >> kind) & 1) && s->helm_pre_dt == dt && s->helm_pre_nu[kind] == nu &&
+    if (s->helm_cb && kind >= 0 && kind < 2 && ((s->helm_pre_mask >> kind) & 1) && s->helm_pre_dt == dt && s->helm_pre_nu[kind].same(nu) &&
         s->helm_pre_walls[kind][0] == wall_lo && s->helm_pre_walls[kind][1] == wall_hi) {
         s->helm_pre_mask &= ~(1 << kind);
         s->helm_set = kind;

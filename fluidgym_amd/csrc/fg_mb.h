@@ -61,6 +61,12 @@ struct MbBlock {
     std::vector<double> det;     // [ncells]
 };
 
+// the viscosity as the step's kernels take it: the handle's scalar, or env b's entry of an installed array (fg_mb_set_viscosity_batch)
+struct MbNu {
+    mb_real v; const mb_real* per_env;
+    __device__ __forceinline__ mb_real at(int b) const { return per_env ? per_env[b] : v; }
+};
+
 // device view handed to kernels by value
 struct MbDev {
     int d, F, N, NB, B;
@@ -89,6 +95,7 @@ struct MbDev {
 struct fg_mb_state {
     int d = 2, B = 1, N = 0, NB = 0, F = 4;
     mb_real nu = 0.f;
+    const mb_real* nu_B = nullptr;   // borrowed device [B]: per-env viscosities (fg_mb_set_viscosity_batch), nullptr = nu
     int quirk_diag_offset = 1;  // computeConnectedPos(..., borderOffset = 1) on diagonal walks (K.cu:2152, 2658, 2825)
     int quirk_first_layer = 1;  // K.cu:1952
     int nonortho_flags = 25;    // CENTER_MATRIX | DIRECT_MATRIX | DIAGONAL_RHS (the simulation's mode) or 10 = DIRECT_RHS | DIAGONAL_RHS

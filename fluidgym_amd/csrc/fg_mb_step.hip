@@ -76,13 +76,14 @@ __device__ __forceinline__ mb_real mb_flux(const MbDev& D, const mb_real* __rest
 }
 
 template <int DIMS>
-__global__ __launch_bounds__(FG_BLOCK) void k_mb_matrix(MbDev D, const mb_real* __restrict__ dt, mb_real nu,
+__global__ __launch_bounds__(FG_BLOCK) void k_mb_matrix(MbDev D, const mb_real* __restrict__ dt, MbNu nu_in,
                                                          const mb_real* __restrict__ cc, const mb_real* __restrict__ fb,
                                                          mb_real* __restrict__ Cdiag, mb_real* __restrict__ Coff,
                                                          mb_real* __restrict__ rA) {
     MB_CELL
     if (!valid || !mb_active(dt, b)) return;
     constexpr int F = 2 * DIMS;
+    const mb_real nu = nu_in.at(b);
     const mb_real det = D.T[(size_t)i * (DIMS * DIMS + 1) + DIMS * DIMS];
     const mb_real* cc_b = cc + (size_t)b * DIMS * N;
     const mb_real* fb_b = fb + (size_t)b * D.NB;
@@ -126,12 +127,13 @@ __device__ __forceinline__ mb_real mb_boundary_source(const MbDev& D, const mb_r
 
 // velocity right-hand side (kPISO_build_advection_RHS): grid.z = component
 template <int DIMS>
-__global__ __launch_bounds__(FG_BLOCK) void k_mb_vrhs(MbDev D, const mb_real* __restrict__ dt, mb_real nu,
+__global__ __launch_bounds__(FG_BLOCK) void k_mb_vrhs(MbDev D, const mb_real* __restrict__ dt, MbNu nu_in,
                                                        const mb_real* __restrict__ u_old, const mb_real* __restrict__ u_res,
                                                        const mb_real* __restrict__ ub, const mb_real* __restrict__ fb,
                                                        const mb_real* __restrict__ src, mb_real* __restrict__ rhs) {
     MB_CELL
     if (!valid || !mb_active(dt, b)) return;
+    const mb_real nu = nu_in.at(b);
     const int c = blockIdx.z;
     const size_t vb = ((size_t)b * DIMS + c) * N;
     const mb_real* ub_c = ub + ((size_t)b * DIMS + c) * D.NB;
@@ -209,7 +211,7 @@ static void mb_slots_written(fg_mb_state* s) {
 
 // h = (u_old/dt - H u* + S) / A   (PISO_build_pressure_rhs): grid.z = component
 template <int DIMS>
-__global__ __launch_bounds__(FG_BLOCK) void k_mb_h(MbDev D, const mb_real* __restrict__ dt, mb_real nu,
+__global__ __launch_bounds__(FG_BLOCK) void k_mb_h(MbDev D, const mb_real* __restrict__ dt, MbNu nu_in,
                                                     const mb_real* __restrict__ rA, const mb_real* __restrict__ Coff,
                                                     const mb_real* __restrict__ u_old, const mb_real* __restrict__ u_star,
                                                     const mb_real* __restrict__ ub, const mb_real* __restrict__ fb,
@@ -217,6 +219,7 @@ __global__ __launch_bounds__(FG_BLOCK) void k_mb_h(MbDev D, const mb_real* __res
     MB_CELL
     if (!valid || !mb_active(dt, b)) return;
     constexpr int F = 2 * DIMS;
+    const mb_real nu = nu_in.at(b);
     const int c = blockIdx.z;
     const size_t vb = ((size_t)b * DIMS + c) * N;
     const mb_real det = D.T[(size_t)i * (DIMS * DIMS + 1) + DIMS * DIMS];
@@ -724,10 +727,11 @@ extern "C" int fg_mb_bind(fg_mb_handle s, mb_real* velocity, mb_real* pressure_r
 __global__ __launch_bounds__(FG_BLOCK) void k_mb_wall_forces(int d, int N, int NB, int n, int layers, const mb_real* __restrict__ u,
                                                               const mb_real* __restrict__ ub, const mb_real* __restrict__ p,
                                                               const int32_t* __restrict__ cell_index, const int32_t* __restrict__ slot_index,
-                                                              const mb_real* __restrict__ geom, mb_real area_scale, mb_real nu,
+                                                              const mb_real* __restrict__ geom, mb_real area_scale, MbNu nu_in,
                                                               mb_real* __restrict__ out) {
     __shared__ mb_real lds[8];
     const int layer = blockIdx.x, b = blockIdx.y;
+    const mb_real nu = nu_in.at(b);
     const mb_real* ue = u + (size_t)b * d * N;
     const mb_real* ube = ub + (size_t)b * d * NB;
     const mb_real* pe = p + (size_t)b * N;
@@ -763,7 +767,20 @@ extern "C" int fg_mb_wall_forces(fg_mb_handle s, const int32_t* cell_index, cons
     FG_REQUIRE(cell_index && slot_index && geom && out && n > 0 && layers > 0, FG_ERR_INVALID_ARG, "fg_mb_wall_forces: bad argument");
     hipLaunchKernelGGL(k_mb_wall_forces, dim3(layers, s->B), dim3(FG_BLOCK), 0, (hipStream_t)stream, s->d, s->N, s->NB, n, layers,
                        (const mb_real*)s->velocity, (const mb_real*)s->bvel, (const mb_real*)s->pressure, cell_index, slot_index, geom, area_scale,
-                       viscosity, out);
+                       MbNu{viscosity, nullptr}, out);
+    FG_HIP_CHECK(hipGetLastError());
+    return FG_OK;
+}
+// the same sums with env b's own viscosity: viscosity_B [B] on the device (read at launch, like the handle's own array), nullptr =
+// the scalar for every env
+extern "C" int fg_mb_wall_forces_batch(fg_mb_handle s, const int32_t* cell_index, const int32_t* slot_index, const mb_real* geom, int32_t n,
+                                       int32_t layers, mb_real area_scale, mb_real viscosity, const mb_real* viscosity_B, mb_real* out,
+                                       void* stream) {
+    FG_REQUIRE(s && s->finalized && s->velocity && s->pressure && s->bvel, FG_ERR_NOT_BOUND, "fg_mb_wall_forces_batch: fields not bound");
+    FG_REQUIRE(cell_index && slot_index && geom && out && n > 0 && layers > 0, FG_ERR_INVALID_ARG, "fg_mb_wall_forces_batch: bad argument");
+    hipLaunchKernelGGL(k_mb_wall_forces, dim3(layers, s->B), dim3(FG_BLOCK), 0, (hipStream_t)stream, s->d, s->N, s->NB, n, layers,
+                       (const mb_real*)s->velocity, (const mb_real*)s->bvel, (const mb_real*)s->pressure, cell_index, slot_index, geom, area_scale,
+                       MbNu{viscosity, viscosity_B}, out);
     FG_HIP_CHECK(hipGetLastError());
     return FG_OK;
 }
@@ -773,11 +790,24 @@ extern "C" int fg_mb_set_viscosity(fg_mb_handle s, mb_real nu) {
     s->nu = nu;
     return FG_OK;
 }
+// per-env viscosities: a borrowed device array [B] the step's kernels read at launch (nullptr: back to the scalar).  Every entry
+// must be positive, as the scalar must: checked here, once, on a host copy -- never inside a step
+extern "C" int fg_mb_set_viscosity_batch(fg_mb_handle s, const mb_real* nu_B) {
+    FG_REQUIRE(s, FG_ERR_INVALID_ARG, "fg_mb_set_viscosity_batch: null handle");
+    if (nu_B) {
+        std::vector<mb_real> host((size_t)s->B);
+        FG_HIP_CHECK(hipMemcpy(host.data(), nu_B, sizeof(mb_real) * host.size(), hipMemcpyDeviceToHost));
+        for (mb_real v : host) FG_REQUIRE(v > 0.f, FG_ERR_INVALID_ARG, "fg_mb_set_viscosity_batch: every viscosity must be positive");
+    }
+    s->nu_B = nu_B;
+    return FG_OK;
+}
 
 extern "C" int fg_mb_piso_step(fg_mb_handle s, const mb_real* dt_B, const fg_mb_step_options* opt, int32_t* stats_host, void* stream) {
     FG_REQUIRE(s && s->finalized && s->velocity, FG_ERR_NOT_BOUND, "fg_mb_piso_step: fields not bound");
     FG_REQUIRE(dt_B && opt, FG_ERR_INVALID_ARG, "fg_mb_piso_step: null argument");
-    FG_REQUIRE(s->nu > 0.f, FG_ERR_INVALID_ARG, "fg_mb_piso_step: viscosity not set");
+    FG_REQUIRE(s->nu > 0.f || s->nu_B, FG_ERR_INVALID_ARG, "fg_mb_piso_step: viscosity not set");
+    const MbNu nu = {s->nu, s->nu_B};
     hipStream_t st = (hipStream_t)stream;
     const int B = s->B, N = s->N, d = s->d, NB = s->NB;
     const int cells = std::max(N, NB);
@@ -807,11 +837,11 @@ extern "C" int fg_mb_piso_step(fg_mb_handle s, const mb_real* dt_B, const fg_mb_
     MB_DISPATCH(s, {
         // ---- predictor (SIM.py:1646-1762, non-orthogonal branch)
         hipLaunchKernelGGL(k_mb_contra<DIMS>, gc, blk, 0, st, D, dt_B, s->velocity, s->bvel, s->cc, s->fb);
-        hipLaunchKernelGGL(k_mb_matrix<DIMS>, gn, blk, 0, st, D, dt_B, s->nu, s->cc, s->fb, s->Cdiag, s->Coff, s->rA);
+        hipLaunchKernelGGL(k_mb_matrix<DIMS>, gn, blk, 0, st, D, dt_B, nu, s->cc, s->fb, s->Cdiag, s->Coff, s->rA);
         hipLaunchKernelGGL(k_mb_copy, gcopy, blk, 0, st, vel_env, dt_B, s->velocity, s->ures);  // CopyVelocityResultFromBlocks
         for (int no = 0; no < opt->advect_non_ortho_steps; ++no) {
             FgRange range_vel("mb_velocity_solve");
-            hipLaunchKernelGGL(k_mb_vrhs<DIMS>, gv, blk, 0, st, D, dt_B, s->nu, s->velocity, s->ures, s->bvel, s->fb, s->source, s->rhs);
+            hipLaunchKernelGGL(k_mb_vrhs<DIMS>, gv, blk, 0, st, D, dt_B, nu, s->velocity, s->ures, s->bvel, s->fb, s->source, s->rhs);
             int m = 0;
             // initial guess: zero on the first non-orthogonal pass, the previous pass's result after that (x = None if no_step == 0
             // or not advect_non_ortho_reuse_result, PISOtorch_simulation.py:1735-1742; tests/golden/reference_split_step.json);
@@ -864,7 +894,7 @@ extern "C" int fg_mb_piso_step(fg_mb_handle s, const mb_real* dt_B, const fg_mb_
             for (int ps = 0; ps < opt->pressure_non_ortho_steps; ++ps) {
                 FgRange range_p("mb_pressure_solve");
                 if (ps == 0) {
-                    hipLaunchKernelGGL(k_mb_h<DIMS>, gv, blk, 0, st, D, dt_B, s->nu, s->rA, s->Coff, s->velocity, s->ures,
+                    hipLaunchKernelGGL(k_mb_h<DIMS>, gv, blk, 0, st, D, dt_B, nu, s->rA, s->Coff, s->velocity, s->ures,
                                        s->bvel, s->fb, s->source, s->hvec);
                     hipLaunchKernelGGL(k_mb_contra<DIMS>, gc, blk, 0, st, D, dt_B, s->hvec, s->bvel, s->cc, (mb_real*)nullptr);
                 }

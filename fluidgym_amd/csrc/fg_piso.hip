@@ -53,7 +53,7 @@ __global__ __launch_bounds__(FG_BLOCK) void k_adv_build(FgGrid g, FgBounds bnd, 
     const size_t N = g.n;
     const fg_real* __restrict__ vel = a.vel + (size_t)c.b * DIMS * N;
     const FgMetric<DIMS, VEC> m = fg_metrics<DIMS, VEC>(g, c);
-    const fg_real nu = a.nu;
+    const fg_real nu = a.nu.at(c.b);
     const fg_real rdt = 1.f / dt;
 
     fg_real J[VEC], diag[VEC], off[2 * DIMS][VEC];

@@ -32,7 +32,7 @@ from .airfoil_grid import BOTTOM, FRONT, TAIL_LOWER, TAIL_UPPER, TOP, make_airfo
 from .channel import jet_profile
 from .cylinder import CylinderEnvBase
 from .cylinder_grid import build_domain, extrude_mesh
-from .fluid_env import FluidEnv
+from .fluid_env import FluidEnv, refuse_per_env
 from .forces import WallRing
 
 AIRFOIL_2D_DEFAULT_CONFIG = {
@@ -90,6 +90,7 @@ class AirfoilEnvBase(CylinderEnvBase):
         if ndims not in (2, 3):
             raise ValueError("ndims must be 2 or 3")
         self._ndims = ndims
+        refuse_per_env("reynolds_number", reynolds_number, "the airfoil env", "its mesh grading depends on the Reynolds number")
         self._reynolds_number = reynolds_number
         self._nu = self.U_mean * self.airfoil_length / reynolds_number
         self._attack_angle_deg = float(attack_angle_deg)

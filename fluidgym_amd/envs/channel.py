@@ -31,7 +31,7 @@ from .. import spaces
 from ..simulation import grids
 from ..simulation.domain import Domain
 from ..simulation.simulation import Simulation, update_advective_boundaries
-from .fluid_env import FluidEnv
+from .fluid_env import FluidEnv, is_per_env, per_env_parameter
 
 CHANNEL_JET_2D_DEFAULT_CONFIG = {
     "reynolds_number": 1e2,
@@ -79,6 +79,8 @@ class ChannelJetEnv2D(FluidEnv):
 
     def __init__(self, reynolds_number: float, resolution_x: int, resolution_y: int, dt: float, adaptive_cfl: float,
                  step_length: float, episode_length: int, lift_penalty: float = 1.0, **kw):
+        reynolds_number = per_env_parameter("reynolds_number", reynolds_number, kw.get("num_envs"))      # a number, or one per env
+        self._heterogeneous = is_per_env(reynolds_number)
         self._reynolds_number = reynolds_number
         self._x, self._y = int(resolution_x), int(resolution_y)
         self._lift_penalty = lift_penalty
@@ -104,7 +106,7 @@ class ChannelJetEnv2D(FluidEnv):
     def _get_domain(self) -> Domain:
         edges = [np.linspace(0.0, self.L, self._x + 1), np.linspace(-self.H / 2, self.H / 2, self._y + 1)]
         coords = grids.vertex_grid(edges)
-        dom = Domain(2, torch.tensor([self._nu]), passiveScalarChannels=0, name="ChannelDomain",
+        dom = Domain(2, torch.as_tensor(self._nu, dtype=torch.float64) if self._heterogeneous else torch.tensor([self._nu]), passiveScalarChannels=0, name="ChannelDomain",
                      device=self._cuda_device, dtype=self._dtype, batch=self._num_envs)
         blk = dom.CreateBlock(vertexCoordinates=coords, name="ChannelBlock")
         blk.CloseBoundary("-x")
@@ -135,6 +137,9 @@ class ChannelJetEnv2D(FluidEnv):
         self._native_glue = (dev.type == "cuda" and self._dtype == torch.float32 and self._x % 4 == 0
                              and os.environ.get("FLUIDGYM_AMD_ENV_GLUE", "1") != "0")
         self._decay = None
+        # nu / (hy / 2): the wall-shear coefficient, a float or env b's own value [B] on the device
+        self._shear_coef = (torch.as_tensor(self._nu / (0.5 * self._hy), dtype=torch.float32, device=dev).contiguous()
+                            if self._heterogeneous else float(self._nu / (0.5 * self._hy)))
 
     def _get_simulation(self, domain: Domain, prep_fn: Dict[str, Any]) -> Simulation:
         return Simulation(
@@ -189,7 +194,10 @@ class ChannelJetEnv2D(FluidEnv):
     def _metrics_now(self):
         u = self._block.velocity
         cross = (u[:, 1] ** 2).mean(dim=(1, 2))
-        shear = self._nu * (u[:, 0, 0, :].mean(dim=1) + u[:, 0, -1, :].mean(dim=1)) / (0.5 * self._hy)
+        if self._heterogeneous:
+            shear = self._shear_coef.to(u.dtype) * (u[:, 0, 0, :].mean(dim=1) + u[:, 0, -1, :].mean(dim=1))
+        else:
+            shear = self._nu * (u[:, 0, 0, :].mean(dim=1) + u[:, 0, -1, :].mean(dim=1)) / (0.5 * self._hy)
         return cross, shear
 
     def _step_native(self, action: torch.Tensor):
@@ -216,9 +224,14 @@ class ChannelJetEnv2D(FluidEnv):
         u, p = self._block.velocity, self._block.pressure
         obs_u, obs_p = torch.empty(B, S, 2, device=dev), torch.empty(B, S, device=dev)
         out = torch.empty(3, B, device=dev)
-        L.check(lib.fg_envglue_channel_observe(u.data_ptr(), p.data_ptr(), self._sensor_idx.data_ptr(), S, B, self._y, X,
-                                               float(self._nu / (0.5 * self._hy)), float(self._lift_penalty), obs_u.data_ptr(),
-                                               obs_p.data_ptr(), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), stream))
+        if self._heterogeneous:
+            L.check(lib.fg_envglue_channel_observe_batch(u.data_ptr(), p.data_ptr(), self._sensor_idx.data_ptr(), S, B, self._y, X,
+                                                         self._shear_coef.data_ptr(), float(self._lift_penalty), obs_u.data_ptr(),
+                                                         obs_p.data_ptr(), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), stream))
+        else:
+            L.check(lib.fg_envglue_channel_observe(u.data_ptr(), p.data_ptr(), self._sensor_idx.data_ptr(), S, B, self._y, X,
+                                                   float(self._nu / (0.5 * self._hy)), float(self._lift_penalty), obs_u.data_ptr(),
+                                                   obs_p.data_ptr(), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), stream))
         return {"velocity": obs_u, "pressure": obs_p}, out[2], False, {"cross_flow_energy": out[0], "wall_shear": out[1]}
 
     def _step_impl(self, action: torch.Tensor):
@@ -256,4 +269,5 @@ class ChannelJetEnv2D(FluidEnv):
 
     @property
     def id(self) -> str:
+        self._refuse_heterogeneous_id()
         return f"ChannelJet2D_Re{self._reynolds_number}_{self._x}x{self._y}"

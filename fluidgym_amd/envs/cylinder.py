@@ -26,7 +26,7 @@ from ..simulation.resample_mb import MultiBlockResampler, MultiBlockResampler3D
 from .. import spaces
 from .channel import jet_profile
 from .cylinder_grid import BOTTOM, LEFT, RIGHT, TOP, build_domain, extrude_mesh, make_vortex_street_mesh
-from .fluid_env import FluidEnv
+from .fluid_env import FluidEnv, is_per_env, per_env_parameter, refuse_per_env
 from .forces import WallRing
 
 CYLINDER_JET_2D_DEFAULT_CONFIG = {
@@ -61,6 +61,10 @@ class CylinderEnvBase(FluidEnv):
                  non_ortho_mode: str = "matrix", **kw):
         if ndims not in (2, 3):
             raise ValueError("ndims must be 2 or 3")
+        if ndims == 3:
+            refuse_per_env("reynolds_number", reynolds_number, "the 3-D cylinder env", "per-env parameters are built for the 2-D cylinder envs")
+        reynolds_number = per_env_parameter("reynolds_number", reynolds_number, kw.get("num_envs"))      # a number, or one per env
+        self._heterogeneous = is_per_env(reynolds_number)
         self._reynolds_number = reynolds_number
         self._circle_resolution_angular = int(resolution)
         self._lift_penalty = lift_penalty
@@ -96,10 +100,12 @@ class CylinderEnvBase(FluidEnv):
 
     @property
     def id(self) -> str:
+        self._refuse_heterogeneous_id()
         return f"{type(self).__name__}_Re{self._reynolds_number}"
 
     @property
     def initial_domain_id(self) -> str:
+        self._refuse_heterogeneous_id()
         return f"cylinder_{self._ndims}D_Re{int(self._reynolds_number)}_Res{self._circle_resolution_angular}"
 
     # ---- sensors (cylinder_env_base.py:430-518)
@@ -171,6 +177,9 @@ class CylinderEnvBase(FluidEnv):
                 self._multilevel = dom.set_pressure_multilevel(fp64=True)
             else:
                 self._multilevel = dom.set_pressure_multilevel()
+        # the viscosity the wall-force launch takes: a float, or env b's own value [B] on the device
+        self._nu_forces = (torch.as_tensor(self._nu, dtype=self._dtype, device=dom.device).contiguous() if self._heterogeneous
+                           else self._nu)
         self._initial_boundary = dom.boundary_velocity.clone()  # inflow / outflow profile, walls at rest
         self._last_control = torch.zeros(self._num_envs, self._n_controls, device=dom.device, dtype=self._dtype)
 
@@ -220,7 +229,7 @@ class CylinderEnvBase(FluidEnv):
 
     def _get_drag_and_lift(self):
         """[B] in 2-D; [B, NZ] per spanwise layer in 3-D (face area = edge length x D / resolution, :676-689)."""
-        f = self._ring.forces(self._domain, self._nu, layer_height=self.D / self._circle_resolution_angular)
+        f = self._ring.forces(self._domain, self._nu_forces, layer_height=self.D / self._circle_resolution_angular)
         norm = 0.5 * self._U_mean ** 2 * self.cylinder_diameter
         return f[:, 0] / norm, f[:, 1] / norm
 
@@ -251,7 +260,7 @@ class CylinderEnvBase(FluidEnv):
             if self._enable_actions:
                 self._apply_action(controls[k])
             self._sim.single_step()
-            self._ring.forces(self._domain, self._nu, layer_height=self.D / self._circle_resolution_angular, out=raw[k])
+            self._ring.forces(self._domain, self._nu_forces, layer_height=self.D / self._circle_resolution_angular, out=raw[k])
         self._last_control_mirror = (self._last_control, c_last)
         obs = self._get_global_obs()
         coeff = raw / (0.5 * self._U_mean ** 2 * self.cylinder_diameter)

@@ -190,9 +190,10 @@ def extrude_mesh(mesh: CylinderMesh, res_z: int, z0: float = -2.0, z1: float = 2
     return out
 
 
-def build_domain(mesh: CylinderMesh, viscosity: float, batch: int = 1, device=None, reference_quirks: bool = True,
+def build_domain(mesh: CylinderMesh, viscosity, batch: int = 1, device=None, reference_quirks: bool = True,
                  non_ortho_flags: int = 25, dtype=None):
-    """The mesh as a ``MultiBlockDomain`` on the GPU (``make_vortex_street_domain`` + ``PrepareSolve``); ``dtype``: torch.float32
+    """The mesh as a ``MultiBlockDomain`` on the GPU (``make_vortex_street_domain`` + ``PrepareSolve``); ``viscosity``: a float or one value
+    per env (``[batch]`` tensor or sequence); ``dtype``: torch.float32
     (default) or torch.float64 (the fp64 build)."""
     import torch
 

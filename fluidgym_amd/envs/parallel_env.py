@@ -220,6 +220,9 @@ class ParallelFluidEnv:
                  force_collectives: Optional[bool] = None, lanes: Optional[int] = None, **env_kwargs: Any):
         if env_kwargs.get("differentiable", False):
             raise ValueError("ParallelFluidEnv does not support differentiable environments.")
+        from .fluid_env import refuse_per_env
+        for key in ("reynolds_number", "rayleigh_number", "prandtl_number", "reynolds_number_wall"):
+            refuse_per_env(key, env_kwargs.get(key), "ParallelFluidEnv", "the batch is split over ranks: build one FluidEnv per parameter set")
         self._env_id = env_id
         self._workers = []
         self._owns_group = False

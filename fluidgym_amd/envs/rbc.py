@@ -35,7 +35,7 @@ from ..simulation.domain import Domain
 from ..simulation.resample import UniformResampler
 from ..simulation.simulation import Simulation
 from . import obs_extraction as X
-from .fluid_env import FluidEnv
+from .fluid_env import FluidEnv, is_per_env, per_env_parameter
 
 RBC_2D_DEFAULT_CONFIG = {
     "rayleigh_number": 8e4,
@@ -72,6 +72,15 @@ RBC_3D_DEFAULT_CONFIG = {          # rbc_env_3d.py's default config (held by tes
 }
 
 
+def _nusselt_factor(rayleigh_number, prandtl_number, like: torch.Tensor):
+    """``sqrt(Ra Pr)``: a float, or -- with one Ra / Pr per env -- env b's own value shaped to broadcast against ``like [B, ...]``."""
+    f = np.sqrt(rayleigh_number * prandtl_number)
+    if np.ndim(f) == 0:
+        return float(f)
+    t = torch.as_tensor(np.ascontiguousarray(f), dtype=like.dtype, device=like.device)
+    return t.reshape((t.numel(),) + (1,) * (like.dim() - 1))
+
+
 class RBCEnvBase(FluidEnv):
     _supports_marl = True
     _resolution_scale_y: float = 2.0
@@ -89,6 +98,11 @@ class RBCEnvBase(FluidEnv):
     def __init__(self, rayleigh_number, prandtl_number, n_heaters, resolution, dt, adaptive_cfl, step_length,
                  episode_length, ndims, local_obs_window=11, local_reward_weight=None, uniform_grid=False,
                  aspect_ratio=1.0, **kw):
+        # a number (as ever) or one value per env of the batch: Ra / Pr then become float64 arrays [num_envs] and everything
+        # derived from them below is per env
+        rayleigh_number = per_env_parameter("rayleigh_number", rayleigh_number, kw.get("num_envs"))
+        prandtl_number = per_env_parameter("prandtl_number", prandtl_number, kw.get("num_envs"))
+        self._heterogeneous = is_per_env(rayleigh_number) or is_per_env(prandtl_number)
         self._rayleigh_number = rayleigh_number
         self._prandtl_number = prandtl_number
         self._local_obs_window = int(local_obs_window)
@@ -100,8 +114,13 @@ class RBCEnvBase(FluidEnv):
         self._x = int(resolution * n_heaters)
         self._y = round(self._resolution_scale_y * self._x / self._aspect_ratio)
         self._L = self._H * self._aspect_ratio
-        self._nu = float((prandtl_number / rayleigh_number) ** 0.5)
-        self._kappa = float((rayleigh_number * prandtl_number) ** -0.5)
+        if self._heterogeneous:
+            n_envs = int(kw.get("num_envs") or 1)
+            self._nu = np.broadcast_to((prandtl_number / rayleigh_number) ** 0.5, (n_envs,)).copy()
+            self._kappa = np.broadcast_to((rayleigh_number * prandtl_number) ** -0.5, (n_envs,)).copy()
+        else:
+            self._nu = float((prandtl_number / rayleigh_number) ** 0.5)
+            self._kappa = float((rayleigh_number * prandtl_number) ** -0.5)
         super().__init__(dt=dt, adaptive_cfl=adaptive_cfl, step_length=step_length, episode_length=episode_length,
                          ndims=ndims, **kw)
 
@@ -145,9 +164,10 @@ class RBCEnvBase(FluidEnv):
 
     def _get_domain(self) -> Domain:
         coords = grids.vertex_grid(self._edges())
-        dom = Domain(self._ndims, torch.tensor([self._nu]), passiveScalarChannels=1, name="RBCDomain",
+        as_t = lambda v: torch.as_tensor(v, dtype=torch.float64) if self._heterogeneous else torch.tensor([v])
+        dom = Domain(self._ndims, as_t(self._nu), passiveScalarChannels=1, name="RBCDomain",
                      device=self._cuda_device, dtype=self._dtype, batch=self._num_envs)
-        dom.setScalarViscosity(torch.tensor([self._kappa]))
+        dom.setScalarViscosity(as_t(self._kappa).reshape(-1, 1) if self._heterogeneous else as_t(self._kappa))
         blk = dom.CreateBlock(vertexCoordinates=coords, name="RBCBlock")
         blk.CloseBoundary("-y")
         blk.CloseBoundary("+y")
@@ -315,7 +335,7 @@ class RBCEnvBase(FluidEnv):
         uy = self._block.velocity[:, 1]
         dims = tuple(range(1, self._ndims + 1))
         mean = (uy * T * self._cell_size).sum(dim=dims) / self._cell_size.sum()
-        return 1.0 + float(np.sqrt(self._rayleigh_number * self._prandtl_number)) * mean
+        return 1.0 + _nusselt_factor(self._rayleigh_number, self._prandtl_number, mean) * mean
 
     @property
     def nu_ref(self) -> float:
@@ -325,7 +345,7 @@ class RBCEnvBase(FluidEnv):
         """``_compute_nusselt`` on per-agent windows (rbc_env_base.py:491-513): ``T, u_y [B, n_agents, *win]``."""
         dims = tuple(range(2, T.dim()))
         mean = (u_y * T * cell_size).sum(dim=dims) / cell_size.sum()
-        return 1.0 + float(np.sqrt(self._rayleigh_number * self._prandtl_number)) * mean
+        return 1.0 + _nusselt_factor(self._rayleigh_number, self._prandtl_number, mean) * mean
 
     def _get_local_obs(self):
         """rbc_env_2d.py:280-325 / rbc_env_3d.py:330-385 with a leading env axis: ``[B, n_agents, ...]``."""
@@ -376,12 +396,14 @@ class RBCEnvBase(FluidEnv):
 
     @property
     def id(self) -> str:
+        self._refuse_heterogeneous_id()
         return (f"RBC{self._ndims}d_Ra{self._rayleigh_number}_Pr{self._prandtl_number}"
                 f"_NH{self._n_heaters}_HW{self._heater_width}")
 
     @property
     def initial_domain_id(self) -> str:
         """rbc_env_base.py:605-611."""
+        self._refuse_heterogeneous_id()
         return (f"rbc_{self._ndims}d_Ra{self._rayleigh_number}_Pr{self._prandtl_number}"
                 f"_NH{self._n_heaters}_HW{self._heater_width}")
 

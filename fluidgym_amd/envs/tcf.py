@@ -37,7 +37,7 @@ from ..simulation import grids
 from ..simulation.domain import Domain
 from ..simulation.simulation import Simulation
 from . import obs_extraction as X
-from .fluid_env import FluidEnv
+from .fluid_env import FluidEnv, refuse_per_env
 
 SMALL_TCF_3D_DEFAULT_CONFIG = {
     "resolution_y": 65,
@@ -87,6 +87,7 @@ class TCF3DBottomEnv(FluidEnv):
         # Smagorinsky sub-grid viscosity (tcf_env.py:441-474): off in every registered id (C_smag = 0); built since round 3
         self._C_smag, self._use_van_driest = float(C_smag), bool(use_van_driest)
         self._L, self._D = float(L), float(D)
+        refuse_per_env("reynolds_number_wall", reynolds_number_wall, "the turbulent-channel env", "its grid and forcing depend on Re_tau")
         self._re_wall = float(reynolds_number_wall)
         self._re_center = (self._re_wall / 0.116) ** (1 / 0.88)   # TCF_tools.Re_wall_to_cl
         self._nu = self._delta / self._re_center

@@ -63,6 +63,8 @@ class NativeSolver:
         self.n_scalars = int(n_scalars)
         self.scalar_bc = {int(f): [int(t) for t in v] for f, v in (scalar_bc or {}).items()}
         self.scalar_viscosities: Dict[int, float] = {}
+        self.viscosity_B: Optional[torch.Tensor] = None                      # per-env arrays the library borrows (set_viscosity)
+        self.scalar_viscosities_B: Dict[int, Optional[torch.Tensor]] = {}
         self.fixed = [f in fixed_faces for f in range(6)]
         cfg = L.FgConfig()
         cfg.dims, cfg.nx, cfg.ny, cfg.nz = self.dims, self.nx, self.ny, self.nz
@@ -194,13 +196,39 @@ class NativeSolver:
         self.bscal[face] = t
         self.bind(L.FG_BOUND_SCALAR + face, t)
 
-    def set_viscosity(self, nu: float):
-        self.viscosity = float(nu)
-        L.check(self.lib.fg_set_viscosity(self.handle, float(nu)), lib=self.lib)
+    def _per_env(self, v, what: str) -> Optional[torch.Tensor]:
+        """None for one value (a float, a one-element tensor or sequence); the device tensor ``[B]`` for one value per env."""
+        if isinstance(v, (int, float)):
+            return None
+        t = (v.detach() if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v, dtype=np.float64))).reshape(-1)
+        if t.numel() == 1:
+            return None
+        if t.numel() != self.B:
+            raise ValueError(f"{what}: expected one value or one per env ({self.B}), got {t.numel()}")
+        return t.to(device=self.device, dtype=self.dtype).contiguous()
 
-    def set_scalar_viscosity(self, ch: int, k: float):
-        self.scalar_viscosities[int(ch)] = float(k)
-        L.check(self.lib.fg_set_scalar_viscosity(self.handle, ch, float(k)), lib=self.lib)
+    def set_viscosity(self, nu):
+        """One viscosity for the batch (a float, as ever) or one per env (``[B]`` tensor or sequence: ``fg_set_viscosity_batch``).
+        The device tensor is kept in ``viscosity_B`` and read by the kernels at launch: writing into it changes the next step.
+        With an array installed ``viscosity`` is None (no single value describes the batch)."""
+        per_env = self._per_env(nu, "set_viscosity")
+        if per_env is None:
+            self.viscosity = float(torch.as_tensor(nu).reshape(-1)[0]) if not isinstance(nu, (int, float)) else float(nu)
+            L.check(self.lib.fg_set_viscosity(self.handle, self.viscosity), lib=self.lib)
+        else:
+            self.viscosity = None
+        self.viscosity_B = per_env      # (kept alive: the library borrows the pointer)
+        L.check(self.lib.fg_set_viscosity_batch(self.handle, _ptr(per_env)), lib=self.lib)
+
+    def set_scalar_viscosity(self, ch: int, k):
+        """Diffusivity of scalar channel ``ch``: a float or one per env (``[B]``, ``fg_set_scalar_viscosity_batch``)."""
+        per_env = self._per_env(k, "set_scalar_viscosity")
+        if per_env is None:
+            kf = float(torch.as_tensor(k).reshape(-1)[0]) if not isinstance(k, (int, float)) else float(k)
+            self.scalar_viscosities[int(ch)] = kf
+            L.check(self.lib.fg_set_scalar_viscosity(self.handle, ch, kf), lib=self.lib)
+        self.scalar_viscosities_B[int(ch)] = per_env
+        L.check(self.lib.fg_set_scalar_viscosity_batch(self.handle, ch, _ptr(per_env)), lib=self.lib)
 
     # ------------------------------------------------------------------ helpers
     def dt_tensor(self, dt) -> torch.Tensor:

@@ -266,6 +266,19 @@ class Block:
         return self.transform[..., 2 * d * d].unsqueeze(1)
 
 
+def per_env_values(v, batch: int, what: str):
+    """``v`` as the domain keeps it: a float for one value (a number, a one-element tensor or sequence -- what it always meant), a
+    float64 tensor ``[batch]`` for one value per env.  Any other length is a ``ValueError`` naming ``what``."""
+    if isinstance(v, (int, float)):
+        return float(v)
+    t = (v.detach() if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v, dtype=np.float64))).reshape(-1).to("cpu", torch.float64)
+    if t.numel() == 1:
+        return float(t[0])
+    if t.numel() != batch:
+        raise ValueError(f"{what}: expected one value or one per env ({batch}), got {t.numel()}")
+    return t.clone()
+
+
 class Domain:
     """Batched stand-in for ``PISOtorch.Domain`` (one block, rectilinear grid)."""
 
@@ -284,8 +297,8 @@ class Domain:
             self.device = torch.device("cuda", torch.cuda.current_device() if torch.cuda.is_available() else 0)
         self.batch = int(batch)
         self.n_scalars = int(passiveScalarChannels)
-        self._viscosity = float(torch.as_tensor(viscosity).reshape(-1)[0])
-        self._scalar_viscosity: Optional[List[float]] = None
+        self._viscosity = per_env_values(viscosity, self.batch, "viscosity")      # float, or [B] for one value per env
+        self._scalar_viscosity: Optional[list] = None
         self.blocks: List[Block] = []
         self.solver: Optional[NativeSolver] = None
         self._rh = None
@@ -300,18 +313,37 @@ class Domain:
         return b
 
     def setScalarViscosity(self, v):
-        vals = [float(x) for x in torch.as_tensor(v).reshape(-1)]
+        """One value per channel (``[C]``, or one element for all channels: the reference's form, read as ever), or one value per
+        env and channel as an explicit 2-D ``[B, C]``."""
+        tv = torch.as_tensor(v)
+        if tv.dim() == 2:
+            if tv.shape[1] != self.n_scalars:
+                raise ValueError(f"scalar viscosity: [B, C] needs C = {self.n_scalars} channels, got {tv.shape[1]}")
+            if tv.shape[0] != self.batch:
+                raise ValueError(f"scalar viscosity: expected one value per env ({self.batch}), got {tv.shape[0]}")
+            vals = [per_env_values(tv[:, ch], self.batch, "scalar viscosity") for ch in range(self.n_scalars)]
+        else:
+            flat = [float(x) for x in tv.reshape(-1)]
+            vals = [flat[0] if len(flat) == 1 else flat[ch] for ch in range(self.n_scalars)]
         self._scalar_viscosity = vals
         if self.solver is not None:
             for ch in range(self.n_scalars):
-                self.solver.set_scalar_viscosity(ch, vals[0] if len(vals) == 1 else vals[ch])
+                self.solver.set_scalar_viscosity(ch, vals[ch])
+
+    @property
+    def heterogeneous(self) -> bool:
+        """True when the viscosity or a scalar diffusivity differs per env."""
+        return isinstance(self._viscosity, torch.Tensor) or any(isinstance(k, torch.Tensor) for k in (self._scalar_viscosity or []))
 
     @property
     def viscosity(self) -> torch.Tensor:
+        """``[1]`` (the reference's shape), or ``[B]`` when every env has its own."""
+        if isinstance(self._viscosity, torch.Tensor):
+            return self._viscosity.to(self.dtype)
         return torch.tensor([self._viscosity], dtype=self.dtype)
 
     def setViscosity(self, v):
-        self._viscosity = float(torch.as_tensor(v).reshape(-1)[0])
+        self._viscosity = per_env_values(v, self.batch, "viscosity")
         if self.solver is not None:
             self.solver.set_viscosity(self._viscosity)
 
@@ -326,7 +358,8 @@ class Domain:
                                    scalar_bc=scalar_bc, device=self.device, dtype=self.dtype)
         self.solver.set_viscosity(self._viscosity)
         if self._scalar_viscosity is not None:
-            self.setScalarViscosity(self._scalar_viscosity)
+            for ch in range(self.n_scalars):
+                self.solver.set_scalar_viscosity(ch, self._scalar_viscosity[ch])
         for name, t in blk._pending.items():
             if name == "velocity_source":
                 blk.setVelocitySource(t)

@@ -48,6 +48,9 @@ def save_domain(domain: Domain, path: str, env: int = 0) -> None:
     """``save_domain`` (domain_io.py:64-185) for env ``env`` of a prepared single-block domain; ``path`` without
     extension."""
     assert domain.IsInitialized(), "PrepareSolve() first: the field tensors live in the solver"
+    if getattr(domain, "heterogeneous", False):
+        raise ValueError("save_domain: this domain has one viscosity / scalar diffusivity per env; the reference's file format holds "
+                         "one value per domain -- save from a domain with a single value (setViscosity(float)) instead")
     data = []
 
     def add(t: torch.Tensor, d: dict, name: str):
@@ -175,6 +178,9 @@ def save_multiblock_domain(domain, path: str, env: int = 0, name: str = "Domain"
         data.append(torch.as_tensor(t).detach().cpu().contiguous().to(real))
 
     dims = domain.dims
+    if getattr(domain, "viscosity_B", None) is not None:
+        raise ValueError("save_multiblock_domain: this domain has one viscosity per env; the reference's file format holds one value "
+                         "per domain")
     dd = {"name": name, "spatialDims": dims}
     add(torch.tensor([domain.viscosity]), dd, "viscosity")
     dd["passiveScalarChannels"] = 0

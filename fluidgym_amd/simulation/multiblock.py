@@ -180,14 +180,17 @@ def multilevel_tables(P, blocks, max_n4: int = 2048, max_n8: int = 512):
 class MultiBlockDomain:
     """``PISOtorch.Domain`` for connected curvilinear blocks, batched over envs."""
 
-    def __init__(self, dims: int, viscosity: float, batch: int = 1, device: Optional[torch.device] = None,
+    def __init__(self, dims: int, viscosity, batch: int = 1, device: Optional[torch.device] = None,
                  reference_quirks: bool = True, non_ortho_flags: int = 25, dtype: torch.dtype = torch.float32):
         if not torch.cuda.is_available():
             raise L.NativeLibraryError("fluidgym_amd needs a GPU: the multi-block path has no CPU fallback")
         self._set_dtype(dtype)
         self.dims, self.batch = int(dims), int(batch)
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        self.viscosity = float(viscosity)
+        # one viscosity (a float, as ever) or one per env ([B] tensor or sequence): `viscosity` stays a float -- the value of a
+        # homogeneous domain -- and `viscosity_B` holds the device tensor the library borrows (None: homogeneous)
+        self.viscosity, self._viscosity_host = self._split_viscosity(viscosity)
+        self.viscosity_B: Optional[torch.Tensor] = None
         self.handle = ctypes.c_void_p()
         L.check(self.lib.fg_mb_create(self.dims, self.batch, self.device.index or 0, ctypes.byref(self.handle)))
         if not reference_quirks:
@@ -201,6 +204,34 @@ class MultiBlockDomain:
         self.n_cells = self.n_boundary_faces = 0
         self._dt = None
         self.multilevel = None   # aggregate counts once set_pressure_multilevel has installed the preconditioner
+
+    def _split_viscosity(self, v):
+        if isinstance(v, (int, float)):
+            return float(v), None
+        t = (v.detach() if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v, dtype=np.float64))).reshape(-1).to("cpu", torch.float64)
+        if t.numel() == 1:
+            return float(t[0]), None
+        if t.numel() != self.batch:
+            raise ValueError(f"viscosity: expected one value or one per env ({self.batch}), got {t.numel()}")
+        if not bool((t > 0).all()):
+            raise ValueError("viscosity: every entry must be positive")
+        return float(t[0]), t
+
+    def set_viscosity(self, v) -> None:
+        """A float for the whole batch or ``[B]`` for one value per env (``fg_mb_set_viscosity_batch``: the device tensor is kept in
+        ``viscosity_B`` and read at launch -- writing into it changes the next step)."""
+        self.viscosity, self._viscosity_host = self._split_viscosity(v)
+        if self.prepared:
+            self._install_viscosity()
+
+    def _install_viscosity(self) -> None:
+        L.check(self.lib.fg_mb_set_viscosity(self.handle, self.viscosity))
+        # (getattr: tests/stub_mb.py replaces __init__ by one that knows the scalar only)
+        host = getattr(self, "_viscosity_host", None)
+        per_env = None if host is None else host.to(device=self.device, dtype=self.dtype).contiguous()
+        if per_env is not None or getattr(self, "viscosity_B", None) is not None:
+            L.check(self.lib.fg_mb_set_viscosity_batch(self.handle, None if per_env is None else ctypes.c_void_p(per_env.data_ptr())))
+        self.viscosity_B = per_env
 
     def _set_dtype(self, dtype: torch.dtype) -> None:
         """float32: ``libfluidgym_hip.so``; float64: the fp64 build (``libfluidgym_hip_f64.so``), in which every float of the
@@ -256,7 +287,7 @@ class MultiBlockDomain:
                 view = blk.boundary(f)
                 t = torch.as_tensor(v, **kw).reshape(d, -1)
                 view.copy_(t.expand(d, view.shape[-1]) if t.shape[-1] == 1 else t)
-        L.check(self.lib.fg_mb_set_viscosity(self.handle, self.viscosity))
+        self._install_viscosity()
         self._bind()
         self.prepared = True
 
@@ -493,8 +524,9 @@ class MultiBlockDomain:
         return self.multilevel
 
     def wall_forces(self, cell_index: torch.Tensor, slot_index: torch.Tensor, geom: torch.Tensor, area_scale: float,
-                    viscosity: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """``[B, 2, layers]`` force on a closed wall from the current fields (``fg_mb_wall_forces``): ``cell_index`` /
+                    viscosity, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``[B, 2, layers]`` force on a closed wall from the current fields (``fg_mb_wall_forces``; with a ``[B]`` tensor as
+        ``viscosity``, env b's own value: ``fg_mb_wall_forces_batch``): ``cell_index`` /
         ``slot_index`` int32 ``[layers, n]`` in ring order, ``geom`` float32 ``[5, n]`` (normal x, y, tangential spacing, wall
         distance, face length).  Asynchronous on the current stream."""
         layers, n = cell_index.shape
@@ -504,6 +536,14 @@ class MultiBlockDomain:
             raise ValueError("wall_forces: out must be a contiguous [B, 2, layers] tensor of the domain's dtype on its device")
         geom = geom if geom.dtype == self.dtype else geom.to(self.dtype)
         st = torch.cuda.current_stream(self.device).cuda_stream
+        if isinstance(viscosity, torch.Tensor) and viscosity.numel() > 1:
+            if viscosity.numel() != self.batch:
+                raise ValueError(f"wall_forces: viscosity must be a float or one value per env ({self.batch})")
+            nu_B = viscosity.detach().reshape(-1).to(device=self.device, dtype=self.dtype).contiguous()
+            L.check(self.lib.fg_mb_wall_forces_batch(self.handle, ctypes.c_void_p(cell_index.data_ptr()), ctypes.c_void_p(slot_index.data_ptr()),
+                                                     ctypes.c_void_p(geom.data_ptr()), int(n), int(layers), float(area_scale), 0.0,
+                                                     ctypes.c_void_p(nu_B.data_ptr()), ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(st)))
+            return out
         L.check(self.lib.fg_mb_wall_forces(self.handle, ctypes.c_void_p(cell_index.data_ptr()), ctypes.c_void_p(slot_index.data_ptr()),
                                            ctypes.c_void_p(geom.data_ptr()), int(n), int(layers), float(area_scale), float(viscosity),
                                            ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(st)))

@@ -122,6 +122,15 @@ int fg_bind(fg_handle h, int field, fg_real* ptr);
 /* Domain.viscosity / Domain.setScalarViscosity (domain_structs.cpp:3070) */
 int fg_set_viscosity(fg_handle h, fg_real viscosity);
 int fg_set_scalar_viscosity(fg_handle h, int channel, fg_real viscosity);
+/* One viscosity / scalar diffusivity PER ENV of the batch (no reference counterpart: its Domain holds one value).  nu_B / k_B:
+ * caller-owned device array [batch], bound like dt_B -- every kernel that needs the value reads entry b at launch (one
+ * wave-uniform load per workgroup), so the values may be rewritten between steps without a call or a host round trip.  NULL
+ * returns to the scalar of fg_set_viscosity / fg_set_scalar_viscosity.  A scalar channel without an array of its own follows
+ * the rule of the scalars (its own value once any channel was set, else the velocity's -- array included).  With a per-cell
+ * FG_VISCOSITY_FIELD bound the field wins for the velocity system; the arrays still apply to the scalars.  The Helmholtz
+ * preconditioner (fg_set_fd_helmholtz) factorises with env b's own diffusivity. */
+int fg_set_viscosity_batch(fg_handle h, const fg_real* nu_B);
+int fg_set_scalar_viscosity_batch(fg_handle h, int channel, const fg_real* k_B);
 
 /* Fast-diagonalisation preconditioner factors for FG_SOLVER_FDCG (host arrays, copied to the device):
  * Qx [nx,nx] / QxT: H-orthonormal eigenbasis of the 1-D x operator and its transpose, Qz / QzT the same
@@ -470,6 +479,11 @@ int fg_envglue_jet_schedule(const float* target, const float* current, const flo
 int fg_envglue_channel_observe(const float* velocity, const float* pressure, const int64_t* sensor, int32_t n_sensors,
                                int32_t batch, int32_t ny, int32_t nx, float shear_scale, float penalty, float* obs_velocity,
                                float* obs_pressure, float* cross, float* shear, float* reward, void* stream);
+/* The same with env b's own shear scale: shear_scale_B = device array [batch] (per-env viscosities, fg_set_viscosity_batch). */
+int fg_envglue_channel_observe_batch(const float* velocity, const float* pressure, const int64_t* sensor, int32_t n_sensors,
+                                     int32_t batch, int32_t ny, int32_t nx, const float* shear_scale_B, float penalty,
+                                     float* obs_velocity, float* obs_pressure, float* cross, float* shear, float* reward,
+                                     void* stream);
 
 /* ---- multi-block, non-orthogonal domains -------------------------------------------
  * The reference's general Domain: several structured blocks of curvilinear cells (vertex coordinates ->
@@ -515,6 +529,9 @@ int fg_mb_get_neighbors(fg_mb_handle h, int32_t* out_host /* [2d*N]: neighbour c
 int fg_mb_get_host_table(fg_mb_handle h, int32_t which, void* out, int64_t* count);
 int fg_mb_bind(fg_mb_handle h, fg_real* velocity, fg_real* pressure_result, fg_real* boundary_velocity, const fg_real* source);
 int fg_mb_set_viscosity(fg_mb_handle h, fg_real nu);
+/* One viscosity per env: caller-owned device array [batch], read by the step's kernels at launch (the values may be rewritten
+ * between steps); NULL returns to the scalar.  Every entry must be > 0 (checked here on a host copy: FG_ERR_INVALID_ARG). */
+int fg_mb_set_viscosity_batch(fg_mb_handle h, const fg_real* nu_B);
 typedef struct fg_mb_step_options {
     int32_t corrector_steps;           /* 2 */
     int32_t advect_non_ortho_steps;    /* 1 (airfoil 2) */
@@ -678,6 +695,10 @@ int fg_mb_multilevel_status(fg_mb_handle h, int32_t* out3);
  * sum over the ring of ((2 nu S - p I) n) * face length * area_scale.  Asynchronous on `stream`. */
 int fg_mb_wall_forces(fg_mb_handle h, const int32_t* cell_index, const int32_t* slot_index, const fg_real* geom, int32_t n,
                       int32_t layers, fg_real area_scale, fg_real viscosity, fg_real* out, void* stream);
+/* The same with env b's own viscosity: viscosity_B = device array [batch] read at launch, or NULL for `viscosity` in every env. */
+int fg_mb_wall_forces_batch(fg_mb_handle h, const int32_t* cell_index, const int32_t* slot_index, const fg_real* geom, int32_t n,
+                            int32_t layers, fg_real area_scale, fg_real viscosity, const fg_real* viscosity_B, fg_real* out,
+                            void* stream);
 int fg_mb_unit_pressure_matrix(fg_mb_handle h, void* stream);
 /* live timing of the CG kernel pair (kind 0: stencil kernel k_mbc_ap, 1: update kernel k_mbc_update): every fourth chunk of
  * iterations has its first pair issued with start/stop events; sums over sampled launches with live systems, their
