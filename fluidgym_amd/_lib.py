@@ -19,6 +19,7 @@ LIB_PATH = os.environ.get("FLUIDGYM_AMD_LIB") or os.path.join(_HERE, "libfluidgy
 LIB_F64_PATH = os.environ.get("FLUIDGYM_AMD_LIB_F64") or os.path.join(_HERE, "libfluidgym_hip_f64.so")
 
 FG_MAX_SCALARS = 4
+FG_FIELD_SUMMARY_WORK_BYTES = 128      # per-env workspace of fg_field_summary (include/fluidgym_hip.h)
 FG_OK = 0
 FG_ERR_NOT_CONVERGED = -5
 FG_ERR_NOT_FINITE = -6
@@ -196,6 +197,8 @@ SIGNATURES = {
     "fg_mb_debug_bicgstab": (c_int, [c_void_p, c_float, c_int32, c_int32, POINTER(c_int64), POINTER(ctypes.c_double), POINTER(c_float), c_void_p]),
     "fg_dacc_host_sum": (c_int, [POINTER(ctypes.c_double), c_int64, ctypes.c_double, POINTER(ctypes.c_double)]),
     "fg_dacc_device_sum": (c_int, [POINTER(ctypes.c_double), c_int64, ctypes.c_double, c_int32, POINTER(ctypes.c_double), c_void_p]),
+    "fg_field_summary": (c_int, [c_void_p, c_int32, c_int32, c_int64, c_int32, c_void_p, c_void_p, c_void_p, ctypes.c_double, ctypes.c_double,
+                                 c_int32, c_void_p, c_void_p]),
     "fg_coherence_litmus": (c_int, [c_int32, c_int32, c_int32, c_int32, POINTER(c_int64), POINTER(ctypes.c_double), c_void_p]),
     "fg_profile_enable": (c_int, [c_void_p, c_int]),
     "fg_profile_kinds": (c_int, []),

@@ -96,7 +96,7 @@ class AirfoilEnvBase(CylinderEnvBase):
         self._attack_angle_deg = float(attack_angle_deg)
         self._resolution_div = int(resolution_div)
         self._surface = np.asarray(naca0012_sharp() if surface is None else surface, np.float64)
-        self._cl_cd_ref = float(lift_drag_reference)
+        self._lift_drag_reference = float(lift_drag_reference)
         self._pressure_use_bicg = pressure_use_BiCG
         self._pressure_deflation = bool(pressure_deflation)
         if non_ortho_mode not in ("matrix", "rhs"):
@@ -115,6 +115,15 @@ class AirfoilEnvBase(CylinderEnvBase):
         FluidEnv.__init__(self, dt=dt, adaptive_cfl=adaptive_cfl, step_length=step_length, episode_length=episode_length,
                           ndims=ndims, **kw)
         self._last_control = None
+
+    @property
+    def _cl_cd_ref(self) -> float:
+        """airfoil_env_base.py:166-172: mean lift over mean drag of the domain statistics; an explicit non-zero
+        ``lift_drag_reference`` wins, and without either it is 0."""
+        if self._lift_drag_reference != 0.0:
+            return self._lift_drag_reference
+        lift, drag = self._metric_stat("lift"), self._metric_stat("drag")
+        return 0.0 if lift is None or drag is None else float(lift.mean / drag.mean)
 
     # ---- geometry on the render grid (airfoil_env_base.py:175-214, 559-660)
     @property
@@ -426,6 +435,18 @@ class AirfoilEnv3D(AirfoilEnvBase):
     @property
     def _nz_per_agent(self) -> int:
         return self._res_z // self._n_agents
+
+    @property
+    def _cd_ref(self) -> float:
+        """airfoil_env_3d.py:289-301: mean drag / mean ``abs_lift`` of the domain statistics, 0 without them (the reward itself
+        uses ``_cl_cd_ref``, there as here)."""
+        s = self._metric_stat("drag")
+        return 0.0 if s is None else float(s.mean)
+
+    @property
+    def _cl_ref(self) -> float:
+        s = self._metric_stat("abs_lift")
+        return 0.0 if s is None else float(s.mean)
 
     # ---- sensors (airfoil_env_3d.py:303-344): the kept 2-D pixels on n_sensors_z spanwise planes
     def _get_sensor_locations(self) -> np.ndarray:

@@ -8,7 +8,8 @@ velocity / pressure sensors read from the uniformly resampled fields (:430-518),
 
 Not carried over: the published initial domains (HuggingFace ``fluidgym-data``; no network) -- ``reset`` starts from a
 projected uniform stream and runs ``initial_domain_steps`` developed-flow steps (the reference generates its initial
-domains with 400, :138) -- and the domain statistics (``_cd_ref`` is 0 unless ``drag_reference`` is given).
+domains with 400, :138).  ``_cd_ref`` is the mean drag of the domain statistics once ``compute_domain_statistics`` has written
+them, ``drag_reference`` when given, else 0.
 
 ``CylinderJetEnv3D`` (``jet_cylinder_env_3d.py``) runs the same mesh extruded over the span (z-periodic): ``n_jets``
 spanwise jet segments, 151 x ``n_jets * 2`` sensors read from the 3-D resampled fields, drag / lift per spanwise layer,
@@ -69,7 +70,7 @@ class CylinderEnvBase(FluidEnv):
         self._circle_resolution_angular = int(resolution)
         self._lift_penalty = lift_penalty
         self._nu = self._U_mean / reynolds_number
-        self._cd_ref = float(drag_reference)
+        self._drag_reference = float(drag_reference)
         self._pressure_use_bicg = pressure_use_BiCG
         self._pressure_deflation = pressure_deflation
         if non_ortho_mode not in ("matrix", "rhs"):
@@ -81,6 +82,15 @@ class CylinderEnvBase(FluidEnv):
                          ndims=ndims, **kw)
         self._last_control = None
         self._sensor_locations = self._get_sensor_locations()
+
+    @property
+    def _cd_ref(self) -> float:
+        """cylinder_env_base.py:270-275: the mean uncontrolled drag of the domain statistics; an explicit non-zero
+        ``drag_reference`` wins, and without either it is 0."""
+        if self._drag_reference != 0.0:
+            return self._drag_reference
+        s = self._metric_stat("drag")
+        return 0.0 if s is None else float(s.mean)
 
     # ---- spaces (cylinder_env_base.py:183-213)
     def _get_action_space(self):

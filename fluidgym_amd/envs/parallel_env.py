@@ -616,6 +616,12 @@ class ParallelFluidEnv:
     def get_uncontrolled_episode_metrics(self):
         raise NotImplementedError("get_uncontrolled_episode_metrics is not implemented for ParallelFluidEnv.")
 
+    def compute_domain_statistics(self, n_steps=None, seed=None, save: bool = True) -> dict:
+        raise NotImplementedError("compute_domain_statistics is not implemented for ParallelFluidEnv (run it on one FluidEnv).")
+
+    def record_uncontrolled_episodes(self, domain_idxs=None) -> None:
+        raise NotImplementedError("record_uncontrolled_episodes is not implemented for ParallelFluidEnv (run it on one FluidEnv).")
+
     def detach(self) -> None:
         raise NotImplementedError("detach is not implemented for ParallelFluidEnv.")
 

@@ -339,7 +339,11 @@ class RBCEnvBase(FluidEnv):
 
     @property
     def nu_ref(self) -> float:
-        return float(self._metrics_stats.get("nusselt", 0.0))
+        """rbc_env_base.py:408-416: the median of the uncontrolled Nusselt number in 2-D, its mean in 3-D; 0 without statistics."""
+        s = self._metric_stat("nusselt")
+        if s is None:
+            return 0.0
+        return float(s.p50 if self._ndims == 2 else s.mean)
 
     def _local_nusselt(self, T, u_y, cell_size):
         """``_compute_nusselt`` on per-agent windows (rbc_env_base.py:491-513): ``T, u_y [B, n_agents, *win]``."""

@@ -16,7 +16,7 @@ Mirrors ``envs/tcf/tcf_env.py`` (``TCF3DBottomEnv`` :94-1063, ``TCF3DBothEnv`` :
 * observation: fluctuation velocity ``u - <u>_V`` (components x, y) and pressure on the plane ``y+ = 15``
   (``_get_global_obs`` :646-677), stacked bottom/top for "both" (``:1166-1180``);
 * reward ``1 - tau / tau_ref`` with the wall stress averaged over the sim steps of the env step (``:788-824``),
-  ``tau_ref`` = 1 without domain statistics (``:556-562``); multi-agent mode: per-actuator windows of patch means
+  ``tau_ref`` = mean uncontrolled wall stress of the domain statistics, 1 without them (``:556-562``); multi-agent mode: per-actuator windows of patch means
   (``_get_local_obs`` :918-992, ``:1182-1195``) and the global reward for every agent (``:994-1010``);
 * solver: adaptive CFL 0.1, advection and pressure tol 1e-6, 2 correctors (``:478-500``).
 
@@ -291,7 +291,8 @@ class TCF3DBottomEnv(FluidEnv):
     # ---- metrics / observations -----------------------------------------------------------
     @property
     def tau_ref(self) -> float:
-        return float(self._metrics_stats.get("wall_stress_bottom", 1.0))
+        s = self._metric_stat("wall_stress_bottom")       # tcf_env.py:557-562
+        return 1.0 if s is None else float(s.mean)
 
     def _get_wall_stress(self):
         """(bottom, top) wall shear stress per env ``[B]`` (tcf_env.py:564-584)."""
@@ -395,7 +396,8 @@ class TCF3DBothEnv(TCF3DBottomEnv):
 
     @property
     def tau_ref(self) -> float:
-        return float(self._metrics_stats.get("wall_stress", 1.0))
+        s = self._metric_stat("wall_stress")              # tcf_env.py:1132-1135
+        return 1.0 if s is None else float(s.mean)
 
     def _additional_initialization(self) -> None:
         super()._additional_initialization()

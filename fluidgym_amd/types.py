@@ -11,7 +11,7 @@ from __future__ import annotations
 
 from enum import Enum
 from pathlib import Path
-from typing import Any, Dict, Optional, Protocol, Tuple, Union, runtime_checkable
+from typing import Any, Dict, NamedTuple, Optional, Protocol, Tuple, Union, runtime_checkable
 
 import torch
 
@@ -20,6 +20,20 @@ class EnvMode(Enum):
     TRAIN = "train"
     VAL = "val"
     TEST = "test"
+
+
+class Stats(NamedTuple):
+    """One record of ``domain_statistics.json`` (the reference's ``Stats``, ``envs/fluid_env.py:33-47``): of a metric over the
+    uncontrolled rollout, or of a field over every cell of every sample."""
+
+    mean: float
+    min: float
+    max: float
+    p5: float
+    p25: float
+    p50: float
+    p75: float
+    p95: float
 
 
 @runtime_checkable

@@ -432,6 +432,26 @@ int fg_coherence_litmus(int32_t atomic_access, int32_t nsys, int32_t cells, int3
  * that is NaN, Inf or >= 2^75 in magnitude makes the sum NaN. */
 int fg_dacc_host_sum(const double* values, int64_t n, double plain, double* out_sum);
 int fg_dacc_device_sum(const double* values_host, int64_t n, double plain, int32_t reps, double* out_sums_host, void* stream);
+/* ---- field summaries for the domain statistics (csrc/fg_fieldstats.hip; both libraries, handle-free) ---------------------
+ * One sample of FluidEnv.compute_domain_statistics: per-env moments and a per-env histogram of a contiguous device field
+ * [batch, channels, n] of fg_real (single-block [B,d,(Z,)Y,X], pressure [B,1,...], the multi-block flat [B,d,N]).  The value of a
+ * cell is component `channel`, or with channel = -1 the Euclidean magnitude over all channels (squares accumulated in fp64 in
+ * ascending channel order, then sqrt).  Two jobs, either or both in the one launch over the field:
+ *   moments    (workspace, moments, counts all non-NULL; all NULL = skipped)  moments[batch][3] = min, max over the finite cells
+ *              and their sum through the exact accumulator above (bit-equal to fg_dacc_host_sum over the same values; exact for
+ *              up to 2^20 cells per env and |value| < 2^75, as there); counts[batch][2] = finite cells, non-finite cells.  An env
+ *              without a finite cell reports NaN, NaN, 0.  workspace: batch * FG_FIELD_SUMMARY_WORK_BYTES device bytes, 64-byte
+ *              aligned, initialised and consumed by the call.
+ *   histogram  (hist non-NULL)  hist[batch][nbins] 64-bit counts, nbins in 1..4096, width > 0: the call ADDS one to bin
+ *              clamp(floor((double(v) - lo) / width), 0, nbins - 1) for every finite cell (fp64 IEEE subtraction and division: the
+ *              host expression gives the same bin); the caller zeroes the array.  Non-finite cells are not binned.
+ * Every cross-workgroup combination is an integer atomic (order-preserving keys for min / max, fixed-point words for the sum), so
+ * an env's outputs depend neither on the launch order nor on the rest of the batch.  All outputs are device arrays; the call is
+ * asynchronous on `stream`.  FG_ERR_INVALID_ARG: a null pointer, n <= 0, batch outside 1..65535, channel outside -1..channels-1,
+ * nbins outside 1..4096 or width <= 0 with a histogram. */
+#define FG_FIELD_SUMMARY_WORK_BYTES 128
+int fg_field_summary(const fg_real* field, int32_t batch, int32_t channels, int64_t n, int32_t channel, void* workspace,
+                     double* moments, int64_t* counts, double lo, double width, int32_t nbins, uint64_t* hist, void* stream);
 int fg_profile_enable(fg_handle h, int on);
 int fg_profile_kinds(void);
 const char* fg_profile_kind_name(int kind);
