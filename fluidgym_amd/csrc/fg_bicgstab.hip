@@ -21,7 +21,7 @@ namespace {
 
 constexpr int A_RHO = 0, A_RV = 2, A_SS = 3, A_TS = 4, A_TT = 5, A_RR = 6;
 // A_RHOE + (it & 1): the rho iteration `it` actually uses -- rw.r, or r.r after a breakdown restart (k_bicg_p; the guard of
-// fg_mb_step.hip MB_BETA: an exact rho = 0 or rw.v = 0 at the fp32 rounding level must not turn into inf / NaN)
+// fg_mb_krylov.hip mbb_p_head: an exact rho = 0 or rw.v = 0 at the fp32 rounding level must not turn into inf / NaN)
 constexpr int A_RHOE = 10;
 
 template <int DIMS, int VEC>

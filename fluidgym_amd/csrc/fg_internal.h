@@ -36,7 +36,7 @@ typedef float4 fg_real4;
 // "intermittent non-finite BiCGStab solve" of round 1 was hunted, the suspicion that plain accesses to these words are not
 // coherent across the per-XCD L2s was tested and REJECTED: fg_coherence_litmus reads back 3.2e7 sums exactly under every
 // combination of plain / agent-scope atomic loads and stores, and the captured failures reproduce identically under all of them
-// (they are exact breakdowns of the fp32 recurrence, fg_mb_step.hip MB_BETA).  Agent-scope loads by every wave
+// (they are exact breakdowns of the fp32 recurrence, fg_mb_krylov.hip mbb_p_head).  Agent-scope loads by every wave
 // cost 4-45 % of env-steps/s (same-address requests serialise at the memory side), so the build switches stay at 0:
 // FG_ACC_ACCESS / FG_FLAG_ACCESS (profiles/bicg_stress.sh): bit 0 = agent-scope atomic loads, bit 1 = agent-scope atomic stores,
 // for the accumulators and for the scalar / flag words.

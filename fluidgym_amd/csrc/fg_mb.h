@@ -18,9 +18,11 @@
 
 // mb_real: the scalar type of the multi-block translation units -- fields, tables, recurrence scalars, C ABI (the public header
 // declares the same entry points with fg_real): float in libfluidgym_hip.so, double in the fp64 build (libfluidgym_hip_f64.so,
-// -DFG_REAL_DOUBLE).  What is written for 32-bit words -- the four-cells-per-thread kernels (float4), the on-chip / L2 / cluster CG
-// and the restrictions fused into the float4 BiCGStab kernels: fg_f32 -- stays compiled and is switched off at run time in that
-// build (fg_mb_create / fg_mb_finalize / mb_bicgstab).  The multilevel preconditioner in kernel form (k_ml_*) and the preconditioned
+// -DFG_REAL_DOUBLE).  What is written for 32-bit words -- the four-cells-per-thread CG kernels (float4) and the on-chip / L2 /
+// cluster CG: fg_f32 -- stays compiled and is switched off at run time in that build (fg_mb_create / fg_mb_finalize).  The
+// four-cell BiCGStab kernels (k_mbb_*<DIMS, 4>: packs of mb_real, fg_mb_krylov.hip) and the restrictions fused with the p / s update
+// are well-formed in doubles too, but have not been measured or tested there and stay switched off as well (mb_bicgstab: vec_mask,
+// ml_fused).  The multilevel preconditioner in kernel form (k_ml_*) and the preconditioned
 // CG on it (k_mbc_*_pre) are written in mb_real and serve both builds; fg_mb_set_multilevel installs the tables in either.
 // (Until round 4 the fp64 build renamed the keyword `float` for these files.)
 typedef float fg_f32;

@@ -17,20 +17,26 @@ namespace {
 
 struct MbGraphKey { MbSolve q; int vec4, project_mean; hipStream_t stream; };
 
-template <int DIMS>
-__device__ __forceinline__ mb_real mb_spmv(const MbDev& D, const MbSolve& q, int b, const mb_real* __restrict__ x, int i) {
+// (A x) at cell i: xi = the vector at the cell itself, gather(n) = the vector at any other cell
+template <int DIMS, typename G>
+__device__ __forceinline__ mb_real mb_spmv_core(const MbDev& D, const MbSolve& q, int b, int i, mb_real xi, G gather) {
     constexpr int F = 2 * DIMS;
-    mb_real y = q.diag[(size_t)b * D.N + i] * x[i];
+    mb_real y = q.diag[(size_t)b * D.N + i] * xi;
 #pragma unroll
     for (int f = 0; f < F; ++f) {
         const int n = D.nbr[(size_t)f * D.N + i];
-        if (n >= 0) y += q.off[((size_t)b * F + f) * D.N + i] * x[n];
+        if (n >= 0) y += q.off[((size_t)b * F + f) * D.N + i] * gather(n);
     }
     return y;
 }
+template <int DIMS>
+__device__ __forceinline__ mb_real mb_spmv(const MbDev& D, const MbSolve& q, int b, const mb_real* __restrict__ x, int i) {
+    return mb_spmv_core<DIMS>(D, q, b, i, x[i], [x](int n) { return x[n]; });
+}
 
-#define MB_SYS                                          \
-    const int i = blockIdx.x * FG_BLOCK + threadIdx.x;  \
+// the thread's first cell i of W consecutive ones (W = 4 only where N % 4 == 0: then valid covers all four), its system and words
+#define MB_SYSW(W)                                              \
+    const int i = (blockIdx.x * FG_BLOCK + threadIdx.x) * (W);  \
     const int sys = q.sys_map ? q.sys_map[blockIdx.y] : (int)blockIdx.y;   /* (compacted launches: MbSolve::sys_map) */ \
     const int b = sys / q.nc;                           \
     const int N = D.N;                                  \
@@ -40,7 +46,18 @@ __device__ __forceinline__ mb_real mb_spmv(const MbDev& D, const MbSolve& q, int
     FgDacc* a = q.acc + (size_t)sys * MB_ACC;           \
     __shared__ mb_real lds[16];                           \
     (void)b; (void)leader; (void)a; (void)lds; (void)valid;
+#define MB_SYS MB_SYSW(1)
 
+// tail of the kernels that lay a residual down (k_mbs_init, k_mbr_residual): |r|^2 to A_RHO and A_RR -- unless the projected start
+// leaves that to k_mbb_project_init (defer_rho) -- and the workgroup's sum of `proj` to sum_slot (>= 0)
+__device__ __forceinline__ void mb_residual_tail(FgDacc* a, mb_real* lds, mb_real rr, mb_real proj, int sum_slot, int defer_rho) {
+    const mb_real s = mb_block_sum(rr, lds);
+    const mb_real s1 = sum_slot >= 0 ? mb_block_sum(proj, lds) : 0.f;
+    if (threadIdx.x == 0) {
+        if (!defer_rho) { acc_add(a + A_RHO, (double)s); acc_add(a + A_RR, (double)s); }
+        if (sum_slot >= 0) acc_add(a + sum_slot, (double)s1);
+    }
+}
 
 __global__ void k_mbs_begin(const mb_real* __restrict__ dt, MbSolve q, int nsys) {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
@@ -69,12 +86,8 @@ __global__ __launch_bounds__(FG_BLOCK) void k_mbs_init(MbDev D, MbSolve q, int u
         if (q.rw) q.rw[vb + i] = r;
         q.p[vb + i] = r;
     }
-    const mb_real s = mb_block_sum(r * r, lds);
-    const mb_real s1 = sum_slot >= 0 ? mb_block_sum(valid ? r * (q.project ? 1.f : D.yproj[i]) : 0.f, lds) : 0.f;
-    if (threadIdx.x == 0) {
-        if (!defer_rho) { acc_add(a + A_RHO, (double)s); acc_add(a + A_RR, (double)s); }
-        if (sum_slot >= 0) acc_add(a + sum_slot, (double)s1);
-    }
+    // (D.yproj is read only where a sum is asked for: it may be null otherwise)
+    mb_residual_tail(a, lds, r * r, (sum_slot >= 0 && valid) ? r * (q.project ? 1.f : D.yproj[i]) : 0.f, sum_slot, defer_rho);
 }
 
 // restart of the BiCGStab recurrence from the current iterate (the reference's residualResetSteps, bicgstab_solver_kernel.cu):
@@ -120,12 +133,7 @@ __global__ __launch_bounds__(FG_BLOCK) void k_mbr_residual(MbDev D, MbSolve q, c
         q.x[vb + i] = 0.f;
         q.r[vb + i] = r; q.rw[vb + i] = r; q.p[vb + i] = r;
     }
-    const mb_real s = mb_block_sum(r * r, lds);
-    const mb_real s1 = sum_slot >= 0 ? mb_block_sum(valid ? r : 0.f, lds) : 0.f;
-    if (threadIdx.x == 0) {
-        if (!defer_rho) { acc_add(a + A_RHO, (double)s); acc_add(a + A_RR, (double)s); }
-        if (sum_slot >= 0) acc_add(a + sum_slot, (double)s1);
-    }
+    mb_residual_tail(a, lds, r * r, r, sum_slot, defer_rho);   // (r is 0 in the threads without a cell)
 }
 
 // best iterate of the refined BiCGStab: at every refinement point the TRUE residual is known (A_RR after k_mbr_residual /
@@ -174,175 +182,124 @@ __global__ __launch_bounds__(FG_BLOCK) void k_mbb_project_init(int N, MbSolve q)
     if (threadIdx.x == 0) { acc_add(a + A_RHO, (double)s); acc_add(a + A_RR, (double)s); }
 }
 
-// ---- BiCGStab (same five-kernel recurrence as fg_bicgstab.hip)
-// beta of iteration `it` and the breakdown guard.  In fp32 the last iterations of a solve whose tolerance sits at the rounding
-// level of its right-hand side run on sums (rw.r, rw.v) that cancel to their rounding lattice -- which contains 0: an exact
-// rho = 0 or rw.v = 0 turned alpha / beta into inf or NaN about once in 10^5-10^6 system solves (deterministic for
-// given inputs, profiles/bicg_history.py).  rw.v == 0 makes k_mbb_s take alpha = 0 (the iteration degenerates to its minimal-
-// residual half); a non-finite beta (rho of the previous iteration 0, omega 0) restarts the recurrence HERE from the current
-// residual: rw = p = r, rho = r.r.  Every workgroup of a system decides from the same words, so the decision is uniform.
-#define MB_BETA                                                                                                                   \
-    const mb_real alpha = sc_ld(q.sc + (sys * 2)), omega = sc_ld(q.sc + (sys * 2 + 1));                                             \
-    const double rho_now = acc_ld(a + (A_RHO + (it & 1)));                                                                         \
-    const mb_real beta = it == 0 ? 0.f : (mb_real)(rho_now / acc_ld(a + (A_RHOE + ((it + 1) & 1)))) * (alpha / omega);                \
-    const bool restart = it > 0 && !isfinite(beta);                                                                                \
-    if (leader) acc_st(a + (A_RHOE + (it & 1)), restart ? acc_ld(a + (A_RR)) : rho_now);
-template <int DIMS>
-__global__ __launch_bounds__(FG_BLOCK) void k_mbb_p(MbDev D, MbSolve q, int it) {
-    MB_SYS
+// ---- BiCGStab (same five-kernel recurrence as fg_bicgstab.hip).  Every kernel exists for W = 1 and W = 4 cells per thread
+// (MB_SYSW, MbPack); mb_bicgstab picks per kernel (FG_MB_BICG_VEC4).
+
+// Head of the kernels that form p (k_mbb_p, k_mbb_pv, k_ml_restrict_p): flag check, verdict on r.r, the leader's bookkeeping, beta
+// of iteration `it` and the breakdown guard.  go == false: the system does not iterate (any more), nothing else is set.
+// The guard: in fp32 the last iterations of a solve whose tolerance sits at the rounding level of its right-hand side run on sums
+// (rw.r, rw.v) that cancel to their rounding lattice -- which contains 0: an exact rho = 0 or rw.v = 0 turned alpha / beta into inf
+// or NaN about once in 10^5-10^6 system solves (deterministic for given inputs, profiles/bicg_history.py).
+// rw.v == 0 makes mbb_s_head take alpha = 0 (the iteration degenerates to its minimal-residual half); a non-finite beta (rho of the
+// previous iteration 0, omega 0) restarts the recurrence HERE from the current residual: rw = p = r, rho = r.r.  Every workgroup of
+// a system decides from the same words, so the decision is uniform.
+// The leader's stores keep their order: info words, then the single flag store (mb_mark).
+struct MbPHead { bool go; mb_real alpha, omega, beta; bool restart; };
+__device__ __forceinline__ MbPHead mbb_p_head(const MbSolve& q, int sys, FgDacc* a, int N, bool leader, int it) {
+    MbPHead h = {false, 0.f, 0.f, 0.f, false};
     const int f = flag_ld(q.flags + (sys));
-    if (f == 4) { if (leader) flag_st(q.flags + (sys), 1); return; }
-    if (f != 0) return;
+    if (f == 4) { if (leader) flag_st(q.flags + (sys), 1); return h; }   // converged on s (mbb_half), x has been advanced
+    if (f != 0) return h;
     const mb_real crit = mb_rms(acc_ld(a + (A_RR)), N);
-    if (!(crit >= q.tol)) { if (leader) mb_mark(q, sys, crit, (it == 0 && q.it_base == 0) ? -1 : it + q.it_base); return; }
+    if (!(crit >= q.tol)) { if (leader) mb_mark(q, sys, crit, (it == 0 && q.it_base == 0) ? -1 : it + q.it_base); return h; }
     if (leader) {
         acc_st(a + (A_SS), 0.0); acc_st(a + (A_TS), 0.0); acc_st(a + (A_TT), 0.0); acc_st(a + (A_ST), 0.0);
         q.info[sys].final_residual = crit;
         q.info[sys].used_iterations = it + q.it_base - 1;
     }
-    MB_BETA
-    if (it == 0 || !valid) return;
-    const mb_real mv = q.project ? (mb_real)(acc_ld(a + (A_SV + 2 * ((it + 1) & 1))) / (double)N) : 0.f;  // sum v of the previous iteration (slots 7 / 9 alternate)
-    if (restart) { const mb_real r = q.r[vb + i]; q.rw[vb + i] = r; q.p[vb + i] = r; }
-    else q.p[vb + i] = q.r[vb + i] + beta * (q.p[vb + i] - omega * (q.v[vb + i] - mv));
+    h.alpha = sc_ld(q.sc + (sys * 2)); h.omega = sc_ld(q.sc + (sys * 2 + 1));
+    const double rho_now = acc_ld(a + (A_RHO + (it & 1)));
+    h.beta = it == 0 ? 0.f : (mb_real)(rho_now / acc_ld(a + (A_RHOE + ((it + 1) & 1)))) * (h.alpha / h.omega);
+    h.restart = it > 0 && !isfinite(h.beta);
+    if (leader) acc_st(a + (A_RHOE + (it & 1)), h.restart ? acc_ld(a + (A_RR)) : rho_now);
+    h.go = true;
+    return h;
 }
-template <int DIMS>
-__global__ __launch_bounds__(FG_BLOCK) void k_mbb_v(MbDev D, MbSolve q, int it) {
-    MB_SYS
-    if (flag_ld(q.flags + (sys)) != 0) return;
-    mb_real part = 0.f, psum = 0.f;
-    if (valid) {
-        const mb_real y = mb_spmv<DIMS>(D, q, b, (q.mp ? q.mp : q.p) + vb, i);
-        q.v[vb + i] = y;
-        part = q.rw[vb + i] * y;  // rw is mean-free: rw . (v - mean v) = rw . v
-        psum = y;
-    }
-    part = mb_block_sum(part, lds);
-    if (q.project) psum = mb_block_sum(psum, lds);
-    { const int sl[2] = {A_RV, A_SV + 2 * (it & 1)}; const mb_real vv[2] = {part, psum}; const bool on[2] = {true, (bool)q.project}; mb_acc_tail<2>(a, sl, vv, on); }
+// mean of v of the previous iteration for the projected recurrence (slots 7 / 9 alternate).  runs_at_it0: the caller also forms p
+// at iteration 0, where there is no previous v (k_mbb_pv, k_ml_restrict_p); k_mbb_p has returned by then and reads unguarded
+__device__ __forceinline__ mb_real mbb_prev_mean_v(const MbSolve& q, const FgDacc* a, int N, int it, bool runs_at_it0) {
+    return (q.project && (!runs_at_it0 || it > 0)) ? (mb_real)(acc_ld(a + (A_SV + 2 * ((it + 1) & 1))) / (double)N) : 0.f;
 }
-template <int DIMS>
-__global__ __launch_bounds__(FG_BLOCK) void k_mbb_s(MbDev D, MbSolve q, int it) {
-    MB_SYS
-    if (flag_ld(q.flags + (sys)) != 0) return;
+// Head of the kernels that form s (k_mbb_s, k_mbb_st, k_ml_restrict_s), behind their flag check: the guarded alpha (rw.v == 0:
+// see mbb_p_head), the accumulator slots of the next iteration zeroed, the mean of v
+struct MbSHead { mb_real alpha, mv; };
+__device__ __forceinline__ MbSHead mbb_s_head(const MbSolve& q, int sys, FgDacc* a, int N, bool leader, int it) {
     const mb_real alpha_raw = (mb_real)(acc_ld(a + (A_RHOE + (it & 1))) / acc_ld(a + (A_RV)));
-    const mb_real alpha = isfinite(alpha_raw) ? alpha_raw : 0.f;   // rw.v == 0: see MB_BETA
-    if (leader) { sc_st(q.sc + (sys * 2), alpha); acc_st(a + (A_RHO + ((it + 1) & 1)), 0.0); acc_st(a + (A_RR), 0.0); acc_st(a + (A_SV + 2 * ((it + 1) & 1)), 0.0); }
-    const mb_real mv = q.project ? (mb_real)(acc_ld(a + (A_SV + 2 * (it & 1))) / (double)N) : 0.f;
-    mb_real part = 0.f;
-    if (valid) {
-        const mb_real r = q.r[vb + i] - alpha * (q.v[vb + i] - mv);
-        q.r[vb + i] = r;
-        part = r * r;
-    }
-    part = mb_block_sum(part, lds);
-    if (threadIdx.x == 0) acc_add(a + A_SS, (double)part);
+    MbSHead h;
+    h.alpha = isfinite(alpha_raw) ? alpha_raw : 0.f;
+    if (leader) { sc_st(q.sc + (sys * 2), h.alpha); acc_st(a + (A_RHO + ((it + 1) & 1)), 0.0); acc_st(a + (A_RR), 0.0); acc_st(a + (A_SV + 2 * ((it + 1) & 1)), 0.0); }
+    h.mv = q.project ? (mb_real)(acc_ld(a + (A_SV + 2 * (it & 1))) / (double)N) : 0.f;
+    return h;
 }
-template <int DIMS>
-__global__ __launch_bounds__(FG_BLOCK) void k_mbb_t(MbDev D, MbSolve q, int it) {
-    MB_SYS
-    if (flag_ld(q.flags + (sys)) != 0) return;
+// "converged on s" (x += alpha p only, bicgstab_solver_kernel.cu:305-329) for k_mbb_x; f = the system's flag.  With separate s and
+// t kernels the t kernel has decided (flag 4).  With the fused kernel the decision is taken HERE from the complete s.s -- every
+// workgroup of the system computes the same value; the leader publishes flag 4, which the p head of the next iteration (or
+// k_mbs_check) turns into "converged".  A workgroup that starts after the leader's store reads 4 instead of 0 and decides the same
+// from s.s.  Returns 0: full iteration, 1: x += alpha p only, -1: non-finite s.s -- flagged, nothing is added to x.
+__device__ __forceinline__ int mbb_half(const MbSolve& q, int sys, const FgDacc* a, int N, bool leader, int it, int f) {
+    if (!q.sbuf) return f == 4;
     const mb_real crit_s = mb_rms(acc_ld(a + (A_SS)), N);
-    if (!(crit_s >= q.tol)) {  // converged on s (bicgstab_solver_kernel.cu:305-329): k_mbb_x applies x += alpha p
-        if (leader) mb_mark(q, sys, crit_s, it, 4);
-        return;
+    if (crit_s >= q.tol) return 0;
+    const bool fin = isfinite(crit_s);
+    if (leader) {
+        q.info[sys].final_residual = crit_s; q.info[sys].used_iterations = it + q.it_base;
+        q.info[sys].converged = fin ? 1 : 0; q.info[sys].is_finite = fin ? 1 : 0;
+        flag_st(q.flags + (sys), fin ? 4 : 2);
     }
-    mb_real pt = 0.f, ptt = 0.f, pst = 0.f;
-    if (valid) {
-        const mb_real t = mb_spmv<DIMS>(D, q, b, (q.ms ? q.ms : q.r) + vb, i);
-        q.t[vb + i] = t;
-        pt = t * q.r[vb + i];  // s is mean-free: (t - mean t) . s = t . s
-        ptt = t * t;
-        pst = t;
-    }
-    pt = mb_block_sum(pt, lds);
-    ptt = mb_block_sum(ptt, lds);
-    if (q.project) pst = mb_block_sum(pst, lds);
-    { const int sl[3] = {A_TS, A_TT, A_ST}; const mb_real vv[3] = {pt, ptt, pst}; const bool on[3] = {true, true, (bool)q.project}; mb_acc_tail<3>(a, sl, vv, on); }
-}
-// "converged on s" (x += alpha p only, bicgstab_solver_kernel.cu:305-329).  With separate s and t kernels the t kernel has decided
-// (flag 4).  With the fused kernel the decision is taken HERE from the complete s.s -- every workgroup of the system computes the
-// same value; the leader publishes flag 4, which k_mbb_p of the next iteration (or k_mbs_check) turns into "converged".  A
-// workgroup that starts after the leader's store reads 4 instead of 0 and decides the same from s.s.  Non-finite s.s: flagged,
-// nothing is added to x.
-#define MB_HALF                                                                                                           \
-    bool half = (f == 4);                                                                                                 \
-    if (q.sbuf) {                                                                                                         \
-        const mb_real crit_s = mb_rms(acc_ld(a + (A_SS)), N);                                                               \
-        half = !(crit_s >= q.tol);                                                                                        \
-        if (half) {                                                                                                       \
-            const bool fin = isfinite(crit_s);                                                                            \
-            if (leader) {                                                                                                 \
-                q.info[sys].final_residual = crit_s; q.info[sys].used_iterations = it + q.it_base;                        \
-                q.info[sys].converged = fin ? 1 : 0; q.info[sys].is_finite = fin ? 1 : 0;                                 \
-                flag_st(q.flags + (sys), fin ? 4 : 2);                                                                    \
-            }                                                                                                             \
-            if (!fin) return;                                                                                             \
-        }                                                                                                                 \
-    }
-template <int DIMS>
-__global__ __launch_bounds__(FG_BLOCK) void k_mbb_x(MbDev D, MbSolve q, int it) {
-    MB_SYS
-    const int f = flag_ld(q.flags + (sys));
-    if (f != 0 && f != 4) return;
-    const mb_real alpha = sc_ld(q.sc + (sys * 2));
-    MB_HALF
-    const double st = q.project ? acc_ld(a + (A_ST)) : 0.0;
-    const mb_real mt = (mb_real)(st / (double)N);
-    const mb_real omega_raw = half ? 0.f : (mb_real)(acc_ld(a + (A_TS)) / (acc_ld(a + (A_TT)) - st * st / (double)N));
-    const mb_real omega = isfinite(omega_raw) ? omega_raw : 0.f;
-    if (leader) { sc_st(q.sc + (sys * 2 + 1), omega); acc_st(a + (A_RV), 0.0); }
-    mb_real prr = 0.f, prho = 0.f;
-    if (valid) {
-        const mb_real pd = (q.mp ? q.mp : q.p)[vb + i];
-        if (half) {
-            q.x[vb + i] += alpha * pd;
-        } else {
-            const mb_real sv = (q.sbuf ? q.sbuf : q.r)[vb + i];
-            q.x[vb + i] += alpha * pd + omega * (q.ms ? q.ms[vb + i] : sv);
-            const mb_real r = sv - omega * (q.t[vb + i] - mt);
-            q.r[vb + i] = r;
-            prr = r * r;
-            prho = q.rw[vb + i] * r;
-        }
-    }
-    if (half) return;
-    mb_real sums[2] = {prr, prho};
-    mb_block_sums<2>(sums, lds);
-    { const int sl[2] = {A_RR, A_RHO + ((it + 1) & 1)}; const mb_real vv[2] = {sums[0], sums[1]}; const bool on[2] = {true, true}; mb_acc_tail<2>(a, sl, vv, on); }
+    return fin ? 1 : -1;
 }
 
-// ---- the same five kernels with four consecutive cells per thread (N % 4 == 0): 128-bit loads / stores of the cell's own
-// data, the -x / +x neighbours of the stencil from the thread's own cells or a lane shuffle (as in k_mbc_ap4).  At
+// W consecutive cells of a thread.  W = 4 (N % 4 == 0): one 128-bit load / store of the cell's own data (256-bit in the fp64
+// build) and the -x / +x neighbours of the stencil from the thread's own cells or a lane shuffle (as in k_mbc_ap4) -- at
 // 16 envs x 46.7 k cells the one-cell kernels took 51 us per iteration, 2-3x what their bytes need.
-#define MB_SYS4                                                   \
-    const int i = (blockIdx.x * FG_BLOCK + threadIdx.x) * 4;      \
-    const int sys = q.sys_map ? q.sys_map[blockIdx.y] : (int)blockIdx.y;   \
-    const int b = sys / q.nc;                                     \
-    const int N = D.N;                                            \
-    const bool valid = i < N;                                     \
-    const bool leader = (blockIdx.x == 0 && threadIdx.x == 0);    \
-    const size_t vb = (size_t)sys * N;                            \
-    FgDacc* a = q.acc + (size_t)sys * MB_ACC;                     \
-    __shared__ mb_real lds[16];                                     \
-    (void)b; (void)leader; (void)a; (void)lds; (void)valid;
-__device__ __forceinline__ float4 ld4(const mb_real* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(mb_real* p, mb_real a, mb_real b, mb_real c, mb_real d) { *reinterpret_cast<float4*>(p) = make_float4(a, b, c, d); }
+template <int W>
+struct MbPack {
+    typedef mb_real Vec __attribute__((ext_vector_type(W)));
+    Vec v;
+    __device__ __forceinline__ mb_real operator[](int e) const { return v[e]; }
+};
+template <int W>
+__device__ __forceinline__ MbPack<W> mb_ld(const mb_real* p) { return *reinterpret_cast<const MbPack<W>*>(p); }
+template <int W>
+__device__ __forceinline__ void mb_st(mb_real* p, const MbPack<W>& v) { *reinterpret_cast<MbPack<W>*>(p) = v; }
+template <int W, typename Fn>
+__device__ __forceinline__ MbPack<W> mb_map(Fn fn) {
+    MbPack<W> o;
+#pragma unroll
+    for (int e = 0; e < W; ++e) o.v[e] = fn(e);
+    return o;
+}
+// a . b and the sum of a over the thread's cells, seeded with the first term: under -ffp-contract=fast a chain of FMAs onto
+// a0 * b0, the order the partial sums have always had (seeding with 0 would round differently)
+template <int W>
+__device__ __forceinline__ mb_real mb_dot(const MbPack<W>& a, const MbPack<W>& b) {
+    mb_real s = a[0] * b[0];
+#pragma unroll
+    for (int e = 1; e < W; ++e) s += a[e] * b[e];
+    return s;
+}
+template <int W>
+__device__ __forceinline__ mb_real mb_sum(const MbPack<W>& a) {
+    mb_real s = a[0];
+#pragma unroll
+    for (int e = 1; e < W; ++e) s += a[e];
+    return s;
+}
 // y = A x for the thread's four cells: xi = the vector at the own cells, gather(n) = the vector at any other cell
 template <int DIMS, typename G>
-__device__ __forceinline__ void mb_spmv4_core(const MbDev& D, const MbSolve& q, int b, int i, const mb_real xi[4], G gather, mb_real y[4]) {
+__device__ __forceinline__ void mb_spmv4_core(const MbDev& D, const MbSolve& q, int b, int i, const MbPack<4>& xi, G gather, MbPack<4>& y) {
     constexpr int F = 2 * DIMS;
     const int N = D.N;
-    const float4 d4 = ld4(q.diag + (size_t)b * N + i);
-    y[0] = d4.x * xi[0]; y[1] = d4.y * xi[1]; y[2] = d4.z * xi[2]; y[3] = d4.w * xi[3];
+    const MbPack<4> d4 = mb_ld<4>(q.diag + (size_t)b * N + i);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) y.v[e] = d4[e] * xi[e];
     const int lane = threadIdx.x & 63;
     const mb_real from_prev = __shfl_up(xi[3], 1), from_next = __shfl_down(xi[0], 1);
 #pragma unroll
     for (int f = 0; f < F; ++f) {
         const int4 n4 = *reinterpret_cast<const int4*>(D.nbr + (size_t)f * N + i);
-        const float4 o4 = ld4(q.off + ((size_t)b * F + f) * N + i);
+        const MbPack<4> oo = mb_ld<4>(q.off + ((size_t)b * F + f) * N + i);
         const int nn[4] = {n4.x, n4.y, n4.z, n4.w};
-        const mb_real oo[4] = {o4.x, o4.y, o4.z, o4.w};
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const int n = nn[e];
@@ -351,104 +308,93 @@ __device__ __forceinline__ void mb_spmv4_core(const MbDev& D, const MbSolve& q, 
             if (f == 0 && n == i + e - 1 && (e > 0 || lane > 0)) xn = e > 0 ? xi[e > 0 ? e - 1 : 0] : from_prev;
             else if (f == 1 && n == i + e + 1 && (e < 3 || lane < 63)) xn = e < 3 ? xi[e < 3 ? e + 1 : 3] : from_next;
             else xn = gather(n);
-            y[e] += oo[e] * xn;
+            y.v[e] += oo[e] * xn;
         }
     }
 }
-template <int DIMS>
-__device__ __forceinline__ void mb_spmv4(const MbDev& D, const MbSolve& q, int b, const mb_real* __restrict__ x, int i, mb_real y[4]) {
-    const float4 x4 = ld4(x + i);
-    const mb_real xi[4] = {x4.x, x4.y, x4.z, x4.w};
-    mb_spmv4_core<DIMS>(D, q, b, i, xi, [x](int n) { return x[n]; }, y);
+// y = A x at the thread's W cells behind one entry: the one-cell gather (mb_spmv_core) or the four-cell one
+template <int DIMS, int W, typename G>
+__device__ __forceinline__ MbPack<W> mb_apply(const MbDev& D, const MbSolve& q, int b, int i, const MbPack<W>& xi, G gather) {
+    MbPack<W> y;
+    if constexpr (W == 4) mb_spmv4_core<DIMS>(D, q, b, i, xi, gather, y);
+    else y.v[0] = mb_spmv_core<DIMS>(D, q, b, i, xi[0], gather);
+    return y;
 }
-template <int DIMS>
-__global__ __launch_bounds__(FG_BLOCK) void k_mbb_p4(MbDev D, MbSolve q, int it) {
-    MB_SYS4
-    const int f = flag_ld(q.flags + (sys));
-    if (f == 4) { if (leader) flag_st(q.flags + (sys), 1); return; }
-    if (f != 0) return;
-    const mb_real crit = mb_rms(acc_ld(a + (A_RR)), N);
-    if (!(crit >= q.tol)) { if (leader) mb_mark(q, sys, crit, (it == 0 && q.it_base == 0) ? -1 : it + q.it_base); return; }
-    if (leader) {
-        acc_st(a + (A_SS), 0.0); acc_st(a + (A_TS), 0.0); acc_st(a + (A_TT), 0.0); acc_st(a + (A_ST), 0.0);
-        q.info[sys].final_residual = crit;
-        q.info[sys].used_iterations = it + q.it_base - 1;
-    }
-    MB_BETA
-    if (it == 0 || !valid) return;
-    const mb_real mv = q.project ? (mb_real)(acc_ld(a + (A_SV + 2 * ((it + 1) & 1))) / (double)N) : 0.f;
-    const float4 r = ld4(q.r + vb + i);
-    if (restart) { st4(q.rw + vb + i, r.x, r.y, r.z, r.w); st4(q.p + vb + i, r.x, r.y, r.z, r.w); return; }
-    const float4 p = ld4(q.p + vb + i), v = ld4(q.v + vb + i);
-    st4(q.p + vb + i, r.x + beta * (p.x - omega * (v.x - mv)), r.y + beta * (p.y - omega * (v.y - mv)),
-        r.z + beta * (p.z - omega * (v.z - mv)), r.w + beta * (p.w - omega * (v.w - mv)));
+
+template <int DIMS, int W>
+__global__ __launch_bounds__(FG_BLOCK) void k_mbb_p(MbDev D, MbSolve q, int it) {
+    MB_SYSW(W)
+    const MbPHead h = mbb_p_head(q, sys, a, N, leader, it);
+    if (!h.go || it == 0 || !valid) return;
+    const mb_real mv = mbb_prev_mean_v(q, a, N, it, false);
+    const MbPack<W> r = mb_ld<W>(q.r + vb + i);
+    if (h.restart) { mb_st<W>(q.rw + vb + i, r); mb_st<W>(q.p + vb + i, r); return; }
+    const MbPack<W> p = mb_ld<W>(q.p + vb + i), v = mb_ld<W>(q.v + vb + i);
+    mb_st<W>(q.p + vb + i, mb_map<W>([&](int e) { return r[e] + h.beta * (p[e] - h.omega * (v[e] - mv)); }));
 }
-template <int DIMS>
-__global__ __launch_bounds__(FG_BLOCK) void k_mbb_v4(MbDev D, MbSolve q, int it) {
-    MB_SYS4
+template <int DIMS, int W>
+__global__ __launch_bounds__(FG_BLOCK) void k_mbb_v(MbDev D, MbSolve q, int it) {
+    MB_SYSW(W)
     if (flag_ld(q.flags + (sys)) != 0) return;
     mb_real part = 0.f, psum = 0.f;
     if (valid) {
-        mb_real y[4];
-        mb_spmv4<DIMS>(D, q, b, (q.mp ? q.mp : q.p) + vb, i, y);
-        st4(q.v + vb + i, y[0], y[1], y[2], y[3]);
-        const float4 w = ld4(q.rw + vb + i);
-        part = w.x * y[0] + w.y * y[1] + w.z * y[2] + w.w * y[3];
-        psum = y[0] + y[1] + y[2] + y[3];
+        const mb_real* __restrict__ x = (q.mp ? q.mp : q.p) + vb;
+        const MbPack<W> y = mb_apply<DIMS, W>(D, q, b, i, mb_ld<W>(x + i), [x](int n) { return x[n]; });
+        mb_st<W>(q.v + vb + i, y);
+        part = mb_dot<W>(mb_ld<W>(q.rw + vb + i), y);  // rw is mean-free: rw . (v - mean v) = rw . v
+        psum = mb_sum<W>(y);
     }
     part = mb_block_sum(part, lds);
     if (q.project) psum = mb_block_sum(psum, lds);
     { const int sl[2] = {A_RV, A_SV + 2 * (it & 1)}; const mb_real vv[2] = {part, psum}; const bool on[2] = {true, (bool)q.project}; mb_acc_tail<2>(a, sl, vv, on); }
 }
-template <int DIMS>
-__global__ __launch_bounds__(FG_BLOCK) void k_mbb_s4(MbDev D, MbSolve q, int it) {
-    MB_SYS4
+template <int DIMS, int W>
+__global__ __launch_bounds__(FG_BLOCK) void k_mbb_s(MbDev D, MbSolve q, int it) {
+    MB_SYSW(W)
     if (flag_ld(q.flags + (sys)) != 0) return;
-    const mb_real alpha_raw = (mb_real)(acc_ld(a + (A_RHOE + (it & 1))) / acc_ld(a + (A_RV)));
-    const mb_real alpha = isfinite(alpha_raw) ? alpha_raw : 0.f;   // rw.v == 0: see MB_BETA
-    if (leader) { sc_st(q.sc + (sys * 2), alpha); acc_st(a + (A_RHO + ((it + 1) & 1)), 0.0); acc_st(a + (A_RR), 0.0); acc_st(a + (A_SV + 2 * ((it + 1) & 1)), 0.0); }
-    const mb_real mv = q.project ? (mb_real)(acc_ld(a + (A_SV + 2 * (it & 1))) / (double)N) : 0.f;
+    const MbSHead h = mbb_s_head(q, sys, a, N, leader, it);
     mb_real part = 0.f;
     if (valid) {
-        const float4 r = ld4(q.r + vb + i), v = ld4(q.v + vb + i);
-        const mb_real s0 = r.x - alpha * (v.x - mv), s1 = r.y - alpha * (v.y - mv), s2 = r.z - alpha * (v.z - mv), s3 = r.w - alpha * (v.w - mv);
-        st4(q.r + vb + i, s0, s1, s2, s3);
-        part = s0 * s0 + s1 * s1 + s2 * s2 + s3 * s3;
+        const MbPack<W> r = mb_ld<W>(q.r + vb + i), v = mb_ld<W>(q.v + vb + i);
+        const MbPack<W> sv = mb_map<W>([&](int e) { return r[e] - h.alpha * (v[e] - h.mv); });
+        mb_st<W>(q.r + vb + i, sv);
+        part = mb_dot<W>(sv, sv);
     }
     part = mb_block_sum(part, lds);
     if (threadIdx.x == 0) acc_add(a + A_SS, (double)part);
 }
-template <int DIMS>
-__global__ __launch_bounds__(FG_BLOCK) void k_mbb_t4(MbDev D, MbSolve q, int it) {
-    MB_SYS4
+template <int DIMS, int W>
+__global__ __launch_bounds__(FG_BLOCK) void k_mbb_t(MbDev D, MbSolve q, int it) {
+    MB_SYSW(W)
     if (flag_ld(q.flags + (sys)) != 0) return;
     const mb_real crit_s = mb_rms(acc_ld(a + (A_SS)), N);
-    if (!(crit_s >= q.tol)) {
+    if (!(crit_s >= q.tol)) {  // converged on s (bicgstab_solver_kernel.cu:305-329): k_mbb_x applies x += alpha p
         if (leader) mb_mark(q, sys, crit_s, it, 4);
         return;
     }
     mb_real pt = 0.f, ptt = 0.f, pst = 0.f;
     if (valid) {
-        mb_real t[4];
-        mb_spmv4<DIMS>(D, q, b, (q.ms ? q.ms : q.r) + vb, i, t);
-        st4(q.t + vb + i, t[0], t[1], t[2], t[3]);
-        const float4 sv = ld4(q.r + vb + i);
-        pt = t[0] * sv.x + t[1] * sv.y + t[2] * sv.z + t[3] * sv.w;
-        ptt = t[0] * t[0] + t[1] * t[1] + t[2] * t[2] + t[3] * t[3];
-        pst = t[0] + t[1] + t[2] + t[3];
+        const mb_real* __restrict__ x = (q.ms ? q.ms : q.r) + vb;
+        const MbPack<W> t = mb_apply<DIMS, W>(D, q, b, i, mb_ld<W>(x + i), [x](int n) { return x[n]; });
+        mb_st<W>(q.t + vb + i, t);
+        pt = mb_dot<W>(t, mb_ld<W>(q.r + vb + i));  // s is mean-free: (t - mean t) . s = t . s
+        ptt = mb_dot<W>(t, t);
+        pst = mb_sum<W>(t);
     }
     pt = mb_block_sum(pt, lds);
     ptt = mb_block_sum(ptt, lds);
     if (q.project) pst = mb_block_sum(pst, lds);
     { const int sl[3] = {A_TS, A_TT, A_ST}; const mb_real vv[3] = {pt, ptt, pst}; const bool on[3] = {true, true, (bool)q.project}; mb_acc_tail<3>(a, sl, vv, on); }
 }
-template <int DIMS>
-__global__ __launch_bounds__(FG_BLOCK) void k_mbb_x4(MbDev D, MbSolve q, int it) {
-    MB_SYS4
+template <int DIMS, int W>
+__global__ __launch_bounds__(FG_BLOCK) void k_mbb_x(MbDev D, MbSolve q, int it) {
+    MB_SYSW(W)
     const int f = flag_ld(q.flags + (sys));
     if (f != 0 && f != 4) return;
     const mb_real alpha = sc_ld(q.sc + (sys * 2));
-    MB_HALF
+    const int hs = mbb_half(q, sys, a, N, leader, it, f);
+    if (hs < 0) return;
+    const bool half = hs > 0;
     const double st = q.project ? acc_ld(a + (A_ST)) : 0.0;
     const mb_real mt = (mb_real)(st / (double)N);
     const mb_real omega_raw = half ? 0.f : (mb_real)(acc_ld(a + (A_TS)) / (acc_ld(a + (A_TT)) - st * st / (double)N));
@@ -456,18 +402,19 @@ __global__ __launch_bounds__(FG_BLOCK) void k_mbb_x4(MbDev D, MbSolve q, int it)
     if (leader) { sc_st(q.sc + (sys * 2 + 1), omega); acc_st(a + (A_RV), 0.0); }
     mb_real prr = 0.f, prho = 0.f;
     if (valid) {
-        const float4 x = ld4(q.x + vb + i), p = ld4((q.mp ? q.mp : q.p) + vb + i);
+        const MbPack<W> x = mb_ld<W>(q.x + vb + i), p = mb_ld<W>((q.mp ? q.mp : q.p) + vb + i);
         if (half) {
-            st4(q.x + vb + i, x.x + alpha * p.x, x.y + alpha * p.y, x.z + alpha * p.z, x.w + alpha * p.w);
+            mb_st<W>(q.x + vb + i, mb_map<W>([&](int e) { return x[e] + alpha * p[e]; }));
         } else {
-            const float4 sv = ld4((q.sbuf ? q.sbuf : q.r) + vb + i), t = ld4(q.t + vb + i), w = ld4(q.rw + vb + i);
-            const float4 sd = q.ms ? ld4(q.ms + vb + i) : sv;
-            st4(q.x + vb + i, x.x + alpha * p.x + omega * sd.x, x.y + alpha * p.y + omega * sd.y, x.z + alpha * p.z + omega * sd.z,
-                x.w + alpha * p.w + omega * sd.w);
-            const mb_real r0 = sv.x - omega * (t.x - mt), r1 = sv.y - omega * (t.y - mt), r2 = sv.z - omega * (t.z - mt), r3 = sv.w - omega * (t.w - mt);
-            st4(q.r + vb + i, r0, r1, r2, r3);
-            prr = r0 * r0 + r1 * r1 + r2 * r2 + r3 * r3;
-            prho = w.x * r0 + w.y * r1 + w.z * r2 + w.w * r3;
+            const MbPack<W> sv = mb_ld<W>((q.sbuf ? q.sbuf : q.r) + vb + i), t = mb_ld<W>(q.t + vb + i), w = mb_ld<W>(q.rw + vb + i);
+            const MbPack<W> sd = q.ms ? mb_ld<W>(q.ms + vb + i) : sv;
+            // the two forms have always rounded this sum differently -- the one-cell kernel adds the whole step fma(alpha, p, omega s)
+            // to x, the four-cell kernel its halves one after the other (two FMAs onto x) -- and each keeps its bits
+            mb_st<W>(q.x + vb + i, mb_map<W>([&](int e) { return W == 1 ? x[e] + fma(alpha, p[e], omega * sd[e]) : x[e] + alpha * p[e] + omega * sd[e]; }));
+            const MbPack<W> r = mb_map<W>([&](int e) { return sv[e] - omega * (t[e] - mt); });
+            mb_st<W>(q.r + vb + i, r);
+            prr = mb_dot<W>(r, r);
+            prho = mb_dot<W>(w, r);
         }
     }
     if (half) return;
@@ -476,160 +423,70 @@ __global__ __launch_bounds__(FG_BLOCK) void k_mbb_x4(MbDev D, MbSolve q, int it)
     { const int sl[2] = {A_RR, A_RHO + ((it + 1) & 1)}; const mb_real vv[2] = {sums[0], sums[1]}; const bool on[2] = {true, true}; mb_acc_tail<2>(a, sl, vv, on); }
 }
 
-// ---- p and v in one launch: p_new = r + beta (p - omega (v - mean v)) for the own cell and, recomputed from r, p, v of the
-// previous iteration, for its neighbours; v_new = A p_new.  p and v ping-pong between two buffers each (the neighbours' old
+// ---- p and v in one launch: p_new = r + beta (p - omega (v - mean v)) for the own cells and, recomputed from r, p, v of the
+// previous iteration, for their neighbours; v_new = A p_new.  p and v ping-pong between two buffers each (the neighbours' old
 // values must survive the launch); the convergence test on r, the breakdown restart and the leader's bookkeeping are k_mbb_p's.
-template <int DIMS>
+template <int DIMS, int W>
 __global__ __launch_bounds__(FG_BLOCK) void k_mbb_pv(MbDev D, MbSolve q, int it) {
-    MB_SYS
-    constexpr int F = 2 * DIMS;
-    const int f = flag_ld(q.flags + (sys));
-    if (f == 4) { if (leader) flag_st(q.flags + (sys), 1); return; }
-    if (f != 0) return;
-    const mb_real crit = mb_rms(acc_ld(a + (A_RR)), N);
-    if (!(crit >= q.tol)) { if (leader) mb_mark(q, sys, crit, (it == 0 && q.it_base == 0) ? -1 : it + q.it_base); return; }
-    if (leader) {
-        acc_st(a + (A_SS), 0.0); acc_st(a + (A_TS), 0.0); acc_st(a + (A_TT), 0.0); acc_st(a + (A_ST), 0.0);
-        q.info[sys].final_residual = crit;
-        q.info[sys].used_iterations = it + q.it_base - 1;
-    }
-    MB_BETA
-    const mb_real mv = (q.project && it > 0) ? (mb_real)(acc_ld(a + (A_SV + 2 * ((it + 1) & 1))) / (double)N) : 0.f;
-    mb_real part = 0.f, psum = 0.f;
-    if (valid) {
-        const mb_real* __restrict__ r = q.r + vb;
-        const mb_real* __restrict__ pp = q.p_prev + vb;
-        const mb_real* __restrict__ vp = q.v_prev + vb;
-        // it == 0: p = r was laid down by the initialisation in the CURRENT p buffer
-        auto pnew = [&](int c) -> mb_real {
-            if (it == 0) return q.p[vb + c];
-            if (restart) return r[c];
-            return r[c] + beta * (pp[c] - omega * (vp[c] - mv));
-        };
-        const mb_real pc = pnew(i);
-        mb_real y = q.diag[(size_t)b * N + i] * pc;
-#pragma unroll
-        for (int ff = 0; ff < F; ++ff) {
-            const int n = D.nbr[(size_t)ff * N + i];
-            if (n >= 0) y += q.off[((size_t)b * F + ff) * N + i] * pnew(n);
-        }
-        mb_real rwv = q.rw[vb + i];
-        if (restart) { rwv = r[i]; q.rw[vb + i] = rwv; }
-        if (it > 0) q.p[vb + i] = pc;
-        q.v[vb + i] = y;
-        part = rwv * y;
-        psum = y;
-    }
-    mb_real sums[2] = {part, psum};
-    mb_block_sums<2>(sums, lds);
-    { const int sl[2] = {A_RV, A_SV + 2 * (it & 1)}; const mb_real vv[2] = {sums[0], sums[1]}; const bool on[2] = {true, (bool)q.project}; mb_acc_tail<2>(a, sl, vv, on); }
-}
-template <int DIMS>
-__global__ __launch_bounds__(FG_BLOCK) void k_mbb_pv4(MbDev D, MbSolve q, int it) {
-    MB_SYS4
-    const int f = flag_ld(q.flags + (sys));
-    if (f == 4) { if (leader) flag_st(q.flags + (sys), 1); return; }
-    if (f != 0) return;
-    const mb_real crit = mb_rms(acc_ld(a + (A_RR)), N);
-    if (!(crit >= q.tol)) { if (leader) mb_mark(q, sys, crit, (it == 0 && q.it_base == 0) ? -1 : it + q.it_base); return; }
-    if (leader) {
-        acc_st(a + (A_SS), 0.0); acc_st(a + (A_TS), 0.0); acc_st(a + (A_TT), 0.0); acc_st(a + (A_ST), 0.0);
-        q.info[sys].final_residual = crit;
-        q.info[sys].used_iterations = it + q.it_base - 1;
-    }
-    MB_BETA
-    const mb_real mv = (q.project && it > 0) ? (mb_real)(acc_ld(a + (A_SV + 2 * ((it + 1) & 1))) / (double)N) : 0.f;
+    MB_SYSW(W)
+    const MbPHead h = mbb_p_head(q, sys, a, N, leader, it);
+    if (!h.go) return;
+    const mb_real mv = mbb_prev_mean_v(q, a, N, it, true);
     mb_real part = 0.f, psum = 0.f;
     if (valid) {
         const mb_real* __restrict__ r = q.r + vb;
         const mb_real* __restrict__ pp = q.p_prev + vb;
         const mb_real* __restrict__ vp = q.v_prev + vb;
         const mb_real* __restrict__ pcur = q.p + vb;
-        mb_real pc[4];
-        if (it == 0) {
-            const float4 p4 = ld4(pcur + i);
-            pc[0] = p4.x; pc[1] = p4.y; pc[2] = p4.z; pc[3] = p4.w;
-        } else {
-            const float4 r4 = ld4(r + i);
-            if (restart) { pc[0] = r4.x; pc[1] = r4.y; pc[2] = r4.z; pc[3] = r4.w; }
+        const mb_real beta = h.beta, omega = h.omega;
+        const bool restart = h.restart;
+        MbPack<W> pc;
+        if (it == 0) pc = mb_ld<W>(pcur + i);   // p = r was laid down by the initialisation in the CURRENT p buffer
+        else {
+            const MbPack<W> r4 = mb_ld<W>(r + i);
+            if (restart) pc = r4;
             else {
-                const float4 p4 = ld4(pp + i), v4 = ld4(vp + i);
-                pc[0] = r4.x + beta * (p4.x - omega * (v4.x - mv)); pc[1] = r4.y + beta * (p4.y - omega * (v4.y - mv));
-                pc[2] = r4.z + beta * (p4.z - omega * (v4.z - mv)); pc[3] = r4.w + beta * (p4.w - omega * (v4.w - mv));
+                const MbPack<W> p4 = mb_ld<W>(pp + i), v4 = mb_ld<W>(vp + i);
+                pc = mb_map<W>([&](int e) { return r4[e] + beta * (p4[e] - omega * (v4[e] - mv)); });
             }
         }
-        mb_real y[4];
-        mb_spmv4_core<DIMS>(D, q, b, i, pc, [=](int n) -> mb_real {
+        const MbPack<W> y = mb_apply<DIMS, W>(D, q, b, i, pc, [=](int n) -> mb_real {
             if (it == 0) return pcur[n];
             if (restart) return r[n];
             return r[n] + beta * (pp[n] - omega * (vp[n] - mv));
-        }, y);
-        float4 w = ld4(q.rw + vb + i);
-        if (restart) { w = make_float4(pc[0], pc[1], pc[2], pc[3]); st4(q.rw + vb + i, w.x, w.y, w.z, w.w); }
-        if (it > 0) st4(q.p + vb + i, pc[0], pc[1], pc[2], pc[3]);
-        st4(q.v + vb + i, y[0], y[1], y[2], y[3]);
-        part = w.x * y[0] + w.y * y[1] + w.z * y[2] + w.w * y[3];
-        psum = y[0] + y[1] + y[2] + y[3];
+        });
+        MbPack<W> w = mb_ld<W>(q.rw + vb + i);
+        if (restart) { w = pc; mb_st<W>(q.rw + vb + i, w); }
+        if (it > 0) mb_st<W>(q.p + vb + i, pc);
+        mb_st<W>(q.v + vb + i, y);
+        part = mb_dot<W>(w, y);
+        psum = mb_sum<W>(y);
     }
     mb_real sums[2] = {part, psum};
     mb_block_sums<2>(sums, lds);
     { const int sl[2] = {A_RV, A_SV + 2 * (it & 1)}; const mb_real vv[2] = {sums[0], sums[1]}; const bool on[2] = {true, (bool)q.project}; mb_acc_tail<2>(a, sl, vv, on); }
 }
 
-// ---- s and t in one launch (five kernels per iteration -> four): s = r - alpha (v - mean v) for the own cell and, recomputed
-// from r and v, for its neighbours; t = A s; s goes to its own buffer (q.sbuf) because the neighbours' r must survive the launch.
-// The convergence-on-s test (bicgstab_solver_kernel.cu:305-329) needs the complete s.s and moves into k_mbb_x.  At 16 x 46.7 k
-// cells every one of these kernels is launch-bound (5-9 us); not used with the right-preconditioned recurrence (t = A M s).
-template <int DIMS>
+// ---- s and t in one launch (five kernels per iteration -> four): s = r - alpha (v - mean v) for the own cells and, recomputed
+// from r and v, for their neighbours; t = A s; s goes to its own buffer (q.sbuf) because the neighbours' r must survive the launch.
+// The convergence-on-s test (bicgstab_solver_kernel.cu:305-329) needs the complete s.s and moves into k_mbb_x (mbb_half).  At
+// 16 x 46.7 k cells every one of these kernels is launch-bound (5-9 us); not used with the right-preconditioned recurrence (t = A M s).
+template <int DIMS, int W>
 __global__ __launch_bounds__(FG_BLOCK) void k_mbb_st(MbDev D, MbSolve q, int it) {
-    MB_SYS
-    constexpr int F = 2 * DIMS;
+    MB_SYSW(W)
     if (flag_ld(q.flags + (sys)) != 0) return;
-    const mb_real alpha_raw = (mb_real)(acc_ld(a + (A_RHOE + (it & 1))) / acc_ld(a + (A_RV)));
-    const mb_real alpha = isfinite(alpha_raw) ? alpha_raw : 0.f;   // rw.v == 0: see MB_BETA
-    if (leader) { sc_st(q.sc + (sys * 2), alpha); acc_st(a + (A_RHO + ((it + 1) & 1)), 0.0); acc_st(a + (A_RR), 0.0); acc_st(a + (A_SV + 2 * ((it + 1) & 1)), 0.0); }
-    const mb_real mv = q.project ? (mb_real)(acc_ld(a + (A_SV + 2 * (it & 1))) / (double)N) : 0.f;
+    const MbSHead h = mbb_s_head(q, sys, a, N, leader, it);
     mb_real pss = 0.f, pts = 0.f, ptt = 0.f, pst = 0.f;
     if (valid) {
         const mb_real* __restrict__ r = q.r + vb;
         const mb_real* __restrict__ v = q.v + vb;
-        const mb_real sv = r[i] - alpha * (v[i] - mv);
-        mb_real t = q.diag[(size_t)b * N + i] * sv;
-#pragma unroll
-        for (int f = 0; f < F; ++f) {
-            const int n = D.nbr[(size_t)f * N + i];
-            if (n >= 0) t += q.off[((size_t)b * F + f) * N + i] * (r[n] - alpha * (v[n] - mv));
-        }
-        q.sbuf[vb + i] = sv;
-        q.t[vb + i] = t;
-        pss = sv * sv; pts = t * sv; ptt = t * t; pst = t;
-    }
-    mb_real sums[4] = {pss, pts, ptt, pst};
-    mb_block_sums<4>(sums, lds);
-    { const int sl[4] = {A_SS, A_TS, A_TT, A_ST}; const mb_real vv[4] = {sums[0], sums[1], sums[2], sums[3]}; const bool on[4] = {true, true, true, (bool)q.project}; mb_acc_tail<4>(a, sl, vv, on); }
-}
-template <int DIMS>
-__global__ __launch_bounds__(FG_BLOCK) void k_mbb_st4(MbDev D, MbSolve q, int it) {
-    MB_SYS4
-    if (flag_ld(q.flags + (sys)) != 0) return;
-    const mb_real alpha_raw = (mb_real)(acc_ld(a + (A_RHOE + (it & 1))) / acc_ld(a + (A_RV)));
-    const mb_real alpha = isfinite(alpha_raw) ? alpha_raw : 0.f;
-    if (leader) { sc_st(q.sc + (sys * 2), alpha); acc_st(a + (A_RHO + ((it + 1) & 1)), 0.0); acc_st(a + (A_RR), 0.0); acc_st(a + (A_SV + 2 * ((it + 1) & 1)), 0.0); }
-    const mb_real mv = q.project ? (mb_real)(acc_ld(a + (A_SV + 2 * (it & 1))) / (double)N) : 0.f;
-    mb_real pss = 0.f, pts = 0.f, ptt = 0.f, pst = 0.f;
-    if (valid) {
-        const mb_real* __restrict__ r = q.r + vb;
-        const mb_real* __restrict__ v = q.v + vb;
-        const float4 r4 = ld4(r + i), v4 = ld4(v + i);
-        const mb_real sv[4] = {r4.x - alpha * (v4.x - mv), r4.y - alpha * (v4.y - mv), r4.z - alpha * (v4.z - mv), r4.w - alpha * (v4.w - mv)};
-        mb_real t[4];
-        mb_spmv4_core<DIMS>(D, q, b, i, sv, [r, v, alpha, mv](int n) { return r[n] - alpha * (v[n] - mv); }, t);
-        st4(q.sbuf + vb + i, sv[0], sv[1], sv[2], sv[3]);
-        st4(q.t + vb + i, t[0], t[1], t[2], t[3]);
-        pss = sv[0] * sv[0] + sv[1] * sv[1] + sv[2] * sv[2] + sv[3] * sv[3];
-        pts = t[0] * sv[0] + t[1] * sv[1] + t[2] * sv[2] + t[3] * sv[3];
-        ptt = t[0] * t[0] + t[1] * t[1] + t[2] * t[2] + t[3] * t[3];
-        pst = t[0] + t[1] + t[2] + t[3];
+        const mb_real alpha = h.alpha, mv = h.mv;
+        const MbPack<W> r4 = mb_ld<W>(r + i), v4 = mb_ld<W>(v + i);
+        const MbPack<W> sv = mb_map<W>([&](int e) { return r4[e] - alpha * (v4[e] - mv); });
+        const MbPack<W> t = mb_apply<DIMS, W>(D, q, b, i, sv, [r, v, alpha, mv](int n) { return r[n] - alpha * (v[n] - mv); });
+        mb_st<W>(q.sbuf + vb + i, sv);
+        mb_st<W>(q.t + vb + i, t);
+        pss = mb_dot<W>(sv, sv); pts = mb_dot<W>(t, sv); ptt = mb_dot<W>(t, t); pst = mb_sum<W>(t);
     }
     mb_real sums[4] = {pss, pts, ptt, pst};
     mb_block_sums<4>(sums, lds);
@@ -704,40 +561,31 @@ __global__ __launch_bounds__(FG_BLOCK) void k_ml_restrict(MlDev M, const mb_real
     if (a < M.n4 && row == 0) { M.r4[(size_t)sys * M.n4 + a] = sum; M.r4c[(size_t)sys * 4 * M.n8 + M.pos4[a]] = sum; }
 }
 // The restriction fused with the vector update that feeds it (the preconditioned BiCGStab applies M to p and to s right after
-// forming them): the thread of an aggregate forms p (k_mbb_p4's update, convergence test and leader bookkeeping) or s (k_mbb_s4's)
-// at its own cells, stores it and sums it -- one launch instead of two, twice per iteration.  The cells of an aggregate are a
-// partition of the mesh (checked in fg_mb_set_multilevel), so every cell is written exactly once.
+// forming them): the thread of an aggregate forms p (k_mbb_p's update, behind the same mbb_p_head) or s (k_mbb_s's, behind
+// mbb_s_head) at its own cells, stores it and sums it -- one launch instead of two, twice per iteration.  The cells of an aggregate
+// are a partition of the mesh (checked in fg_mb_set_multilevel), so every cell is written exactly once.
 template <int DIMS>
 __global__ __launch_bounds__(FG_BLOCK) void k_ml_restrict_p(MbDev D, MbSolve q, MlDev M, int it) {
     const int tq = blockIdx.x * FG_BLOCK + threadIdx.x, ag = tq >> 2, row = tq & 3, sys = q.sys_map ? q.sys_map[blockIdx.y] : (int)blockIdx.y, N = D.N;
     const bool leader = (blockIdx.x == 0 && threadIdx.x == 0);
     const size_t vb = (size_t)sys * N;
     FgDacc* a = q.acc + (size_t)sys * MB_ACC;
-    const int f = flag_ld(q.flags + (sys));
-    if (f == 4) { if (leader) flag_st(q.flags + (sys), 1); return; }
-    if (f != 0) return;
-    const mb_real crit = mb_rms(acc_ld(a + (A_RR)), N);
-    if (!(crit >= q.tol)) { if (leader) mb_mark(q, sys, crit, (it == 0 && q.it_base == 0) ? -1 : it + q.it_base); return; }
-    if (leader) {
-        acc_st(a + (A_SS), 0.0); acc_st(a + (A_TS), 0.0); acc_st(a + (A_TT), 0.0); acc_st(a + (A_ST), 0.0);
-        q.info[sys].final_residual = crit;
-        q.info[sys].used_iterations = it + q.it_base - 1;
-    }
-    MB_BETA
-    const mb_real mv = (q.project && it > 0) ? (mb_real)(acc_ld(a + (A_SV + 2 * ((it + 1) & 1))) / (double)N) : 0.f;
+    const MbPHead h = mbb_p_head(q, sys, a, N, leader, it);
+    if (!h.go) return;
+    const mb_real mv = mbb_prev_mean_v(q, a, N, it, true);
     mb_real sum = 0.f;
     if (ag < M.n4) {
         const uint2 rc = M.rect4[ag];
-        const int w = rc.y & 255, h = (rc.y >> 8) & 255, stride = rc.y >> 16;
-        for (int dy = row; dy < h; dy += 4)
+        const int w = rc.y & 255, hh = (rc.y >> 8) & 255, stride = rc.y >> 16;
+        for (int dy = row; dy < hh; dy += 4)
             for (int dx = 0; dx < w; ++dx) {
                 const size_t c = vb + rc.x + dy * stride + dx;
                 mb_real pv;
                 if (it == 0) pv = q.p[c];                       // p = r was laid down by the initialisation
                 else {
                     const mb_real r = q.r[c];
-                    if (restart) { q.rw[c] = r; pv = r; }
-                    else pv = r + beta * (q.p[c] - omega * (q.v[c] - mv));
+                    if (h.restart) { q.rw[c] = r; pv = r; }
+                    else pv = r + h.beta * (q.p[c] - h.omega * (q.v[c] - mv));
                     q.p[c] = pv;
                 }
                 sum += pv;
@@ -754,18 +602,15 @@ __global__ __launch_bounds__(FG_BLOCK) void k_ml_restrict_s(MbDev D, MbSolve q, 
     FgDacc* a = q.acc + (size_t)sys * MB_ACC;
     __shared__ mb_real lds[16];
     if (flag_ld(q.flags + (sys)) != 0) return;
-    const mb_real alpha_raw = (mb_real)(acc_ld(a + (A_RHOE + (it & 1))) / acc_ld(a + (A_RV)));
-    const mb_real alpha = isfinite(alpha_raw) ? alpha_raw : 0.f;   // rw.v == 0: see MB_BETA
-    if (leader) { sc_st(q.sc + (sys * 2), alpha); acc_st(a + (A_RHO + ((it + 1) & 1)), 0.0); acc_st(a + (A_RR), 0.0); acc_st(a + (A_SV + 2 * ((it + 1) & 1)), 0.0); }
-    const mb_real mv = q.project ? (mb_real)(acc_ld(a + (A_SV + 2 * (it & 1))) / (double)N) : 0.f;
+    const MbSHead h = mbb_s_head(q, sys, a, N, leader, it);
     mb_real part = 0.f, sum = 0.f;
     if (ag < M.n4) {
         const uint2 rc = M.rect4[ag];
-        const int w = rc.y & 255, h = (rc.y >> 8) & 255, stride = rc.y >> 16;
-        for (int dy = row; dy < h; dy += 4)
+        const int w = rc.y & 255, hh = (rc.y >> 8) & 255, stride = rc.y >> 16;
+        for (int dy = row; dy < hh; dy += 4)
             for (int dx = 0; dx < w; ++dx) {
                 const size_t c = vb + rc.x + dy * stride + dx;
-                const mb_real sv = q.r[c] - alpha * (q.v[c] - mv);
+                const mb_real sv = q.r[c] - h.alpha * (q.v[c] - h.mv);
                 q.r[c] = sv;
                 part += sv * sv;
                 sum += sv;
@@ -1463,7 +1308,7 @@ MlDev mb_ml_dev(const fg_mb_state* s) {
     M.cnt4 = s->ml_cnt4; M.g8 = s->ml_g8;
     return M;
 }
-// fused = 0: z = M in.  1 / 2: `in` is q.p / q.r and its update (k_mbb_p4 / k_mbb_s4) happens inside the restriction
+// fused = 0: z = M in.  1 / 2: `in` is q.p / q.r and its update (k_mbb_p / k_mbb_s) happens inside the restriction
 // (k_ml_restrict_p / _s), iteration index `it`.
 // the per-env scale of the multilevel preconditioner (sum_i P_ii / geom_diag_sum) for the matrix diagonal `diag`
 void mb_ml_scale(fg_mb_state* s, const mb_real* diag, hipStream_t st) {
@@ -1580,9 +1425,9 @@ int mb_bicgstab(fg_mb_state* s, const mb_real* dt, const mb_real* diag, const mb
     // a refined solve that has not converged after 1500 iterations is not going to: hand over to the caller's CG fallback
     // instead of spending the reference's 5000 (one hard env would stall the whole batch)
     if (refine && max_iterations > 1500) max_iterations = 1500;
-    // Four-cells-per-thread kernels (k_mbb_*4) whenever the cell count allows; FG_MB_BICG_VEC4 (read at create) is the test /
+    // Four-cells-per-thread kernels (k_mbb_*<DIMS, 4>) whenever the cell count allows; FG_MB_BICG_VEC4 (read at create) is the test /
     // harness switch between the two kernel forms, not a workaround: the failures it once bisected were exact breakdowns of the
-    // recurrence (MB_BETA), deterministic per kernel form because the two forms sum in different orders.
+    // recurrence (mbb_p_head), deterministic per kernel form because the two forms sum in different orders.
     const int vec_mask = (n % 4 != 0) ? 0 : (s->dbg_vec_mask & 31);
     const dim3 grid4((n / 4 + FG_BLOCK - 1) / FG_BLOCK, nsys);
     auto keep_best = [&](int first) {
@@ -1663,27 +1508,31 @@ int mb_bicgstab(fg_mb_state* s, const mb_real* dt, const mb_real* diag, const mb
         MbSolve qi = q;
         dim3 gi = grid, gi4 = grid4;
         if (n_map > 0) { qi.sys_map = s->sys_map_dev; qi.n_map = n_map; gi.y = gi4.y = (unsigned)n_map; }
-        MB_DISPATCH(s, {   // vec_mask: which of the five kernels run in their four-cell form
-            if (fused_pv) {
-                if ((vec_mask & 3) == 3) hipLaunchKernelGGL(k_mbb_pv4<DIMS>, gi4, blk, 0, st, s->dev, qi, li); else hipLaunchKernelGGL(k_mbb_pv<DIMS>, gi, blk, 0, st, s->dev, qi, li);
-            } else {
-            if (ml_fused) {}   // p is formed inside the restriction (mb_ml_apply below)
-            else if (vec_mask & 1) hipLaunchKernelGGL(k_mbb_p4<DIMS>, gi4, blk, 0, st, s->dev, qi, li); else hipLaunchKernelGGL(k_mbb_p<DIMS>, gi, blk, 0, st, s->dev, qi, li);
-            if (ilu) mb_ilu_apply(s, qi, qi.p, s->ilu_mp, st);
-            else if (ml) mb_ml_apply(s, qi, qi.p, s->ml_mp, st, ml_fused ? 1 : 0, li);
-            if (vec_mask & 2) hipLaunchKernelGGL(k_mbb_v4<DIMS>, gi4, blk, 0, st, s->dev, qi, li); else hipLaunchKernelGGL(k_mbb_v<DIMS>, gi, blk, 0, st, s->dev, qi, li);
+        // one kernel role: in its four-cell form over gi4 when vec_mask has all of `bits` (1 p, 2 v, 4 s, 8 t, 16 x; a fused kernel
+        // needs both of its halves), else in its one-cell form over gi
+#define MBB_LAUNCH(K, bits)                                                                                        \
+        do {                                                                                                       \
+            if ((vec_mask & (bits)) == (bits)) hipLaunchKernelGGL((K<DIMS, 4>), gi4, blk, 0, st, s->dev, qi, li);  \
+            else hipLaunchKernelGGL((K<DIMS, 1>), gi, blk, 0, st, s->dev, qi, li);                                 \
+        } while (0)
+        MB_DISPATCH(s, {
+            if (fused_pv) MBB_LAUNCH(k_mbb_pv, 3);
+            else {
+                if (!ml_fused) MBB_LAUNCH(k_mbb_p, 1);   // (ml_fused: p is formed inside the restriction, mb_ml_apply below)
+                if (ilu) mb_ilu_apply(s, qi, qi.p, s->ilu_mp, st);
+                else if (ml) mb_ml_apply(s, qi, qi.p, s->ml_mp, st, ml_fused ? 1 : 0, li);
+                MBB_LAUNCH(k_mbb_v, 2);
             }
-            if (fused_st) {
-                if ((vec_mask & 12) == 12) hipLaunchKernelGGL(k_mbb_st4<DIMS>, gi4, blk, 0, st, s->dev, qi, li); else hipLaunchKernelGGL(k_mbb_st<DIMS>, gi, blk, 0, st, s->dev, qi, li);
-            } else {
-                if (ml_fused) {}   // s is formed inside the restriction
-                else if (vec_mask & 4) hipLaunchKernelGGL(k_mbb_s4<DIMS>, gi4, blk, 0, st, s->dev, qi, li); else hipLaunchKernelGGL(k_mbb_s<DIMS>, gi, blk, 0, st, s->dev, qi, li);
+            if (fused_st) MBB_LAUNCH(k_mbb_st, 12);
+            else {
+                if (!ml_fused) MBB_LAUNCH(k_mbb_s, 4);   // (ml_fused: s is formed inside the restriction)
                 if (ilu) mb_ilu_apply(s, qi, qi.r, s->ilu_ms, st);
                 else if (ml) mb_ml_apply(s, qi, qi.r, s->ml_ms, st, ml_fused ? 2 : 0, li);
-                if (vec_mask & 8) hipLaunchKernelGGL(k_mbb_t4<DIMS>, gi4, blk, 0, st, s->dev, qi, li); else hipLaunchKernelGGL(k_mbb_t<DIMS>, gi, blk, 0, st, s->dev, qi, li);
+                MBB_LAUNCH(k_mbb_t, 8);
             }
-            if (vec_mask & 16) hipLaunchKernelGGL(k_mbb_x4<DIMS>, gi4, blk, 0, st, s->dev, qi, li); else hipLaunchKernelGGL(k_mbb_x<DIMS>, gi, blk, 0, st, s->dev, qi, li);
+            MBB_LAUNCH(k_mbb_x, 16);
         });
+#undef MBB_LAUNCH
         if (it + 1 >= next_poll || it + 1 == max_iterations) {
             next_poll = it + 1 + (it < 20 ? 2 : 10);   // long (pressure) solves: fewer host round trips
             FgPollOut po = fg_poll_next(&s->poll);

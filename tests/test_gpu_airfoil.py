@@ -143,7 +143,7 @@ def test_multilevel_trial_of_the_pressure_bicgstab(monkeypatch):
 
 def test_restriction_fused_with_the_vector_updates_is_the_separate_launches(monkeypatch):
     """Preconditioned pressure BiCGStab: p and s formed inside the restriction of the multilevel preconditioner
-    (k_ml_restrict_p / _s, the default up to 32 systems) against k_mbb_p4 / _s4 followed by k_ml_restrict (FG_MB_ML_FUSE=0, what
+    (k_ml_restrict_p / _s, the default up to 32 systems) against k_mbb_p / _s followed by k_ml_restrict (FG_MB_ML_FUSE=0, what
     larger batches run).  Same p and s; the restricted sums and s.s are added in another grouping (four threads per aggregate, one per
     row), so the two runs agree to the solver tolerance, with the same number of attempts and nearly the same iteration counts."""
     out = {}
