@@ -35,6 +35,7 @@ from ..simulation.domain import Domain
 from ..simulation.resample import UniformResampler
 from ..simulation.simulation import Simulation
 from . import obs_extraction as X
+from .flow_statistics import FlowStatisticsMixin
 from .fluid_env import FluidEnv, is_per_env, per_env_parameter
 
 RBC_2D_DEFAULT_CONFIG = {
@@ -81,8 +82,9 @@ def _nusselt_factor(rayleigh_number, prandtl_number, like: torch.Tensor):
     return t.reshape((t.numel(),) + (1,) * (like.dim() - 1))
 
 
-class RBCEnvBase(FluidEnv):
+class RBCEnvBase(FlowStatisticsMixin, FluidEnv):
     _supports_marl = True
+    _flow_stats_scalar = True           # start_flow_statistics records the temperature as channel T
     _resolution_scale_y: float = 2.0
     _non_uniform_grid_base = 1.02
     _H: float = 1.0
@@ -394,6 +396,8 @@ class RBCEnvBase(FluidEnv):
         for _ in range(self._n_sim_steps):
             if not self._sim.single_step():
                 raise RuntimeError("simulation step failed")
+            if self._flow_stats is not None:
+                self._record_flow_sample()
         nu = self.compute_global_nusselt()
         obs = self._get_global_obs()
         return obs, self.nu_ref - nu, False, {"nusselt": nu}

@@ -37,6 +37,7 @@ from ..simulation import grids
 from ..simulation.domain import Domain
 from ..simulation.simulation import Simulation
 from . import obs_extraction as X
+from .flow_statistics import FlowStatisticsMixin
 from .fluid_env import FluidEnv, refuse_per_env
 
 SMALL_TCF_3D_DEFAULT_CONFIG = {
@@ -72,7 +73,7 @@ def reichardt_profile(y_plus: torch.Tensor) -> torch.Tensor:
     return (1 / k) * torch.log(1 + k * y_plus) + 7.8 * (1 - torch.exp(-y11) - y11 * torch.exp(-y_plus / 3))
 
 
-class TCF3DBottomEnv(FluidEnv):
+class TCF3DBottomEnv(FlowStatisticsMixin, FluidEnv):
     _supports_marl = True
     _actuation = "bottom"
     _scale_actions = True
@@ -354,12 +355,19 @@ class TCF3DBottomEnv(FluidEnv):
             if not self._sim.single_step():
                 raise RuntimeError("simulation step failed")
             b, t = self._get_wall_stress()
+            if self._flow_stats is not None:
+                self._record_flow_sample()
             tb.append(b)
             tt.append(t)
         tau_bottom, tau_top = torch.stack(tb).mean(dim=0), torch.stack(tt).mean(dim=0)
         tau_total = 0.5 * (tau_bottom + tau_top)
         info = {"wall_stress": tau_total, "wall_stress_bottom": tau_bottom, "wall_stress_top": tau_top}
         return (self._get_global_obs() if want_obs else None), self._get_reward(tau_total, tau_bottom), False, info
+
+    def start_flow_statistics(self, order: int = 2, every: int = 1) -> None:
+        super().start_flow_statistics(order=order, every=every)
+        e = np.asarray(self._block.edges[1], np.float64)                              # walls at y = -1, +1: u_wall(), y+
+        self._flow_stats.set_wall_units(0.5 * (e[1:] + e[:-1]), self._nu)
 
     @property
     def id(self) -> str:

@@ -452,6 +452,31 @@ int fg_dacc_device_sum(const double* values_host, int64_t n, double plain, int32
 #define FG_FIELD_SUMMARY_WORK_BYTES 128
 int fg_field_summary(const fg_real* field, int32_t batch, int32_t channels, int64_t n, int32_t channel, void* workspace,
                      double* moments, int64_t* counts, double lo, double width, int32_t nbins, uint64_t* hist, void* stream);
+/* ---- online plane-averaged flow statistics (csrc/fg_planestats.hip; both libraries, handle-free) ------------------------------
+ * One sample of PlaneMoments (simulation/plane_stats.py; the reference's WelfordOnlineParallel_Torch, CovarianceOnlineParallel_Torch
+ * and MultivariateMomentsOnlineParallel_Torch, online_statistics.py:31-266, 419-787): for every row (env, y) the mean over (z, x) of K
+ * channels and the sums of products of their deviations from that mean, merged into running accumulators on the device in ONE launch.
+ *   channels[k]      HOST table of K device pointers: cell (env, z, y, x) of channel k is
+ *                    channels[k][env * batch_stride[k] + (z * ny + y) * nx + x]; batch_stride (HOST table, in reals, each >= nz * ny * nx)
+ *                    lets a caller pass the component slices of velocity [B, d, (Z,) Y, X], pressure [B, 1, ...] and passiveScalar in
+ *                    place.  Both tables are copied into the kernel arguments: no device table, no host-to-device copy.  2-D: nz = 1.
+ *   K                3..5 (u,v,p / u,v,w,p or u,v,p,T / u,v,w,p,T: the kernel does not care what a channel means)
+ *   order            2..4
+ *   n [batch], mean [batch][ny][K], central [batch][ny][M]: fp64 device accumulators, updated in place.  central holds, in this order,
+ *                    the K (K + 1) / 2 sums of d_i d_j for i <= j (i ascending, then j), for order >= 3 the K sums of d_i^3, for order 4
+ *                    the K sums of d_i^4.  The sample's mean and central sums are taken in fp64 (two passes over the plane) and merged
+ *                    by the pairwise update of Pebay et al. 2016 with delta = mean_sample - mean_running; an env with n = 0 stores the
+ *                    sample.  n advances by nz * nx per call.
+ *   tickets [batch]  64-bit device counters that order the one write of n[env] after the reads of it by the env's rows.  The caller
+ *                    zeroes n and tickets together before the first sample (mean and central need no initialisation) and keeps ny.
+ * One workgroup (one wave for planes of up to 1024 cells) owns a row and reduces in a fixed tree: no floating-point atomics, so a row's
+ * result depends neither on the launch order nor on the other envs nor on `batch`, and repeats bit for bit.  16-byte loads are used
+ * when nx and every batch stride are multiples of 16 bytes / sizeof(fg_real) and every channel pointer is 16-byte aligned, scalar loads
+ * otherwise.  A non-finite cell makes the sample, hence the accumulators, of its row NaN (all channels) and nothing else.  Asynchronous
+ * on `stream`; nothing returns to the host.  FG_ERR_INVALID_ARG: a null pointer, K outside 3..5, order outside 2..4, a non-positive
+ * extent, a batch stride below nz * ny * nx, nz * nx above 2^30 or batch * ny above 2^31 - 1. */
+int fg_plane_moments(const fg_real* const* channels, const int64_t* batch_stride, int32_t K, int32_t batch, int32_t nz, int32_t ny,
+                     int32_t nx, int32_t order, double* n, double* mean, double* central, uint64_t* tickets, void* stream);
 int fg_profile_enable(fg_handle h, int on);
 int fg_profile_kinds(void);
 const char* fg_profile_kind_name(int kind);
