@@ -1,0 +1,297 @@
+// Online wavenumber spectra of wall-parallel planes (PlaneSpectra, simulation/plane_spectra.py): for every slab (env, channel k,
+// listed plane j) the unnormalised DFT of the real plane [nz, nx] over (z, x) -- over x alone for 2-D fields, nz = 1 -- and the
+// running sums of |u^| and |u^|^2 of the modes kz < max(nz / 2, 1), kx < nx / 2.
+//
+// The reference keeps these with PSDOnline_Torch (pict/data/online_statistics.py:269-416; fed by VelocityStats.record_vel_stats,
+// TCF_tools.py:445-459, 1491-1500): an index_select copy of the planes, a full complex fftn in HBM, an abs, a slice, a mean and a
+// merge, all of it twice for the mirrored planes.  Here one sample of a batch is ONE launch that reads every selected plane once
+// and reads and writes the accumulators once.
+//
+// Ownership and order: one workgroup of four waves owns a slab and holds its nz x nx/2 half spectrum in LDS.
+//   x pass   a wave takes batches of row PAIRS (z, z + 1): the two real rows are the real and imaginary part of one complex row,
+//            transformed by a Stockham autosort FFT (radix 4, then one radix 2) in the wave's own two work buffers and split into
+//            the two rows' spectra, of which only kx < nx / 2 is kept (real input; the Nyquist column is not recorded).  As many
+//            pairs go into one batch as the work buffer holds, so that short rows still fill the 64 lanes.
+//   z pass   a wave copies batches of columns kx out of the slab into its work buffers, transforms them the same way and writes
+//            kz < nz / 2 back to the columns it took, which no other wave touches.
+//   sums     the 256 threads walk the kept modes in memory order and add |u^| and |u^|^2 (evaluated in fp64) to the accumulators:
+//            one thread per element, no atomics.  A slab's result depends on nothing but its cells and the extents.
+// LDS layout: slab rows are nx / 2 + 1 complex apart.  The z pass reads and writes the slab along z with consecutive lanes on
+// consecutive z; at a row pitch of nx / 2 complex (a power of two, >= one 256-byte bank row from nx = 64 on) every lane of a group
+// would hit the same banks, with one complex of padding consecutive z are 2 (fp32) / 4 (fp64) banks apart and the 32 / 16 lanes
+// of an 8- / 16-byte access group cover the 64 banks once.
+// Twiddles: (cos, sin)(2 pi k / max(nx, nz)) from sincospi of the exact argument 2 k / max(nx, nz) in fp64, rounded to fg_real once
+// per workgroup into LDS; a shorter axis reads the table with a stride.
+#include <float.h>
+
+#include <mutex>
+
+#include "fg_internal.h"
+
+namespace {
+
+constexpr int PS_MAX_K = 5;
+constexpr int PS_MAX_PLANES = 32;
+constexpr int PS_WAVES = 4;
+constexpr int PS_VEC = FG_F64 ? 2 : 4;            // reals per 16-byte load
+constexpr int PS_LDS_LIMIT = 160 * 1024;          // what a workgroup may declare on gfx950
+#if FG_F64
+typedef double2 ps_c;
+#else
+typedef float2 ps_c;
+#endif
+constexpr fg_real PS_REAL_MAX = FG_F64 ? (fg_real)DBL_MAX : (fg_real)FLT_MAX;
+constexpr int PS_WORK_MIN =2048 / (int)sizeof(ps_c);   // a work buffer holds at least 2 KB: 256 (fp32) / 128 (fp64) complex
+
+struct PsArgs {
+    const fg_real* ch[PS_MAX_K];          // by value, as in fg_plane_moments
+    long long bstride[PS_MAX_K];
+    int planes[PS_MAX_PLANES];
+    long long zstride;                    // ny * nx
+    int K, n_planes, nz, nx, lnz, lnx;    // ln = log2
+    int pitch, work, nmax, vec;           // slab row pitch and work buffer length in complex; max(nx, nz); 16-byte loads
+    double* amp;
+    double* power;
+};
+
+// what the kernel declares for extents (nz, nx): twiddles, slab, two work buffers per wave, the non-finite flag
+inline long long ps_work(int nz, int nx) { const int m = nx > nz ? nx : nz; return m > PS_WORK_MIN ? m : PS_WORK_MIN; }
+inline long long ps_lds_bytes(int nz, int nx) {
+    const long long nmax = nx > nz ? nx : nz;
+    return (nmax + (long long)nz * (nx / 2 + 1) + 2 * PS_WAVES * ps_work(nz, nx)) * (long long)sizeof(ps_c) + 16;
+}
+
+__device__ __forceinline__ void ps_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __forceinline__ ps_c ps_make(fg_real x, fg_real y) { ps_c r; r.x = x; r.y = y; return r; }
+__device__ __forceinline__ ps_c ps_cmul(ps_c a, ps_c w) { return ps_make(a.x * w.x - a.y * w.y, a.x * w.y + a.y * w.x); }
+
+// Forward Stockham autosort FFT of total / N sequences of N = 2^ln complex that lie one after the other in x (the arithmetic of
+// fgfft::stockham, fg_fftrow.h, for fg_real and a run-time length): radix 4 while the remaining length allows it, then one radix-2
+// stage; ping-pongs between x and y and returns the buffer that holds the result.  tw: W^k at tw[k * tws].
+__device__ __forceinline__ ps_c* ps_stockham(ps_c* x, ps_c* y, const ps_c* __restrict__ tw, int ln, int tws, int total, int lane) {
+    const int N = 1 << ln;
+    auto twid = [&](int k) { ps_c w = tw[(k & (N - 1)) * tws]; w.y = -w.y; return w; };
+    int sft = 0, lrem = ln;
+    while (lrem >= 2) {
+        const int sm = (1 << sft) - 1, nq = N >> 2;
+        for (int i = lane; i < (total >> 2); i += 64) {
+            const int s = i >> (ln - 2), t = i & (nq - 1);
+            const int q = t & sm, ps = t - q;
+            const ps_c* xs = x + (s << ln);
+            const ps_c a0 = xs[t], a1 = xs[t + nq], a2 = xs[t + 2 * nq], a3 = xs[t + 3 * nq];
+            const ps_c r1 = ps_make(a1.y, -a1.x), r3 = ps_make(a3.y, -a3.x);
+            const ps_c b0 = ps_make(a0.x + a1.x + a2.x + a3.x, a0.y + a1.y + a2.y + a3.y);
+            const ps_c c1 = ps_make(a0.x + r1.x - a2.x - r3.x, a0.y + r1.y - a2.y - r3.y);
+            const ps_c c2 = ps_make(a0.x - a1.x + a2.x - a3.x, a0.y - a1.y + a2.y - a3.y);
+            const ps_c c3 = ps_make(a0.x - r1.x - a2.x + r3.x, a0.y - r1.y - a2.y + r3.y);
+            ps_c* o = y + (s << ln) + 4 * ps + q;
+            o[0] = b0;
+            o[1 << sft] = ps_cmul(c1, twid(ps));
+            o[2 << sft] = ps_cmul(c2, twid(2 * ps));
+            o[3 << sft] = ps_cmul(c3, twid(3 * ps));
+        }
+        ps_wave_sync();
+        ps_c* tmp = x; x = y; y = tmp;
+        sft += 2; lrem -= 2;
+    }
+    if (lrem == 1) {
+        const int sm = (1 << sft) - 1, nh = N >> 1;
+        for (int i = lane; i < (total >> 1); i += 64) {
+            const int s = i >> (ln - 1), t = i & (nh - 1);
+            const int q = t & sm, ps = t - q;
+            const ps_c u = x[(s << ln) + t], v = x[(s << ln) + t + nh];
+            ps_c* o = y + (s << ln) + 2 * ps + q;
+            o[0] = ps_make(u.x + v.x, u.y + v.y);
+            o[1 << sft] = ps_cmul(ps_make(u.x - v.x, u.y - v.y), twid(ps));
+        }
+        ps_wave_sync();
+        ps_c* tmp = x; x = y; y = tmp;
+    }
+    return x;
+}
+
+// VEC consecutive reals of the rows at pa and pb (pb == nullptr: a 2-D field, the imaginary row is 0) as VEC complex at dst
+template <int VEC>
+__device__ __forceinline__ bool ps_stage(const fg_real* pa, const fg_real* pb, ps_c* dst) {
+    fg_real va[VEC], vb[VEC];
+    if constexpr (VEC == 1) {
+        va[0] = pa[0];
+        vb[0] = pb ? pb[0] : (fg_real)0;
+    } else {
+#if FG_F64
+        const double2 qa = *reinterpret_cast<const double2*>(pa);
+        const double2 qb = pb ? *reinterpret_cast<const double2*>(pb) : make_double2(0.0, 0.0);
+        va[0] = qa.x; va[1] = qa.y; vb[0] = qb.x; vb[1] = qb.y;
+#else
+        const float4 qa = *reinterpret_cast<const float4*>(pa);
+        const float4 qb = pb ? *reinterpret_cast<const float4*>(pb) : make_float4(0.f, 0.f, 0.f, 0.f);
+        va[0] = qa.x; va[1] = qa.y; va[2] = qa.z; va[3] = qa.w; vb[0] = qb.x; vb[1] = qb.y; vb[2] = qb.z; vb[3] = qb.w;
+#endif
+    }
+    bool bad = false;
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+        dst[e] = ps_make(va[e], vb[e]);
+        bad = bad || !(FG_FABS(va[e]) <= PS_REAL_MAX) || !(FG_FABS(vb[e]) <= PS_REAL_MAX);
+    }
+    return bad;
+}
+
+// one kernel for both load widths (a.vec is uniform): the arithmetic, hence the bits, cannot depend on how the rows were loaded
+__global__ __launch_bounds__(256) void k_plane_spectra(PsArgs a) {
+    extern __shared__ __align__(16) unsigned char ps_lds[];
+    ps_c* tw = reinterpret_cast<ps_c*>(ps_lds);
+    ps_c* slab = tw + a.nmax;
+    ps_c* work = slab + a.nz * a.pitch;
+    int* s_bad = reinterpret_cast<int*>(work + 2 * PS_WAVES * a.work);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int sid = blockIdx.x;
+    const int j = sid % a.n_planes, k = (sid / a.n_planes) % a.K, b = sid / (a.n_planes * a.K);
+    const fg_real* base = a.ch[k] + (long long)b * a.bstride[k] + (long long)a.planes[j] * a.nx;
+    const int nz = a.nz, nx = a.nx, hx = nx >> 1, lhx = a.lnx - 1, pitch = a.pitch;
+    ps_c* x = work + wave * 2 * a.work;
+    ps_c* y = x + a.work;
+
+    for (int i = tid; i < a.nmax; i += 256) {
+        double s, c;
+        sincospi(2.0 * (double)i / (double)a.nmax, &s, &c);
+        tw[i] = ps_make((fg_real)c, (fg_real)s);
+    }
+    if (tid == 0) *s_bad = 0;
+    __syncthreads();
+
+    // ---- x pass: row pairs (2 q, 2 q + 1), nb pairs per batch
+    {
+        const int npairs = nz > 1 ? nz >> 1 : 1;
+        int nb = a.work >> a.lnx;
+        nb = nb < npairs ? nb : npairs;
+        const int lvec = a.vec ? (PS_VEC == 4 ? 2 : 1) : 0, lnxv = a.lnx - lvec;
+        const int tws = a.nmax >> a.lnx;
+        bool bad = false;
+        for (int q0 = wave * nb; q0 < npairs; q0 += PS_WAVES * nb) {
+            for (int i = lane; i < (nb << lnxv); i += 64) {
+                const int s = i >> lnxv, xe = (i & ((1 << lnxv) - 1)) << lvec;
+                const fg_real* pa = base + (long long)(2 * (q0 + s)) * a.zstride + xe;
+                const fg_real* pb = nz > 1 ? pa + a.zstride : nullptr;
+                ps_c* dst = x + (s << a.lnx) + xe;
+                bad = (a.vec ? ps_stage<PS_VEC>(pa, pb, dst) : ps_stage<1>(pa, pb, dst)) || bad;
+            }
+            ps_wave_sync();
+            const ps_c* X = ps_stockham(x, y, tw, a.lnx, tws, nb << a.lnx, lane);
+            // the spectrum of z = a + i b split into those of the rows:  A = (Z_k + conj Z_{n-k}) / 2,  B = (Z_k - conj Z_{n-k}) / 2i
+            for (int i = lane; i < (nb << lhx); i += 64) {
+                const int s = i >> lhx, kx = i & (hx - 1);
+                const ps_c Z = X[(s << a.lnx) + kx], M = X[(s << a.lnx) + ((nx - kx) & (nx - 1))];
+                ps_c* row = slab + (2 * (q0 + s)) * pitch + kx;
+                row[0] = ps_make((fg_real)0.5 * (Z.x + M.x), (fg_real)0.5 * (Z.y - M.y));
+                if (nz > 1) row[pitch] = ps_make((fg_real)0.5 * (Z.y + M.y), (fg_real)-0.5 * (Z.x - M.x));
+            }
+            ps_wave_sync();      // the work buffers are staged again by the next batch
+        }
+        if (bad) *s_bad = 1;
+    }
+    __syncthreads();
+
+    // ---- z pass: columns kx < nx / 2, nbc columns per batch; consecutive lanes on consecutive z (see the layout note above)
+    if (nz > 1) {
+        const int hz = nz >> 1, lhz = a.lnz - 1;
+        int nbc = a.work >> a.lnz;
+        nbc = nbc < hx ? nbc : hx;
+        const int tws = a.nmax >> a.lnz;
+        for (int c0 = wave * nbc; c0 < hx; c0 += PS_WAVES * nbc) {
+            for (int i = lane; i < (nbc << a.lnz); i += 64) x[i] = slab[(i & (nz - 1)) * pitch + c0 + (i >> a.lnz)];
+            ps_wave_sync();
+            const ps_c* X = ps_stockham(x, y, tw, a.lnz, tws, nbc << a.lnz, lane);
+            for (int i = lane; i < (nbc << lhz); i += 64) {
+                const int c = i >> lhz, kz = i & (hz - 1);
+                slab[kz * pitch + c0 + c] = X[(c << a.lnz) + kz];
+            }
+            ps_wave_sync();
+        }
+        __syncthreads();
+    }
+
+    // ---- sums: element (kz, kx) of this slab's accumulators belongs to one thread
+    const int kept = (nz > 1 ? nz >> 1 : 1) << lhx;
+    const bool poisoned = *s_bad != 0;       // a non-finite cell anywhere in the slab: every mode of it is NaN, by rule and not by luck
+    double* ga = a.amp + (long long)sid * kept;
+    double* gp = a.power + (long long)sid * kept;
+    for (int i = tid; i < kept; i += 256) {
+        const ps_c v = slab[(i >> lhx) * pitch + (i & (hx - 1))];
+        const double re = (double)v.x, im = (double)v.y;
+        double p = re * re + im * im, m = sqrt(p);
+        if (poisoned) p = m = (double)NAN;
+        ga[i] += m;
+        gp[i] += p;
+    }
+}
+
+// kernels that declare more than 64 KB of dynamic LDS opt in once per device
+bool ps_opt_in() {
+    static std::mutex mu;
+    static int state[64];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { (void)hipGetLastError(); return false; }
+    std::lock_guard<std::mutex> lock(mu);
+    if (state[dev] == 0) {
+        state[dev] = 1;
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_plane_spectra), hipFuncAttributeMaxDynamicSharedMemorySize, PS_LDS_LIMIT) !=
+            hipSuccess) {
+            (void)hipGetLastError();
+            state[dev] = -1;
+        }
+    }
+    return state[dev] == 1;
+}
+
+inline int ps_log2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
+
+}  // namespace
+
+extern "C" int fg_plane_spectra(const fg_real* const* channels, const int64_t* batch_stride, int32_t K, int32_t batch, int32_t nz,
+                                int32_t ny, int32_t nx, const int32_t* planes, int32_t n_planes, double* amp, double* power,
+                                void* stream) {
+    FG_REQUIRE(channels && batch_stride && planes, FG_ERR_INVALID_ARG, "fg_plane_spectra: null channel, stride or plane table");
+    FG_REQUIRE(amp && power, FG_ERR_INVALID_ARG, "fg_plane_spectra: null accumulator (amp, power)");
+    FG_REQUIRE(K >= 1 && K <= PS_MAX_K, FG_ERR_INVALID_ARG, "fg_plane_spectra: K must be 1..5");
+    FG_REQUIRE(n_planes >= 1 && n_planes <= PS_MAX_PLANES, FG_ERR_INVALID_ARG, "fg_plane_spectra: n_planes must be 1..32");
+    FG_REQUIRE(batch > 0 && nz > 0 && ny > 0 && nx > 0, FG_ERR_INVALID_ARG, "fg_plane_spectra: batch, nz, ny, nx must be positive");
+    FG_REQUIRE((long long)batch * K * n_planes <= 0x7fffffffLL, FG_ERR_INVALID_ARG, "fg_plane_spectra: batch * K * n_planes too large for one launch");
+    PsArgs a;
+    for (int j = 0; j < PS_MAX_PLANES; ++j) {
+        a.planes[j] = 0;
+        if (j >= n_planes) continue;
+        FG_REQUIRE(planes[j] >= 0 && planes[j] < ny, FG_ERR_INVALID_ARG, "fg_plane_spectra: plane index outside [0, ny)");
+        a.planes[j] = planes[j];
+    }
+    const long long field = (long long)nz * ny * nx;
+    bool vec = nx % PS_VEC == 0;
+    for (int k = 0; k < PS_MAX_K; ++k) {
+        a.ch[k] = nullptr; a.bstride[k] = 0;
+        if (k >= K) continue;
+        FG_REQUIRE(channels[k], FG_ERR_INVALID_ARG, "fg_plane_spectra: null channel pointer");
+        FG_REQUIRE(batch_stride[k] >= field, FG_ERR_INVALID_ARG, "fg_plane_spectra: batch stride smaller than nz * ny * nx");
+        a.ch[k] = channels[k]; a.bstride[k] = (long long)batch_stride[k];
+        vec = vec && ((uintptr_t)channels[k] % 16 == 0) && (batch_stride[k] % PS_VEC == 0);
+    }
+    FG_REQUIRE(nx >= 8 && nx <= 512 && (nx & (nx - 1)) == 0, FG_ERR_UNSUPPORTED, "fg_plane_spectra: nx must be a power of two in 8..512");
+    FG_REQUIRE(nz == 1 || (nz >= 4 && nz <= 256 && (nz & (nz - 1)) == 0), FG_ERR_UNSUPPORTED,
+               "fg_plane_spectra: nz must be 1 or a power of two in 4..256");
+    const long long lds = ps_lds_bytes(nz, nx);
+    FG_REQUIRE(lds <= PS_LDS_LIMIT, FG_ERR_UNSUPPORTED,
+               FG_F64 ? "fg_plane_spectra: the slab nz x (nx / 2 + 1) complex doubles with its work buffers must fit in 160 KB of LDS"
+                      : "fg_plane_spectra: the slab nz x (nx / 2 + 1) complex floats with its work buffers must fit in 160 KB of LDS");
+    a.zstride = (long long)ny * nx;
+    a.K = K; a.n_planes = n_planes; a.nz = nz; a.nx = nx; a.lnz = ps_log2(nz); a.lnx = ps_log2(nx);
+    a.pitch = nx / 2 + 1; a.work = (int)ps_work(nz, nx); a.nmax = nx > nz ? nx : nz; a.vec = vec ? 1 : 0;
+    a.amp = amp; a.power = power;
+    FG_REQUIRE(ps_opt_in(), FG_ERR_HIP, "fg_plane_spectra: the device refused 160 KB of LDS per workgroup");
+    hipLaunchKernelGGL(k_plane_spectra, dim3((unsigned)(batch * K * n_planes)), dim3(256), (size_t)lds, (hipStream_t)stream, a);
+    FG_HIP_CHECK(hipGetLastError());
+    return FG_OK;
+}

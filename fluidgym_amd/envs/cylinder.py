@@ -27,6 +27,7 @@ from ..simulation.resample_mb import MultiBlockResampler, MultiBlockResampler3D
 from .. import spaces
 from .channel import jet_profile
 from .cylinder_grid import BOTTOM, LEFT, RIGHT, TOP, build_domain, extrude_mesh, make_vortex_street_mesh
+from .flow_statistics import FlowStatisticsMixin
 from .fluid_env import FluidEnv, is_per_env, per_env_parameter, refuse_per_env
 from .forces import WallRing
 
@@ -42,7 +43,7 @@ CYLINDER_ROT_2D_DEFAULT_CONFIG = dict(CYLINDER_JET_2D_DEFAULT_CONFIG)
 ONCHIP_PCG_MAX_CELLS = 24 * 1024   # the multilevel-preconditioned on-chip CG (2-D): fg_mb_onchip.hip OC_L2_CELLS
 
 
-class CylinderEnvBase(FluidEnv):
+class CylinderEnvBase(FlowStatisticsMixin, FluidEnv):      # (multi-block: the statistics refuse with NotImplementedError)
     _supports_marl = False
     _action_smoothing_alpha: float = 0.1
     H: float = 4.1

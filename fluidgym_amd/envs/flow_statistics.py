@@ -1,10 +1,13 @@
 """``start_flow_statistics`` / ``stop_flow_statistics`` of the wall-bounded single-block envs (TCF, RBC): one sample of the
 plane-averaged statistics (``simulation/plane_stats.PlaneMoments``) after every ``every``-th sim step, on the GPU, while active.
-The reference records them from its run scripts with ``VelocityStats.record_vel_stats`` (``TCF_tools.py:1480-1507``)."""
+The reference records them from its run scripts with ``VelocityStats.record_vel_stats`` (``TCF_tools.py:1480-1507``).
+``start_flow_spectra`` / ``stop_flow_spectra`` do the same, independently, for the wavenumber spectra of chosen wall-parallel
+planes (``simulation/plane_spectra.PlaneSpectra``; the reference's ``PSD_planes``, ``TCF_tools.py:445-459, 1491-1500``)."""
 from __future__ import annotations
 
-from typing import Optional
+from typing import Optional, Sequence
 
+from ..simulation.plane_spectra import PlaneSpectra, check_extents
 from ..simulation.plane_stats import PlaneMoments
 
 
@@ -13,18 +16,27 @@ class FlowStatisticsMixin:
     _flow_stats_every: int = 1
     _flow_stats_tick: int = 0
     _flow_stats_scalar: bool = False                # whether the passive scalar is recorded as channel T
+    _flow_spectra: Optional[PlaneSpectra] = None    # None (the default): the step path does nothing for the spectra
+    _flow_spectra_every: int = 1
+    _flow_spectra_tick: int = 0
 
     def start_flow_statistics(self, order: int = 2, every: int = 1) -> None:
         """Start a fresh record of moments up to ``order``; a sample is taken after every ``every``-th sim step of ``step()``."""
         if getattr(self, "_domain", None) is None:
             raise RuntimeError("start_flow_statistics: reset() the env first (the domain does not exist yet)")
-        if self._domain.getNumBlocks() != 1:
+        if self._flow_blocks() != 1:
             raise NotImplementedError("flow statistics need a single-block domain")
         if int(every) < 1:
             raise ValueError(f"every must be at least 1, got {every}")
-        channels = ("u", "v") + (("w",) if self._ndims == 3 else ()) + ("p",) + (("T",) if self._flow_stats_scalar else ())
-        self._flow_stats = PlaneMoments(channels, order)
+        self._flow_stats = PlaneMoments(self._flow_channels(), order)
         self._flow_stats_every, self._flow_stats_tick = int(every), 0
+
+    def _flow_blocks(self) -> int:
+        count = getattr(self._domain, "getNumBlocks", None)
+        return count() if count is not None else len(self._domain.blocks)       # (the multi-block domain keeps a list)
+
+    def _flow_channels(self):
+        return ("u", "v") + (("w",) if self._ndims == 3 else ()) + ("p",) + (("T",) if self._flow_stats_scalar else ())
 
     def stop_flow_statistics(self) -> PlaneMoments:
         """Stop recording and hand out the record (on the GPU; its accessors, ``pooled()`` and ``save`` read it back)."""
@@ -40,3 +52,35 @@ class FlowStatisticsMixin:
             return
         blk = self._domain.getBlock(0)
         self._flow_stats.update(blk.velocity, blk.pressure, blk.passiveScalar if self._flow_stats_scalar else None)
+
+    def start_flow_spectra(self, planes: Sequence[int], every: int = 1, symmetric: bool = True) -> None:
+        """Start a fresh record of the wavenumber spectra of the rows ``planes`` (and, ``symmetric``, of their mirror images) of
+        the channels of the moments; a sample is taken after every ``every``-th sim step of ``step()``."""
+        if getattr(self, "_domain", None) is None:
+            raise RuntimeError("start_flow_spectra: reset() the env first (the domain does not exist yet)")
+        if self._flow_blocks() != 1:
+            raise NotImplementedError("flow spectra need a single-block domain")
+        if int(every) < 1:
+            raise ValueError(f"every must be at least 1, got {every}")
+        vel = self._domain.getBlock(0).velocity
+        nz, ny, nx = ((1,) + tuple(int(s) for s in vel.shape[2:]))[-3:]
+        check_extents(nz, nx, vel.element_size(), "start_flow_spectra")
+        spectra = PlaneSpectra(self._flow_channels(), planes, symmetric)
+        spectra.plane_table(ny)                            # planes outside the grid are refused here, not at the first sample
+        self._flow_spectra = spectra
+        self._flow_spectra_every, self._flow_spectra_tick = int(every), 0
+
+    def stop_flow_spectra(self) -> PlaneSpectra:
+        """Stop recording and hand out the record (on the GPU; its accessors, ``pooled()`` and ``save`` read it back)."""
+        if self._flow_spectra is None:
+            raise RuntimeError("stop_flow_spectra: no spectra are being recorded")
+        spectra, self._flow_spectra = self._flow_spectra, None
+        return spectra
+
+    def _record_spectra_sample(self) -> None:
+        """Called after a sim step while spectra are active."""
+        self._flow_spectra_tick += 1
+        if self._flow_spectra_tick % self._flow_spectra_every:
+            return
+        blk = self._domain.getBlock(0)
+        self._flow_spectra.update(blk.velocity, blk.pressure, blk.passiveScalar if self._flow_stats_scalar else None)

@@ -398,6 +398,8 @@ class RBCEnvBase(FlowStatisticsMixin, FluidEnv):
                 raise RuntimeError("simulation step failed")
             if self._flow_stats is not None:
                 self._record_flow_sample()
+            if self._flow_spectra is not None:
+                self._record_spectra_sample()
         nu = self.compute_global_nusselt()
         obs = self._get_global_obs()
         return obs, self.nu_ref - nu, False, {"nusselt": nu}

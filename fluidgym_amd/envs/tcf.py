@@ -357,6 +357,8 @@ class TCF3DBottomEnv(FlowStatisticsMixin, FluidEnv):
             b, t = self._get_wall_stress()
             if self._flow_stats is not None:
                 self._record_flow_sample()
+            if self._flow_spectra is not None:
+                self._record_spectra_sample()
             tb.append(b)
             tt.append(t)
         tau_bottom, tau_top = torch.stack(tb).mean(dim=0), torch.stack(tt).mean(dim=0)

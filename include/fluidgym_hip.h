@@ -477,6 +477,27 @@ int fg_field_summary(const fg_real* field, int32_t batch, int32_t channels, int6
  * extent, a batch stride below nz * ny * nx, nz * nx above 2^30 or batch * ny above 2^31 - 1. */
 int fg_plane_moments(const fg_real* const* channels, const int64_t* batch_stride, int32_t K, int32_t batch, int32_t nz, int32_t ny,
                      int32_t nx, int32_t order, double* n, double* mean, double* central, uint64_t* tickets, void* stream);
+/* ---- online wavenumber spectra of wall-parallel planes (csrc/fg_planespectra.hip; both libraries, handle-free) -----------------
+ * One sample of PlaneSpectra (simulation/plane_spectra.py; the reference's PSDOnline_Torch, online_statistics.py:269-416): for every
+ * slab (env, channel k, listed plane j) the unnormalised DFT of the real plane [nz, nx] over (z, x) -- the convention of
+ * numpy.fft.fftn; over x alone when nz = 1 -- of which |u^| is ADDED to amp and |u^|^2 to power, in ONE launch.
+ *   channels, batch_stride, K   as for fg_plane_moments (HOST tables, copied into the kernel arguments), K = 1..5
+ *   planes           HOST table of n_planes = 1..32 row indices in [0, ny); duplicates are allowed; a caller that wants the mirrored
+ *                    plane lists ny - 1 - p as one more entry
+ *   amp, power       fp64 device arrays [batch][K][n_planes][max(nz / 2, 1)][nx / 2] of running SUMS: modes kz < max(nz / 2, 1),
+ *                    kx < nx / 2 (the reference's fft_slice: the Nyquist mode is not recorded).  The caller zeroes both before the
+ *                    first sample and counts the samples itself, so that merging two records is an addition.
+ * One workgroup owns a slab: its rows are read once (16-byte loads when nx and every batch stride are multiples of 16 bytes /
+ * sizeof(fg_real) and every channel pointer is 16-byte aligned), both transform passes run in LDS on fg_real, |u^| and |u^|^2 are
+ * evaluated in fp64, and every accumulator element is read and written by exactly one thread: no floating-point atomics, a slab's
+ * result depends only on its cells and the extents and repeats bit for bit.  A non-finite cell makes both accumulators of its slab
+ * NaN (every mode) and touches nothing else.  Asynchronous on `stream`; nothing returns to the host.
+ * FG_ERR_UNSUPPORTED (before any launch): nx not a power of two in 8..512, nz neither 1 nor a power of two in 4..256, or a slab that
+ * does not fit in LDS: (max(nx, nz) + nz (nx / 2 + 1) + 8 max(nx, nz, 2048 / c)) c + 16 bytes above 160 KB, c = 2 sizeof(fg_real).
+ * 128 x 128 fits in both libraries.  FG_ERR_INVALID_ARG: a null pointer, K outside 1..5, n_planes outside 1..32, a plane index
+ * outside [0, ny), a non-positive extent, a batch stride below nz * ny * nx, batch * K * n_planes above 2^31 - 1. */
+int fg_plane_spectra(const fg_real* const* channels, const int64_t* batch_stride, int32_t K, int32_t batch, int32_t nz, int32_t ny,
+                     int32_t nx, const int32_t* planes, int32_t n_planes, double* amp, double* power, void* stream);
 int fg_profile_enable(fg_handle h, int on);
 int fg_profile_kinds(void);
 const char* fg_profile_kind_name(int kind);
