@@ -2,11 +2,17 @@
 plane-averaged statistics (``simulation/plane_stats.PlaneMoments``) after every ``every``-th sim step, on the GPU, while active.
 The reference records them from its run scripts with ``VelocityStats.record_vel_stats`` (``TCF_tools.py:1480-1507``).
 ``start_flow_spectra`` / ``stop_flow_spectra`` do the same, independently, for the wavenumber spectra of chosen wall-parallel
-planes (``simulation/plane_spectra.PlaneSpectra``; the reference's ``PSD_planes``, ``TCF_tools.py:445-459, 1491-1500``)."""
+planes (``simulation/plane_spectra.PlaneSpectra``; the reference's ``PSD_planes``, ``TCF_tools.py:445-459, 1491-1500``), and
+``start_flow_budgets`` / ``stop_flow_budgets`` for the Reynolds-stress budgets of 3-D channels
+(``simulation/plane_budgets.PlaneBudgets``; the reference's ``TurbulentEnergyBudgetsOnlineParallel_Torch``,
+``TCF_tools.py:438-443, 1512-1516``)."""
 from __future__ import annotations
 
 from typing import Optional, Sequence
 
+import numpy as np
+
+from ..simulation.plane_budgets import PlaneBudgets
 from ..simulation.plane_spectra import PlaneSpectra, check_extents
 from ..simulation.plane_stats import PlaneMoments
 
@@ -19,6 +25,9 @@ class FlowStatisticsMixin:
     _flow_spectra: Optional[PlaneSpectra] = None    # None (the default): the step path does nothing for the spectra
     _flow_spectra_every: int = 1
     _flow_spectra_tick: int = 0
+    _flow_budgets: Optional[PlaneBudgets] = None    # None (the default): the step path does nothing for the budgets
+    _flow_budgets_every: int = 1
+    _flow_budgets_tick: int = 0
 
     def start_flow_statistics(self, order: int = 2, every: int = 1) -> None:
         """Start a fresh record of moments up to ``order``; a sample is taken after every ``every``-th sim step of ``step()``."""
@@ -84,3 +93,39 @@ class FlowStatisticsMixin:
             return
         blk = self._domain.getBlock(0)
         self._flow_spectra.update(blk.velocity, blk.pressure, blk.passiveScalar if self._flow_stats_scalar else None)
+
+    def start_flow_budgets(self, every: int = 1, forcing: Optional[bool] = None) -> None:
+        """Start a fresh record of the Reynolds-stress budgets; a sample is taken after every ``every``-th sim step of ``step()``.
+        The coordinates are the block's cell centres, periodic x / z faces wrap, ``forcing`` defaults to whether the block has a
+        velocity source."""
+        if getattr(self, "_domain", None) is None:
+            raise RuntimeError("start_flow_budgets: reset() the env first (the domain does not exist yet)")
+        if self._flow_blocks() != 1:
+            raise NotImplementedError("flow budgets need a single-block domain")
+        if self._ndims != 3:
+            raise NotImplementedError("flow budgets need a 3-D domain")
+        if int(every) < 1:
+            raise ValueError(f"every must be at least 1, got {every}")
+        blk = self._domain.getBlock(0)
+        if forcing is None:
+            forcing = blk.velocitySource is not None
+        elif forcing and blk.velocitySource is None:
+            raise ValueError("start_flow_budgets: forcing=True needs a block with a velocity source")
+        x, y, z = (0.5 * (np.asarray(e, np.float64)[1:] + np.asarray(e, np.float64)[:-1]) for e in blk.edges)
+        self._flow_budgets = PlaneBudgets(x, y, z, forcing=bool(forcing), wrap=(not blk.isFixed("-x"), not blk.isFixed("-z")))
+        self._flow_budgets_every, self._flow_budgets_tick = int(every), 0
+
+    def stop_flow_budgets(self) -> PlaneBudgets:
+        """Stop recording and hand out the record (on the GPU; its accessors, ``pooled()`` and ``save`` read it back)."""
+        if self._flow_budgets is None:
+            raise RuntimeError("stop_flow_budgets: no budgets are being recorded")
+        budgets, self._flow_budgets = self._flow_budgets, None
+        return budgets
+
+    def _record_budgets_sample(self) -> None:
+        """Called after a sim step while budgets are active."""
+        self._flow_budgets_tick += 1
+        if self._flow_budgets_tick % self._flow_budgets_every:
+            return
+        blk = self._domain.getBlock(0)
+        self._flow_budgets.update(blk.velocity, blk.pressure, blk.velocitySource if self._flow_budgets.forcing else None)

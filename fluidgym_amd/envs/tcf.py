@@ -359,6 +359,8 @@ class TCF3DBottomEnv(FlowStatisticsMixin, FluidEnv):
                 self._record_flow_sample()
             if self._flow_spectra is not None:
                 self._record_spectra_sample()
+            if self._flow_budgets is not None:
+                self._record_budgets_sample()
             tb.append(b)
             tt.append(t)
         tau_bottom, tau_top = torch.stack(tb).mean(dim=0), torch.stack(tt).mean(dim=0)
@@ -370,6 +372,11 @@ class TCF3DBottomEnv(FlowStatisticsMixin, FluidEnv):
         super().start_flow_statistics(order=order, every=every)
         e = np.asarray(self._block.edges[1], np.float64)                              # walls at y = -1, +1: u_wall(), y+
         self._flow_stats.set_wall_units(0.5 * (e[1:] + e[:-1]), self._nu)
+
+    def start_flow_budgets(self, every: int = 1, forcing=None) -> None:
+        super().start_flow_budgets(every=every, forcing=forcing)
+        e = np.asarray(self._block.edges[1], np.float64)
+        self._flow_budgets.set_wall_units(0.5 * (e[1:] + e[:-1]), self._nu)
 
     @property
     def id(self) -> str:

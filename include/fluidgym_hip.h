@@ -477,6 +477,38 @@ int fg_field_summary(const fg_real* field, int32_t batch, int32_t channels, int6
  * extent, a batch stride below nz * ny * nx, nz * nx above 2^30 or batch * ny above 2^31 - 1. */
 int fg_plane_moments(const fg_real* const* channels, const int64_t* batch_stride, int32_t K, int32_t batch, int32_t nz, int32_t ny,
                      int32_t nx, int32_t order, double* n, double* mean, double* central, uint64_t* tickets, void* stream);
+/* ---- online Reynolds-stress budgets of channel flows (csrc/fg_planebudgets.hip; both libraries, handle-free) -------------------
+ * One sample of PlaneBudgets (simulation/plane_budgets.py; the reference's TurbulentEnergyBudgetsOnlineParallel_Torch,
+ * online_statistics.py:790-1268): for every row (env, y) the means over (z, x) of K channels -- u, v, w, the three pressure gradients,
+ * the nine velocity gradients, with forcing the three source components -- and the M sums of products of their deviations that the
+ * budget terms need, merged into running accumulators on the device in ONE launch; the gradients are formed in registers.
+ *   fields[f]        HOST table of n_fields device pointers in the order u, v, w, p (n_fields = 4: K = 15, M = 43) or
+ *                    u, v, w, p, s_x, s_y, s_z (n_fields = 7: K = 18, M = 52); cell (env, z, y, x) of field f is
+ *                    fields[f][env * batch_stride[f] + (z * ny + y) * nx + x], as for fg_plane_moments: the component slices of
+ *                    velocity [B, 3, Z, Y, X], pressure [B, 1, Z, Y, X] and velocitySource are read in place.  Both tables are copied
+ *                    into the kernel arguments.
+ *   x [nx], y [ny], z [nz]   fp64 DEVICE arrays of cell-centre coordinates (strictly monotonic).  The gradient along an axis is
+ *                    (f[i + 1] - f[i - 1]) / |pos[i + 1] - pos[i - 1]|; beyond an end the ghost position is mirrored (2 pos[0] - pos[1],
+ *                    2 pos[n - 1] - pos[n - 2]) and the ghost value is 0 (the reference's _data_grad(borders="ZERO"), on y the wall).
+ *   wrap_x, wrap_z   non-zero: the ghost VALUE on that axis is the cell at the other end (a periodic axis); the ghost distance stays the
+ *                    mirrored one, exact on a uniform axis.  Zero: the reference's zero padding.
+ *   n [batch], mean [batch][ny][K], central [batch][ny][M]: fp64 device accumulators, updated in place.  Channels: 0..2 u, v, w;
+ *                    3..5 dp/dx, dp/dy, dp/dz; 6 + 3 k + i = d u_i / d x_k; 15..17 s_x, s_y, s_z.  central holds, in this order, the 6 sums
+ *                    d_i d_j of (u, v, w) (i <= j), the 10 sums d_i d_j d_k (i <= j <= k), the 9 sums u_i' (dp/dx_j)' (i, then j), with
+ *                    forcing the 9 sums u_i' s_j', then for k = 0..2 the 6 second-order sums of (d_k u, d_k v, d_k w).  Two fp64 passes
+ *                    per sample and the pairwise update of Pebay et al. 2016 with delta = mean_sample - mean_running, mixed third-order
+ *                    sums included; an env with n = 0 stores the sample.  n advances by nz * nx per call.
+ *   tickets [batch]  as for fg_plane_moments: zeroed with n before the first sample.
+ * Ownership and order are those of fg_plane_moments (one workgroup, or one wave for planes of up to 1024 cells, per row; fixed tree; no
+ * floating-point atomics): a row's result depends only on its cells, its two neighbour rows, the coordinates and the extents, and
+ * repeats bit for bit.  16-byte loads when nx and every batch stride are multiples of 16 bytes / sizeof(fg_real) and every field pointer
+ * is 16-byte aligned, scalar loads otherwise.  A non-finite value in any channel of a row (a non-finite cell of row y reaches rows y - 1
+ * and y + 1 through d/dy) makes the sample, hence the accumulators, of that row NaN and nothing else.  Asynchronous on `stream`; nothing
+ * returns to the host.  FG_ERR_INVALID_ARG: a null pointer, n_fields neither 4 nor 7, batch <= 0, an extent below 2, a batch stride
+ * below nz * ny * nx, nz * nx above 2^30 or batch * ny above 2^31 - 1. */
+int fg_plane_budgets(const fg_real* const* fields, const int64_t* batch_stride, int32_t n_fields, int32_t batch, int32_t nz, int32_t ny,
+                     int32_t nx, const double* x, const double* y, const double* z, int32_t wrap_x, int32_t wrap_z, double* n,
+                     double* mean, double* central, uint64_t* tickets, void* stream);
 /* ---- online wavenumber spectra of wall-parallel planes (csrc/fg_planespectra.hip; both libraries, handle-free) -----------------
  * One sample of PlaneSpectra (simulation/plane_spectra.py; the reference's PSDOnline_Torch, online_statistics.py:269-416): for every
  * slab (env, channel k, listed plane j) the unnormalised DFT of the real plane [nz, nx] over (z, x) -- the convention of

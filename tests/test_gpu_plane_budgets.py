@@ -1,0 +1,231 @@
+"""``fg_plane_budgets`` / ``PlaneBudgets`` on the GPU, both libraries: three samples merged on the device against the long-double
+one-shot and against the host twin, the reference's golden values, repeatability, independence of the envs, non-finite cells, merging,
+and the env interface ``start_flow_budgets`` / ``stop_flow_budgets``."""
+import functools
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import fluidgym_amd
+from fluidgym_amd.envs.flow_statistics import FlowStatisticsMixin
+from fluidgym_amd.simulation.plane_budgets import HostPlaneBudgets, PlaneBudgets
+from tests.plane_budgets_ref import (BOUND_GOLDEN, BOUND_ONE_SHOT, channel_stack, make_grid, make_samples, one_shot, scaled_errors,
+                                     worst_errors)
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden", "reference_plane_budgets.npz")
+# (B, nz, ny, nx): every cell a border cell on every axis; odd extents, scalar loads, one wave per row; the 16-byte path (one wave);
+# a plane larger than one pass of the workgroup with a tail (fp32: scalar loads, fp64: 16-byte loads); the same with 16-byte loads
+# in fp32 (272 items of four cells for 256 threads)
+SHAPES = [(1, 2, 2, 2), (2, 3, 5, 7), (3, 4, 6, 64), (2, 9, 5, 130), (1, 8, 3, 136)]
+DTYPES = [np.float32, np.float64]
+ZERO, WRAP = (False, False), (True, True)
+TCF = dict(num_envs=2, randomize_initial_state=False, resolution_x_z=16, resolution_y=16, step_length=0.6, use_marl=False)
+
+
+@functools.lru_cache(maxsize=None)
+def _samples(shape, dtype):
+    return make_samples(shape, seed=sum(shape), dtype=dtype)
+
+
+@functools.lru_cache(maxsize=None)
+def _truth(shape, dtype, forcing, wrap):
+    """(the one-shot, the host twin's state) of the three samples; computed once, never written to."""
+    grid = make_grid(*shape[1:])
+    samples = _samples(shape, dtype)
+    host = HostPlaneBudgets(*grid, forcing=forcing, wrap=wrap)
+    for u, p, s in samples:
+        host.update(u, p, s)
+    return one_shot([channel_stack(s, grid, forcing, wrap) for s in samples], forcing), host._state()
+
+
+def _to_gpu(sample):
+    return tuple(torch.from_numpy(a).cuda() for a in sample)
+
+
+def _device_run(shape, samples, forcing, wrap, envs=None):
+    acc = PlaneBudgets(*make_grid(*shape[1:]), forcing=forcing, wrap=wrap)
+    for sample in samples:
+        u, p, s = sample if isinstance(sample[0], torch.Tensor) else _to_gpu(sample)
+        if envs is not None:
+            u, p, s = u[envs], p[envs], s[envs]            # views into the same memory
+        acc.update(u, p, s)
+    return acc
+
+
+@pytest.mark.parametrize("wrap", [ZERO, WRAP], ids=["zero", "wrap"])
+@pytest.mark.parametrize("forcing", [False, True], ids=["plain", "forcing"])
+@pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "f64"])
+@pytest.mark.parametrize("shape", SHAPES, ids=str)
+def test_three_samples_equal_the_one_shot_and_the_host_twin_and_repeat(shape, dtype, forcing, wrap):
+    truth, host = _truth(shape, dtype, forcing, wrap)
+    gpu = [_to_gpu(s) for s in _samples(shape, dtype)]
+    acc = _device_run(shape, gpu, forcing, wrap)
+    assert (acc.K, acc.M) == ((18, 52) if forcing else (15, 43))
+    state = acc._state()
+    assert np.array_equal(state[0], np.full(shape[0], 3.0 * shape[1] * shape[3]))
+    em, ec = worst_errors(acc, truth)
+    print(f"{shape} {np.dtype(dtype).name}: against the one-shot: mean {em:.2e}, central {ec:.2e} of the absolute-monomial sum")
+    assert em <= BOUND_ONE_SHOT and ec <= BOUND_ONE_SHOT
+    # the host twin, in the same units
+    n, _, _, abs1, absM = truth
+    hm = np.abs(state[1] - host[1]) / np.where(abs1 > 0, np.asarray(abs1 / n[:, None, None], np.float64), 1.0)
+    hc = np.abs(state[2] - host[2]) / np.where(absM > 0, np.asarray(absM, np.float64), 1.0)
+    print(f"against the host twin: mean {hm.max():.2e}, central {hc.max():.2e}")
+    assert np.array_equal(state[0], host[0]) and hm.max() <= BOUND_GOLDEN and hc.max() <= BOUND_GOLDEN
+    again = _device_run(shape, gpu, forcing, wrap)._state()
+    assert all(a.tobytes() == b.tobytes() for a, b in zip(state, again))
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "f64"])
+@pytest.mark.parametrize("shape", SHAPES[1:], ids=str)
+def test_an_env_of_a_batch_equals_the_env_run_alone(shape, dtype):
+    gpu = [_to_gpu(s) for s in _samples(shape, dtype)]
+    n, mean, cen = _device_run(shape, gpu, True, WRAP)._state()
+    for b in range(shape[0]):
+        an, am, ac = _device_run(shape, gpu, True, WRAP, envs=slice(b, b + 1))._state()
+        assert an[0] == n[b] and am[0].tobytes() == mean[b].tobytes() and ac[0].tobytes() == cen[b].tobytes()
+
+
+@pytest.mark.parametrize("forcing", [False, True], ids=["plain", "forcing"])
+def test_the_golden_inputs_meet_the_golden_values(forcing):
+    g = np.load(GOLDEN)
+    pre = "f_" if forcing else "nf_"
+    grid = (g["x"], g["y"], g["z"])
+    samples = [(g["velocity"][s], g["pressure"][s], g["source"][s]) for s in range(3)]
+    acc = PlaneBudgets(*grid, forcing=forcing, wrap=ZERO)
+    for s in samples:
+        acc.update(*_to_gpu(s))
+    n, _, _, abs1, absM = one_shot([channel_stack(s, grid, forcing, ZERO) for s in samples], forcing)
+    gn, mean, cen = acc._state()
+    assert gn.tolist() == [float(g[pre + "n"])]
+    worst = 0.0
+    for c in range(acc.K):
+        name = "mean_%d" % (c if c < 6 else c - 9) if (c < 6 or c >= 15) else "grad%d_mean_%d" % ((c - 6) // 3, (c - 6) % 3)
+        worst = max(worst, np.max(np.abs(mean[..., c] - g[pre + name][:, :, 0]) / np.asarray(abs1[..., c] / n[:, None], np.float64)))
+    for q, key in enumerate(acc.keys):
+        if len(key) != 2:
+            continue
+        if 6 <= key[0] < 15:
+            k = (key[0] - 6) // 3
+            name = "grad%d_moment_" % k + "_".join(str(sum(1 for c in key if c == 6 + 3 * k + i)) for i in range(3))
+        else:
+            chans = list(range(6)) + ([15, 16, 17] if forcing else [])
+            name = "moment_" + "_".join(str(sum(1 for c in key if c == ch)) for ch in chans)
+        worst = max(worst, np.max(np.abs(cen[..., q] - g[pre + name][:, :, 0]) / np.asarray(absM[..., q], np.float64)))
+    print("worst error against the golden values / absolute-monomial sum:", worst)
+    assert worst <= BOUND_GOLDEN
+    for t in ("production", "dissipation", "velocity_pressure_gradient"):
+        ref = g[pre + t + "_01"]
+        assert np.max(np.abs(getattr(acc, t)(0, 1)[0] - ref)) <= BOUND_GOLDEN * np.max(np.abs(ref))
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "f64"])
+@pytest.mark.parametrize("shape", [(2, 3, 5, 7), (3, 4, 6, 64), (2, 9, 5, 130)], ids=str)
+def test_a_nan_in_v_poisons_its_row_and_the_two_next_to_it(shape, dtype):
+    samples = [tuple(a.copy() for a in s) for s in _samples(shape, dtype)]
+    clean = _device_run(shape, samples, False, WRAP)._state()
+    b, y = shape[0] - 1, 2
+    samples[1][0][b, 1, shape[1] - 1, y, shape[3] // 2] = np.nan
+    dirty = _device_run(shape, samples, False, WRAP)._state()
+    bad = np.zeros((shape[0], shape[2]), bool)
+    bad[b, y - 1:y + 2] = True
+    for a, d in zip(clean[1:], dirty[1:]):
+        assert np.isnan(d[bad]).all() and a[~bad].tobytes() == d[~bad].tobytes()
+    assert clean[0].tobytes() == dirty[0].tobytes()
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "f64"])
+def test_merge_of_two_device_records_and_pooled_equal_the_one_shot(dtype):
+    shape = (2, 3, 5, 7)
+    samples = _samples(shape, dtype)
+    grid = make_grid(*shape[1:])
+    a, b = _device_run(shape, samples[:1], True, WRAP), _device_run(shape, samples[1:], True, WRAP)
+    assert a.merge(b) is a and isinstance(a, PlaneBudgets)
+    stacks = [channel_stack(s, grid, True, WRAP) for s in samples]
+    em, ec = worst_errors(a, one_shot(stacks, True))
+    pm, pc = worst_errors(a.pooled(), one_shot(stacks, True, pool_envs=True))
+    print(f"merge: mean {em:.2e}, central {ec:.2e}; pooled: mean {pm:.2e}, central {pc:.2e}")
+    assert max(em, ec, pm, pc) <= BOUND_ONE_SHOT
+
+
+def test_a_changed_batch_or_grid_raises():
+    shape = (2, 3, 5, 7)
+    gpu = [_to_gpu(s) for s in _samples(shape, np.float32)]
+    acc = _device_run(shape, gpu[:1], False, WRAP)
+    u, p, s = gpu[1]
+    with pytest.raises(ValueError, match="changed"):
+        acc.update(u[:1], p[:1])
+    with pytest.raises(ValueError, match="does not fit"):
+        acc.update(u[..., :6], p[..., :6])
+    with pytest.raises(TypeError):
+        acc.update(u.double(), p)
+    acc.update(u, p)
+    assert acc.n.tolist() == [2.0 * 3 * 7] * 2
+    with pytest.raises(RuntimeError, match="no sample"):
+        PlaneBudgets(*make_grid(*shape[1:])).n
+
+
+def test_tcf_env_records_what_a_host_twin_fed_through_the_same_hook_records(monkeypatch):
+    env = fluidgym_amd.make("TCFSmall3D-both-easy-v0", **TCF)
+    assert env._flow_budgets is None
+    with pytest.raises(RuntimeError, match="reset"):
+        env.start_flow_budgets()
+    with pytest.raises(RuntimeError, match="no budgets"):
+        env.stop_flow_budgets()
+    env.reset(seed=4)
+    with pytest.raises(ValueError):
+        env.start_flow_budgets(every=0)
+    env.start_flow_budgets(every=2)
+    acc = env._flow_budgets
+    blk = env._domain.getBlock(0)
+    nz, ny, nx = blk.velocity.shape[2:]
+    assert acc.wrap == (True, True) and acc.forcing == (blk.velocitySource is not None) and len(acc.y) == ny
+    assert np.array_equal(acc.y, 0.5 * (np.asarray(blk.edges[1], np.float64)[1:] + np.asarray(blk.edges[1], np.float64)[:-1]))
+    host = HostPlaneBudgets(acc.x, acc.y, acc.z, forcing=acc.forcing, wrap=acc.wrap)
+    device_update, fed = acc.update, []
+
+    def both(velocity, pressure, source=None):
+        device_update(velocity, pressure, source)
+        smp = (velocity.cpu().numpy(), pressure.cpu().numpy(), None if source is None else source.cpu().numpy())
+        host.update(*smp)
+        fed.append(smp)
+
+    acc.update = both
+    zero = torch.zeros(env._zero_action.shape, device=env.cuda_device)
+    for _ in range(2):
+        env.step(zero)
+    out = env.stop_flow_budgets()
+    samples = (2 * env._n_sim_steps) // 2
+    assert out is acc and env._flow_budgets is None and len(fed) == samples
+    n, mean, cen = out._state()
+    assert n.tolist() == [float(samples * nz * nx)] * 2
+    truth = one_shot([channel_stack(smp, (acc.x, acc.y, acc.z), acc.forcing, acc.wrap) for smp in fed], acc.forcing)
+    em, ec = worst_errors(out, truth)
+    print(f"env record against the one-shot: mean {em:.2e}, central {ec:.2e} of the absolute-monomial sum")
+    assert em <= BOUND_ONE_SHOT and ec <= BOUND_ONE_SHOT
+    hm, hc = scaled_errors((n, mean, cen), (truth[0],) + tuple(np.asarray(v, np.longdouble) for v in host._state()[1:]) + truth[3:])
+    print(f"env record against the host twin: mean {hm.max():.2e}, central {hc.max():.2e} of the absolute-monomial sum")
+    assert np.array_equal(n, host._state()[0]) and hm.max() <= BOUND_GOLDEN and hc.max() <= BOUND_GOLDEN
+    assert out.u_wall().shape == (2,) and np.isfinite(out.budget(0, 0, as_wall=True)["production"]).all()
+    # no budgets active: the step path must not reach the sampler at all
+    def boom(*a, **k):
+        raise AssertionError("the budget sampler ran although no budgets are recorded")
+
+    monkeypatch.setattr(FlowStatisticsMixin, "_record_budgets_sample", boom)
+    monkeypatch.setattr(PlaneBudgets, "update", boom)
+    env.step(zero)
+    assert env._flow_budgets is None
+    env.close()
+
+
+def test_budgets_refuse_two_dimensional_domains():
+    env = fluidgym_amd.make("RBC2D-easy-v0", num_envs=2, n_heaters=4, resolution=8, randomize_initial_state=False, step_length=0.5)
+    env.reset(seed=1)
+    with pytest.raises(NotImplementedError, match="3-D"):
+        env.start_flow_budgets()
+    env.close()
