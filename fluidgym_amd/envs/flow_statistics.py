@@ -5,7 +5,9 @@ The reference records them from its run scripts with ``VelocityStats.record_vel_
 planes (``simulation/plane_spectra.PlaneSpectra``; the reference's ``PSD_planes``, ``TCF_tools.py:445-459, 1491-1500``), and
 ``start_flow_budgets`` / ``stop_flow_budgets`` for the Reynolds-stress budgets of 3-D channels
 (``simulation/plane_budgets.PlaneBudgets``; the reference's ``TurbulentEnergyBudgetsOnlineParallel_Torch``,
-``TCF_tools.py:438-443, 1512-1516``)."""
+``TCF_tools.py:438-443, 1512-1516``), and ``start_flow_time_correlation`` / ``stop_flow_time_correlation`` for the temporal two-point
+correlations of the planes (``simulation/plane_timecorr.PlaneTimeCorrelation``; the reference's
+``TemporalTwoPointCorrelation_Online_torch``, ``TCF_tools.py:431-436, 1508-1511``)."""
 from __future__ import annotations
 
 from typing import Optional, Sequence
@@ -14,7 +16,8 @@ import numpy as np
 
 from ..simulation.plane_budgets import PlaneBudgets
 from ..simulation.plane_spectra import PlaneSpectra, check_extents
-from ..simulation.plane_stats import PlaneMoments
+from ..simulation.plane_stats import CHANNEL_SETS, PlaneMoments
+from ..simulation.plane_timecorr import PlaneTimeCorrelation
 
 
 class FlowStatisticsMixin:
@@ -28,6 +31,9 @@ class FlowStatisticsMixin:
     _flow_budgets: Optional[PlaneBudgets] = None    # None (the default): the step path does nothing for the budgets
     _flow_budgets_every: int = 1
     _flow_budgets_tick: int = 0
+    _flow_timecorr: Optional[PlaneTimeCorrelation] = None   # None (the default): the step path does nothing for the correlations
+    _flow_timecorr_every: int = 1
+    _flow_timecorr_tick: int = 0
 
     def start_flow_statistics(self, order: int = 2, every: int = 1) -> None:
         """Start a fresh record of moments up to ``order``; a sample is taken after every ``every``-th sim step of ``step()``."""
@@ -129,3 +135,40 @@ class FlowStatisticsMixin:
             return
         blk = self._domain.getBlock(0)
         self._flow_budgets.update(blk.velocity, blk.pressure, blk.velocitySource if self._flow_budgets.forcing else None)
+
+    def start_flow_time_correlation(self, lags: int, every: int = 1, stride: Optional[int] = None,
+                                    channels: Optional[Sequence[str]] = None) -> None:
+        """Start a fresh record of the temporal correlations over ``lags`` samples; a sample is taken after every ``every``-th sim
+        step of ``step()``.  ``stride`` None: one base at the first sample, as the reference; ``stride = S``: a new base at every
+        ``S``-th sample.  ``channels`` default to the velocity components; any channel set of the moments is taken."""
+        if getattr(self, "_domain", None) is None:
+            raise RuntimeError("start_flow_time_correlation: reset() the env first (the domain does not exist yet)")
+        if self._flow_blocks() != 1:
+            raise NotImplementedError("flow time correlations need a single-block domain")
+        if int(every) < 1:
+            raise ValueError(f"every must be at least 1, got {every}")
+        velocity = ("u", "v") + (("w",) if self._ndims == 3 else ())
+        channels = velocity if channels is None else tuple(channels)
+        if channels != velocity and (channels not in CHANNEL_SETS or ("w" in channels) != (self._ndims == 3)):
+            raise ValueError(f"channels must be {velocity} or one of {CHANNEL_SETS} that fits the {self._ndims}-D domain, got {channels}")
+        if "T" in channels and not self._domain.getBlock(0).hasPassiveScalar():
+            raise ValueError("start_flow_time_correlation: channel T needs a domain with a passive scalar")
+        self._flow_timecorr = PlaneTimeCorrelation(channels, lags, stride)
+        self._flow_timecorr_every, self._flow_timecorr_tick = int(every), 0
+
+    def stop_flow_time_correlation(self) -> PlaneTimeCorrelation:
+        """Stop recording and hand out the record (on the GPU; its accessors, ``pooled()`` and ``save`` read it back)."""
+        if self._flow_timecorr is None:
+            raise RuntimeError("stop_flow_time_correlation: no time correlations are being recorded")
+        corr, self._flow_timecorr = self._flow_timecorr, None
+        return corr
+
+    def _record_time_correlation_sample(self) -> None:
+        """Called after a sim step while time correlations are active; the sample's time is the simulation's host-side clock."""
+        self._flow_timecorr_tick += 1
+        if self._flow_timecorr_tick % self._flow_timecorr_every:
+            return
+        blk = self._domain.getBlock(0)
+        corr = self._flow_timecorr
+        corr.update(blk.velocity, blk.pressure if "p" in corr.channels else None,
+                    blk.passiveScalar if "T" in corr.channels else None, time=self._sim.total_time)

@@ -402,6 +402,8 @@ class RBCEnvBase(FlowStatisticsMixin, FluidEnv):
                 self._record_spectra_sample()
             if self._flow_budgets is not None:
                 self._record_budgets_sample()
+            if self._flow_timecorr is not None:
+                self._record_time_correlation_sample()
         nu = self.compute_global_nusselt()
         obs = self._get_global_obs()
         return obs, self.nu_ref - nu, False, {"nusselt": nu}

@@ -361,6 +361,8 @@ class TCF3DBottomEnv(FlowStatisticsMixin, FluidEnv):
                 self._record_spectra_sample()
             if self._flow_budgets is not None:
                 self._record_budgets_sample()
+            if self._flow_timecorr is not None:
+                self._record_time_correlation_sample()
             tb.append(b)
             tt.append(t)
         tau_bottom, tau_top = torch.stack(tb).mean(dim=0), torch.stack(tt).mean(dim=0)
@@ -377,6 +379,11 @@ class TCF3DBottomEnv(FlowStatisticsMixin, FluidEnv):
         super().start_flow_budgets(every=every, forcing=forcing)
         e = np.asarray(self._block.edges[1], np.float64)
         self._flow_budgets.set_wall_units(0.5 * (e[1:] + e[:-1]), self._nu)
+
+    def start_flow_time_correlation(self, lags: int, every: int = 1, stride=None, channels=None) -> None:
+        super().start_flow_time_correlation(lags, every=every, stride=stride, channels=channels)
+        e = np.asarray(self._block.edges[1], np.float64)                              # ETT and t+ from the nominal friction velocity
+        self._flow_timecorr.set_wall_units(0.5 * (e[1:] + e[:-1]), self._nu, self._u_wall)
 
     @property
     def id(self) -> str:

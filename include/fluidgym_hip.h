@@ -477,6 +477,36 @@ int fg_field_summary(const fg_real* field, int32_t batch, int32_t channels, int6
  * extent, a batch stride below nz * ny * nx, nz * nx above 2^30 or batch * ny above 2^31 - 1. */
 int fg_plane_moments(const fg_real* const* channels, const int64_t* batch_stride, int32_t K, int32_t batch, int32_t nz, int32_t ny,
                      int32_t nx, int32_t order, double* n, double* mean, double* central, uint64_t* tickets, void* stream);
+/* ---- online temporal two-point correlations of wall-parallel planes (csrc/fg_planetimecorr.hip; both libraries, handle-free) ------
+ * One sample of PlaneTimeCorrelation (simulation/plane_timecorr.py; the reference's TemporalTwoPointCorrelation_Online_torch,
+ * online_statistics.py:1271-1343): for every row (env, y) and channel k the fluctuation c' = c - mean_{z,x}(c) of the plane is
+ * correlated with the fluctuations b' the same plane had at earlier samples, kept in a ring of base slots, in ONE launch.
+ *   channels[k], batch_stride[k]   HOST tables of K = 1..5 entries, addressed as for fg_plane_moments (fields read in place, both
+ *                    tables copied into the kernel arguments).
+ *   lags             lags recorded, 0 .. lags - 1 samples.
+ *   slot_lag [n_slots]   HOST table, n_slots = 1..8, read during the call: what each slot does at this sample.  -1: idle.  0: this
+ *                    sample's c', rounded to fg_real, is stored as the slot's base and correlated with itself -- the slot's sum of
+ *                    b'^2 and its cross term are taken from the stored (rounded) values, so lag 0 and the later lags see one base.
+ *                    l > 0: the sample is correlated with the stored base, at lag l.  Two slots never hold the same lag >= 0.
+ *   base [n_slots][batch][K][nz][ny][nx]   DEVICE, fg_real: the stored fluctuations.
+ *   base_ss [n_slots][batch][ny][K]        DEVICE, fp64: the sum of b'^2 over the plane, written with the base.
+ *   acc [batch][ny][K][lags][4]            DEVICE, fp64, zeroed by the caller before the first sample.  For every live slot, at its
+ *                    lag l, four values are ADDED: the coefficient sum b'c' / sqrt(sum b'^2 sum c'^2), sum b'c' / cells,
+ *                    sum b'^2 / cells and sum c'^2 / cells (cells = nz nx).  How many bases have reached a lag is the caller's
+ *                    count: the schedule is the caller's, so two records merge by addition.
+ * Two fp64 passes per channel of a row: the plane sum for the mean, then the same cells again for the sums.  Ownership and order are
+ * those of fg_plane_moments (one workgroup, or one wave for planes of up to 1024 cells, per row; fixed tree; no floating-point
+ * atomics; every accumulator element and every base cell written by exactly one thread): a row's result depends only on its cells,
+ * its stored bases and the extents, and repeats bit for bit.  16-byte loads and stores when nx and every batch stride are multiples of
+ * 16 bytes / sizeof(fg_real) and every channel pointer and base are 16-byte aligned, scalar ones otherwise.  Nothing is filtered: a
+ * non-finite cell makes all four entries of its row and channel NaN at the lags this sample touches -- at every lag of the base when
+ * the sample is stored as one -- and nothing else.  A plane of one cell has no fluctuation: coefficient 0 / 0 = NaN, the sums 0.
+ * Asynchronous on `stream`; nothing returns to the host; a sample whose slots are all idle launches nothing.  FG_ERR_INVALID_ARG: a
+ * null pointer, K outside 1..5, lags < 1, n_slots outside 1..8, a slot_lag entry outside [-1, lags), two slots with the same
+ * lag >= 0, a non-positive extent, a batch stride below nz * ny * nx, nz * nx above 2^30 or batch * ny above 2^31 - 1. */
+int fg_plane_timecorr(const fg_real* const* channels, const int64_t* batch_stride, int32_t K, int32_t batch, int32_t nz, int32_t ny,
+                      int32_t nx, int32_t lags, int32_t n_slots, const int32_t* slot_lag, fg_real* base, double* base_ss, double* acc,
+                      void* stream);
 /* ---- online Reynolds-stress budgets of channel flows (csrc/fg_planebudgets.hip; both libraries, handle-free) -------------------
  * One sample of PlaneBudgets (simulation/plane_budgets.py; the reference's TurbulentEnergyBudgetsOnlineParallel_Torch,
  * online_statistics.py:790-1268): for every row (env, y) the means over (z, x) of K channels -- u, v, w, the three pressure gradients,
