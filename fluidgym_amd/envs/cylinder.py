@@ -27,7 +27,7 @@ from ..simulation.resample_mb import MultiBlockResampler, MultiBlockResampler3D
 from .. import spaces
 from .channel import jet_profile
 from .cylinder_grid import BOTTOM, LEFT, RIGHT, TOP, build_domain, extrude_mesh, make_vortex_street_mesh
-from .flow_statistics import FlowStatisticsMixin
+from .flow_statistics import FieldStatisticsMixin, FlowStatisticsMixin
 from .fluid_env import FluidEnv, is_per_env, per_env_parameter, refuse_per_env
 from .forces import WallRing
 
@@ -43,7 +43,8 @@ CYLINDER_ROT_2D_DEFAULT_CONFIG = dict(CYLINDER_JET_2D_DEFAULT_CONFIG)
 ONCHIP_PCG_MAX_CELLS = 24 * 1024   # the multilevel-preconditioned on-chip CG (2-D): fg_mb_onchip.hip OC_L2_CELLS
 
 
-class CylinderEnvBase(FlowStatisticsMixin, FluidEnv):      # (multi-block: the statistics refuse with NotImplementedError)
+class CylinderEnvBase(FieldStatisticsMixin, FlowStatisticsMixin, FluidEnv):      # (multi-block: the plane statistics refuse with
+                                                                                 # NotImplementedError, the per-cell ones record)
     _supports_marl = False
     _action_smoothing_alpha: float = 0.1
     H: float = 4.1
@@ -271,6 +272,8 @@ class CylinderEnvBase(FlowStatisticsMixin, FluidEnv):      # (multi-block: the s
             if self._enable_actions:
                 self._apply_action(controls[k])
             self._sim.single_step()
+            if self._field_stats is not None:
+                self._record_field_sample()
             self._ring.forces(self._domain, self._nu_forces, layer_height=self.D / self._circle_resolution_angular, out=raw[k])
         self._last_control_mirror = (self._last_control, c_last)
         obs = self._get_global_obs()

@@ -7,13 +7,19 @@ planes (``simulation/plane_spectra.PlaneSpectra``; the reference's ``PSD_planes`
 (``simulation/plane_budgets.PlaneBudgets``; the reference's ``TurbulentEnergyBudgetsOnlineParallel_Torch``,
 ``TCF_tools.py:438-443, 1512-1516``), and ``start_flow_time_correlation`` / ``stop_flow_time_correlation`` for the temporal two-point
 correlations of the planes (``simulation/plane_timecorr.PlaneTimeCorrelation``; the reference's
-``TemporalTwoPointCorrelation_Online_torch``, ``TCF_tools.py:431-436, 1508-1511``)."""
+``TemporalTwoPointCorrelation_Online_torch``, ``TCF_tools.py:431-436, 1508-1511``).
+
+The multi-block envs (cylinder, airfoil) have no homogeneous plane; ``FieldStatisticsMixin`` gives them ``start_field_statistics`` /
+``stop_field_statistics``: the time-averaged fields per cell, in 3-D averaged over the span as well
+(``simulation/cell_moments.CellMoments``; the reference's ``WelfordOnlineParallel_Torch`` / ``CovarianceOnlineParallel_Torch`` per
+block)."""
 from __future__ import annotations
 
 from typing import Optional, Sequence
 
 import numpy as np
 
+from ..simulation.cell_moments import CellMoments
 from ..simulation.plane_budgets import PlaneBudgets
 from ..simulation.plane_spectra import PlaneSpectra, check_extents
 from ..simulation.plane_stats import CHANNEL_SETS, PlaneMoments
@@ -172,3 +178,33 @@ class FlowStatisticsMixin:
         corr = self._flow_timecorr
         corr.update(blk.velocity, blk.pressure if "p" in corr.channels else None,
                     blk.passiveScalar if "T" in corr.channels else None, time=self._sim.total_time)
+
+
+class FieldStatisticsMixin:
+    _field_stats: Optional[CellMoments] = None      # None (the default): the step path does nothing for the statistics
+    _field_stats_every: int = 1
+    _field_stats_tick: int = 0
+
+    def start_field_statistics(self, every: int = 1, span_average: bool = True) -> None:
+        """Start a fresh per-cell record of ``u, v(, w), p``; a sample is taken after every ``every``-th sim step of ``step()``.
+        ``span_average`` (3-D): one column per ``(block, y, x)``, averaged over the span; off, every cell is recorded."""
+        if getattr(self, "_domain", None) is None:
+            raise RuntimeError("start_field_statistics: reset() the env first (the domain does not exist yet)")
+        if int(every) < 1:
+            raise ValueError(f"every must be at least 1, got {every}")
+        self._field_stats = CellMoments.for_domain(self._domain, span_average)
+        self._field_stats_every, self._field_stats_tick = int(every), 0
+
+    def stop_field_statistics(self) -> CellMoments:
+        """Stop recording and hand out the record (on the GPU; its accessors, ``pooled()`` and ``save`` read it back)."""
+        if self._field_stats is None:
+            raise RuntimeError("stop_field_statistics: no field statistics are being recorded")
+        stats, self._field_stats = self._field_stats, None
+        return stats
+
+    def _record_field_sample(self) -> None:
+        """Called after a sim step while field statistics are active; the fields are read, never written."""
+        self._field_stats_tick += 1
+        if self._field_stats_tick % self._field_stats_every:
+            return
+        self._field_stats.update(self._domain.velocity, self._domain.pressure)

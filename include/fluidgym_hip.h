@@ -507,6 +507,38 @@ int fg_plane_moments(const fg_real* const* channels, const int64_t* batch_stride
 int fg_plane_timecorr(const fg_real* const* channels, const int64_t* batch_stride, int32_t K, int32_t batch, int32_t nz, int32_t ny,
                       int32_t nx, int32_t lags, int32_t n_slots, const int32_t* slot_lag, fg_real* base, double* base_ss, double* acc,
                       void* stream);
+/* ---- online per-cell flow statistics of multi-block domains (csrc/fg_cellstats.hip; both libraries, handle-free) ----------------
+ * One sample of CellMoments (simulation/cell_moments.py; the reference's WelfordOnlineParallel_Torch and
+ * CovarianceOnlineParallel_Torch applied per block with dims = [0] in 2-D and [0, 2] in 3-D, online_statistics.py:31-266): for every
+ * column of every env the mean of the K = dims + 1 channels u, v(, w), p over the column's nz cells and the K (K + 1) / 2 sums of
+ * products of deviations from it, merged into running accumulators on the device in ONE launch.
+ *   velocity [batch][dims][n_cells], pressure [batch][n_cells]   the flat fields of a multi-block domain, contiguous, read in place
+ *   block_table      HOST table of n_blocks (1..8) rows (cell_offset, layer_cells, nz, column_offset), copied into the kernel
+ *                    arguments: cell z of column c (0 <= c < layer_cells) of a block is field[cell_offset + z * layer_cells + c], its
+ *                    accumulators are column column_offset + c.  2-D, or no span averaging: nz = 1 and layer_cells = the block's
+ *                    cells.  nz may differ from block to block.  column_offset must be the sum of layer_cells of the rows before; NC
+ *                    is the sum over all rows.
+ *   samples          calls already merged into the accumulators, counted by the HOST: a column has seen n_A = samples * nz cells.
+ *                    0 stores the sample (mean and central need no initialisation).  The device keeps no counter.
+ *   mean [batch][K][NC], central [batch][K (K + 1) / 2][NC]   fp64 device accumulators, updated in place; central holds the sums of
+ *                    d_i d_j for i <= j (i ascending, then j).  The sample's mean and central sums are taken in fp64, the cells in
+ *                    ascending z, and merged by the order-2 rule of fg_plane_moments with n_B = nz.
+ * A thread owns a column (16-byte loads: 16 / sizeof(fg_real) neighbouring columns, each with sums of its own); no floating-point
+ * atomic, no cross-lane operation, and the file is compiled with -ffp-contract=off (every product and sum rounded on its own): a
+ * column's result depends on its own cells and `samples` only -- not on `batch`, the other envs or blocks, the load form or the
+ * launch order -- and repeats bit for bit.  16-byte loads are used in a block whose
+ * cell_offset, layer_cells and column_offset are multiples of 16 / sizeof(fg_real) when n_cells and NC are too and all four pointers
+ * are 16-byte aligned; scalar loads otherwise.  A non-finite cell makes the accumulators of its column NaN (all channels) and nothing
+ * else.  Asynchronous on `stream`; nothing returns to the host.  FG_ERR_INVALID_ARG: a null pointer, dims outside 2..3, batch outside
+ * 1..65535, n_cells outside 1..2^31 - 1, n_blocks outside 1..8, samples outside 0..2^40 - 1, a non-positive layer_cells or nz, cells
+ * of a block outside the field, a column_offset that is not the running sum. */
+int fg_mb_cell_moments(const fg_real* velocity, const fg_real* pressure, int32_t dims, int32_t batch, int64_t n_cells,
+                       const int64_t* block_table, int32_t n_blocks, int64_t samples, double* mean, double* central, void* stream);
+/* What a thread of that launch would own in every block: widths[i] = 1 (one column, scalar loads) or 16 / sizeof(fg_real) (that many
+ * neighbouring columns, 16-byte loads), decided by the same code from the same pointers and table.  Host only: nothing is
+ * dereferenced but block_table and widths, nothing is launched.  Same argument checks and codes as fg_mb_cell_moments. */
+int fg_mb_cell_moments_widths(const fg_real* velocity, const fg_real* pressure, int64_t n_cells, const int64_t* block_table,
+                              int32_t n_blocks, const double* mean, const double* central, int32_t* widths);
 /* ---- online Reynolds-stress budgets of channel flows (csrc/fg_planebudgets.hip; both libraries, handle-free) -------------------
  * One sample of PlaneBudgets (simulation/plane_budgets.py; the reference's TurbulentEnergyBudgetsOnlineParallel_Torch,
  * online_statistics.py:790-1268): for every row (env, y) the means over (z, x) of K channels -- u, v, w, the three pressure gradients,
