@@ -8,7 +8,7 @@
 // holds them (blocks contiguous in N, x fastest, z slowest):
 //   pass 1   the sums of the K channels over the column's nz cells, ascending z, fp64          -> the sample's mean
 //   pass 2   the same cells again (just read: L1 / L2), the sums of d_i d_j (i <= j), fp64     -> the sample's central sums
-//   merge    with the running accumulators mean [B][K][NC], central [B][K (K + 1) / 2][NC] by the order-2 rule of fg_planestats.hip
+//   merge    with the running accumulators mean [B][K][NC], central [B][K (K + 1) / 2][NC] by the order-2 rule of fg_rowstat.h
 //            (parallel Welford / Schubert-Gertz, delta = mean_sample - mean_running), n_A = samples * nz, n_B = nz; the first
 //            sample (samples = 0) is stored.  `samples` is a kernel argument: the host counts, the device keeps no counter.
 //
@@ -22,12 +22,14 @@
 #include <float.h>
 #include <limits.h>
 
-#include "fg_internal.h"
+#include "fg_rowstat.h"
 
 namespace {
 
+namespace rs = fg_rowstat;
+
 constexpr int CM_MAX_BLOCKS = 8;
-constexpr int CM_VEC = FG_F64 ? 2 : 4;   // reals per 16-byte load
+constexpr int CM_VEC = rs::VEC;
 
 struct CmBlock {
     long long cell_offset, column_offset, item_offset;   // item: what one thread owns, `width` neighbouring columns
@@ -42,21 +44,6 @@ struct CmArgs {
     double* central;
     CmBlock blk[CM_MAX_BLOCKS];          // by value: no table in device memory, no copy per call
 };
-
-template <int W>
-__device__ __forceinline__ void cm_load(const fg_real* p, double (&v)[W]) {
-    if constexpr (W == 1) {
-        v[0] = (double)p[0];
-    } else {
-#if FG_F64
-        const double2 q = *reinterpret_cast<const double2*>(p);
-        v[0] = q.x; v[1] = q.y;
-#else
-        const float4 q = *reinterpret_cast<const float4*>(p);
-        v[0] = (double)q.x; v[1] = (double)q.y; v[2] = (double)q.z; v[3] = (double)q.w;
-#endif
-    }
-}
 
 // W neighbouring accumulators of one plane: 8-byte accesses for one column, 16-byte ones for an aligned group
 template <int W>
@@ -103,7 +90,7 @@ __device__ __forceinline__ void cm_column(const CmArgs& a, int b, long long cell
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             double v[W];
-            cm_load<W>(base[k] + off, v);
+            rs::load<W>(base[k] + off, v);
 #pragma unroll
             for (int j = 0; j < W; ++j) mu[k][j] += v[j];
         }
@@ -134,7 +121,7 @@ __device__ __forceinline__ void cm_column(const CmArgs& a, int b, long long cell
         double d[K][W];
 #pragma unroll
         for (int k = 0; k < K; ++k) {
-            cm_load<W>(base[k] + off, d[k]);
+            rs::load<W>(base[k] + off, d[k]);
 #pragma unroll
             for (int j = 0; j < W; ++j) d[k][j] -= mu[k][j];
         }
@@ -183,7 +170,7 @@ __device__ __forceinline__ void cm_column(const CmArgs& a, int b, long long cell
             double A[W];
             cm_acc_load<W>(gc + (long long)q * a.NC, A);
 #pragma unroll
-            for (int j = 0; j < W; ++j) A[j] = A[j] + c[q][j] + dl[i1][j] * dl[i2][j] * w2;
+            for (int j = 0; j < W; ++j) A[j] = rs::merge2(A[j], c[q][j], dl[i1][j], dl[i2][j], w2);
             cm_acc_store<W>(gc + (long long)q * a.NC, A);
             ++q;
         }

@@ -19,24 +19,21 @@
 // (i <= j <= k), the 9 u_i dp/dx_j (i, then j), with forcing the 9 u_i s_j, then per direction k the 6 second-order sums of
 // (d_k u, d_k v, d_k w).
 //
-// Ownership, order, the ticket for n[env] and the handling of non-finite cells are those of fg_planestats.hip: one workgroup of 256
-// threads (one wave for planes of up to 1024 cells) owns a row, lanes add their cells in ascending order, xor butterfly, waves in
-// ascending order through LDS, no floating-point atomic: a row's result depends on nothing but the row's cells, its two neighbour
-// rows, the coordinates and the extents.  A non-finite value in any channel of a row -- a non-finite cell of the row itself or, through
-// d/dy, of a neighbour row -- makes the sample of that row NaN.
+// Ownership, order, the loads and the ticket for n[env] are those of fg_rowstat.h; a row's result depends on nothing but the row's
+// cells, its two neighbour rows, the coordinates and the extents.  A non-finite value in any channel of a row -- a non-finite cell of
+// the row itself or, through d/dy, of a neighbour row -- makes the sample of that row NaN.
 #include <float.h>
 
-#include "fg_internal.h"
+#include "fg_rowstat.h"
 
 namespace {
 
+namespace rs = fg_rowstat;
+
 constexpr int PB_MAX_FIELDS = 7;         // u, v, w, p, s_x, s_y, s_z
-constexpr int PB_WAVE_CELLS = 1024;      // planes up to this many cells are reduced by one wave
-constexpr int PB_VEC = FG_F64 ? 2 : 4;   // reals per 16-byte load
 
 struct PbArgs {
-    const fg_real* f[PB_MAX_FIELDS];     // by value, as in fg_plane_moments
-    long long bstride[PB_MAX_FIELDS];
+    rs::ChannelTable<PB_MAX_FIELDS> t;
     long long zstride, rows;             // ny * nx; batch * ny
     int nz, ny, nx;
     int wrap_x, wrap_z;
@@ -49,45 +46,11 @@ struct PbArgs {
     unsigned long long* tickets;
 };
 
-template <int VEC>
-__device__ __forceinline__ void pb_load(const fg_real* p, fg_real (&v)[VEC]) {
-    if constexpr (VEC == 1) {
-        v[0] = p[0];
-    } else {
-#if FG_F64
-        const double2 q = *reinterpret_cast<const double2*>(p);
-        v[0] = q.x; v[1] = q.y;
-#else
-        const float4 q = *reinterpret_cast<const float4*>(p);
-        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-#endif
-    }
-}
-
 // 1 / |pos[i + 1] - pos[i - 1]| with mirrored ghost positions at both ends (n >= 2)
 __device__ __forceinline__ double pb_rdist(const double* pos, int i, int n) {
     const double lo = i > 0 ? pos[i - 1] : 2.0 * pos[0] - pos[1];
     const double hi = i < n - 1 ? pos[i + 1] : 2.0 * pos[n - 1] - pos[n - 2];
     return 1.0 / fabs(hi - lo);
-}
-
-template <int N, int S, bool WAVE>
-__device__ __forceinline__ void pb_reduce(double (&v)[N], double (&s_red)[4][S], int tid) {
-#pragma unroll
-    for (int q = 0; q < N; ++q) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v[q] += __shfl_xor(v[q], off, 64);
-    }
-    if constexpr (!WAVE) {
-        if ((tid & 63) == 0) {
-#pragma unroll
-            for (int q = 0; q < N; ++q) s_red[tid >> 6][q] = v[q];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < N; ++q) v[q] = ((s_red[0][q] + s_red[1][q]) + s_red[2][q]) + s_red[3][q];
-        __syncthreads();
-    }
 }
 
 // what one work item (VEC consecutive cells in x of the row) reads: the cells themselves, their neighbours in y and z as vectors, the
@@ -104,7 +67,7 @@ template <int NF, int VEC>
 __device__ __forceinline__ void pb_read(const PbArgs& a, const fg_real* const (&base)[NF], int y, int z, int x0, PbItem<NF, VEC>& it) {
     const long long off = (long long)z * a.zstride + x0;
 #pragma unroll
-    for (int f = 0; f < NF; ++f) pb_load<VEC>(base[f] + off, it.c[f]);
+    for (int f = 0; f < NF; ++f) rs::load<VEC>(base[f] + off, it.c[f]);
     // z - 1, z + 1, x0 - 1, x0 + VEC: an offset, or no read at all
     const bool has_zm = z > 0 || a.wrap_z, has_zp = z < a.nz - 1 || a.wrap_z;
     const long long ozm = z > 0 ? off - a.zstride : off + (long long)(a.nz - 1) * a.zstride;
@@ -116,10 +79,10 @@ __device__ __forceinline__ void pb_read(const PbArgs& a, const fg_real* const (&
     for (int f = 0; f < 4; ++f) {
 #pragma unroll
         for (int j = 0; j < VEC; ++j) it.ym[f][j] = it.yp[f][j] = it.zm[f][j] = it.zp[f][j] = (fg_real)0;
-        if (y > 0) pb_load<VEC>(base[f] + off - a.nx, it.ym[f]);
-        if (y < a.ny - 1) pb_load<VEC>(base[f] + off + a.nx, it.yp[f]);
-        if (has_zm) pb_load<VEC>(base[f] + ozm, it.zm[f]);
-        if (has_zp) pb_load<VEC>(base[f] + ozp, it.zp[f]);
+        if (y > 0) rs::load<VEC>(base[f] + off - a.nx, it.ym[f]);
+        if (y < a.ny - 1) rs::load<VEC>(base[f] + off + a.nx, it.yp[f]);
+        if (has_zm) rs::load<VEC>(base[f] + ozm, it.zm[f]);
+        if (has_zp) rs::load<VEC>(base[f] + ozp, it.zp[f]);
         it.xm[f] = has_xm ? base[f][oxm] : (fg_real)0;
         it.xp[f] = has_xp ? base[f][oxp] : (fg_real)0;
     }
@@ -162,14 +125,10 @@ __global__ __launch_bounds__(256) void k_plane_budgets(PbArgs a) {
     constexpr int Q3 = 6, QP = 16, QS = 25, QG = F ? 34 : 25, M = QG + 18;
     __shared__ double s_red[4][M];
     const int tid = threadIdx.x;
-    const long long row = WAVE ? (long long)blockIdx.x * 4 + (tid >> 6) : (long long)blockIdx.x;
-    if (WAVE && row >= a.rows) return;                       // a whole wave; this form has no barrier
-    const int b = (int)(row / a.ny), y = (int)(row - (long long)b * a.ny);
-    const int nxv = a.nx / VEC, items = a.nz * nxv;
-    const int t0 = WAVE ? (tid & 63) : tid, step = WAVE ? 64 : 256;
+    FG_ROWSTAT_OWN_ROW(a, VEC, WAVE, tid);
     const fg_real* base[NF];
 #pragma unroll
-    for (int f = 0; f < NF; ++f) base[f] = a.f[f] + (long long)b * a.bstride[f] + (long long)y * a.nx;
+    for (int f = 0; f < NF; ++f) base[f] = a.t.ch[f] + (long long)b * a.t.bstride[f] + (long long)y * a.nx;
     const double ry = pb_rdist(a.y, y, a.ny);
 
     double mu[K];
@@ -187,9 +146,9 @@ __global__ __launch_bounds__(256) void k_plane_budgets(PbArgs a) {
             for (int k = 0; k < K; ++k) mu[k] += ch[k];
         }
     }
-    pb_reduce<K, M, WAVE>(mu, s_red, tid);
+    rs::reduce<K, M, WAVE>(mu, s_red, tid);
     const double cells = (double)a.nz * (double)a.nx;
-    bool bad = false;
+    bool bad = false;                                        // (not rs::finish_means: with it the register allocation of this kernel changes)
 #pragma unroll
     for (int k = 0; k < K; ++k) {
         mu[k] = mu[k] / cells;
@@ -243,7 +202,7 @@ __global__ __launch_bounds__(256) void k_plane_budgets(PbArgs a) {
             }
         }
     }
-    pb_reduce<M, M, WAVE>(c, s_red, tid);
+    rs::reduce<M, M, WAVE>(c, s_red, tid);
     if (t0 != 0) return;
 
     // ---- merge: A = the running record, B = this sample, delta = mean_B - mean_A (Pebay et al. 2016, eq. 3.1 without weights)
@@ -270,7 +229,7 @@ __global__ __launch_bounds__(256) void k_plane_budgets(PbArgs a) {
 #pragma unroll
             for (int i2 = i1; i2 < 3; ++i2) {
                 a2[q2] = gc[q2];
-                gc[q2] = a2[q2] + c[q2] + dl[i1] * dl[i2] * w2;
+                gc[q2] = rs::merge2(a2[q2], c[q2], dl[i1], dl[i2], w2);
                 ++q2;
             }
         }
@@ -293,10 +252,10 @@ __global__ __launch_bounds__(256) void k_plane_budgets(PbArgs a) {
 #pragma unroll
             for (int i2 = 0; i2 < 3; ++i2) {
                 const int qp = QP + 3 * i1 + i2;
-                gc[qp] = gc[qp] + c[qp] + dl[i1] * dl[3 + i2] * w2;
+                gc[qp] = rs::merge2(gc[qp], c[qp], dl[i1], dl[3 + i2], w2);
                 if constexpr (F) {
                     const int qs = QS + 3 * i1 + i2;
-                    gc[qs] = gc[qs] + c[qs] + dl[i1] * dl[15 + i2] * w2;
+                    gc[qs] = rs::merge2(gc[qs], c[qs], dl[i1], dl[15 + i2], w2);
                 }
             }
         }
@@ -307,27 +266,20 @@ __global__ __launch_bounds__(256) void k_plane_budgets(PbArgs a) {
             for (int i1 = 0; i1 < 3; ++i1) {
 #pragma unroll
                 for (int i2 = i1; i2 < 3; ++i2) {
-                    gc[q] = gc[q] + c[q] + dl[6 + 3 * k + i1] * dl[6 + 3 * k + i2] * w2;
+                    gc[q] = rs::merge2(gc[q], c[q], dl[6 + 3 * k + i1], dl[6 + 3 * k + i2], w2);
                     ++q;
                 }
             }
         }
     }
-    // every row of env b has read n[b] before it takes its ticket; the last one of this call's ny rows advances n[b]
-    const unsigned long long ticket = __hip_atomic_fetch_add(&a.tickets[b], 1ull, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-    if ((ticket + 1ull) % (unsigned long long)a.ny == 0ull) a.n[b] = n;
+    FG_ROWSTAT_ADVANCE_N(a, b, n);
 }
 
 template <int NF>
 void pb_launch(const PbArgs& a, bool vec, bool wave, hipStream_t st) {
-    const dim3 grid((unsigned)(wave ? (a.rows + 3) / 4 : a.rows));
-    if (vec) {
-        if (wave) hipLaunchKernelGGL((k_plane_budgets<NF, PB_VEC, true>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((k_plane_budgets<NF, PB_VEC, false>), grid, dim3(256), 0, st, a);
-    } else {
-        if (wave) hipLaunchKernelGGL((k_plane_budgets<NF, 1, true>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((k_plane_budgets<NF, 1, false>), grid, dim3(256), 0, st, a);
-    }
+    rs::launch(a.rows, vec, wave, [&](dim3 grid, auto v, auto w) {
+        hipLaunchKernelGGL((k_plane_budgets<NF, decltype(v)::value, decltype(w)::value>), grid, dim3(256), 0, st, a);
+    });
 }
 
 }  // namespace
@@ -342,25 +294,16 @@ extern "C" int fg_plane_budgets(const fg_real* const* fields, const int64_t* bat
                "fg_plane_budgets: n_fields must be 4 (u, v, w, p) or 7 (with the forcing s_x, s_y, s_z)");
     FG_REQUIRE(batch > 0, FG_ERR_INVALID_ARG, "fg_plane_budgets: batch must be positive");
     FG_REQUIRE(nz >= 2 && ny >= 2 && nx >= 2, FG_ERR_INVALID_ARG, "fg_plane_budgets: nz, ny, nx must be at least 2 (a central difference)");
-    FG_REQUIRE((long long)nz * nx <= (1LL << 30), FG_ERR_INVALID_ARG, "fg_plane_budgets: a plane of more than 2^30 cells");
-    FG_REQUIRE((long long)batch * ny <= 0x7fffffffLL, FG_ERR_INVALID_ARG, "fg_plane_budgets: batch * ny too large for one launch");
-    const long long field = (long long)nz * ny * nx;
     PbArgs a;
-    bool vec = nx % PB_VEC == 0;
-    for (int f = 0; f < PB_MAX_FIELDS; ++f) {
-        a.f[f] = nullptr; a.bstride[f] = 0;
-        if (f >= n_fields) continue;
-        FG_REQUIRE(fields[f], FG_ERR_INVALID_ARG, "fg_plane_budgets: null field pointer");
-        FG_REQUIRE(batch_stride[f] >= field, FG_ERR_INVALID_ARG, "fg_plane_budgets: batch stride smaller than nz * ny * nx");
-        a.f[f] = fields[f]; a.bstride[f] = (long long)batch_stride[f];
-        vec = vec && ((uintptr_t)fields[f] % 16 == 0) && (batch_stride[f] % PB_VEC == 0);
-    }
+    bool vec;
+    const int rc = rs::fill_rows(a.t, vec, "fg_plane_budgets", "field", fields, batch_stride, n_fields, batch, nz, ny, nx);
+    if (rc != FG_OK) return rc;
     a.zstride = (long long)ny * nx; a.rows = (long long)batch * ny;
     a.nz = nz; a.ny = ny; a.nx = nx;
     a.wrap_x = wrap_x != 0; a.wrap_z = wrap_z != 0;
     a.x = x; a.y = y; a.z = z;
     a.n = n; a.mean = mean; a.central = central; a.tickets = (unsigned long long*)tickets;
-    const bool wave = (long long)nz * nx <= PB_WAVE_CELLS;
+    const bool wave = (long long)nz * nx <= rs::WAVE_CELLS;
     hipStream_t st = (hipStream_t)stream;
     if (n_fields == 4) pb_launch<4>(a, vec, wave, st);
     else pb_launch<7>(a, vec, wave, st);

@@ -26,14 +26,15 @@
 
 #include <mutex>
 
-#include "fg_internal.h"
+#include "fg_rowstat.h"
 
 namespace {
+
+namespace rs = fg_rowstat;
 
 constexpr int PS_MAX_K = 5;
 constexpr int PS_MAX_PLANES = 32;
 constexpr int PS_WAVES = 4;
-constexpr int PS_VEC = FG_F64 ? 2 : 4;            // reals per 16-byte load
 constexpr int PS_LDS_LIMIT = 160 * 1024;          // what a workgroup may declare on gfx950
 #if FG_F64
 typedef double2 ps_c;
@@ -44,8 +45,7 @@ constexpr fg_real PS_REAL_MAX = FG_F64 ? (fg_real)DBL_MAX : (fg_real)FLT_MAX;
 constexpr int PS_WORK_MIN =2048 / (int)sizeof(ps_c);   // a work buffer holds at least 2 KB: 256 (fp32) / 128 (fp64) complex
 
 struct PsArgs {
-    const fg_real* ch[PS_MAX_K];          // by value, as in fg_plane_moments
-    long long bstride[PS_MAX_K];
+    rs::ChannelTable<PS_MAX_K> t;         // loads and their checks: fg_rowstat.h
     int planes[PS_MAX_PLANES];
     long long zstride;                    // ny * nx
     int K, n_planes, nz, nx, lnz, lnx;    // ln = log2
@@ -119,20 +119,10 @@ __device__ __forceinline__ ps_c* ps_stockham(ps_c* x, ps_c* y, const ps_c* __res
 template <int VEC>
 __device__ __forceinline__ bool ps_stage(const fg_real* pa, const fg_real* pb, ps_c* dst) {
     fg_real va[VEC], vb[VEC];
-    if constexpr (VEC == 1) {
-        va[0] = pa[0];
-        vb[0] = pb ? pb[0] : (fg_real)0;
-    } else {
-#if FG_F64
-        const double2 qa = *reinterpret_cast<const double2*>(pa);
-        const double2 qb = pb ? *reinterpret_cast<const double2*>(pb) : make_double2(0.0, 0.0);
-        va[0] = qa.x; va[1] = qa.y; vb[0] = qb.x; vb[1] = qb.y;
-#else
-        const float4 qa = *reinterpret_cast<const float4*>(pa);
-        const float4 qb = pb ? *reinterpret_cast<const float4*>(pb) : make_float4(0.f, 0.f, 0.f, 0.f);
-        va[0] = qa.x; va[1] = qa.y; va[2] = qa.z; va[3] = qa.w; vb[0] = qb.x; vb[1] = qb.y; vb[2] = qb.z; vb[3] = qb.w;
-#endif
-    }
+    rs::load<VEC>(pa, va);
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) vb[e] = (fg_real)0;
+    if (pb) rs::load<VEC>(pb, vb);
     bool bad = false;
 #pragma unroll
     for (int e = 0; e < VEC; ++e) {
@@ -152,7 +142,7 @@ __global__ __launch_bounds__(256) void k_plane_spectra(PsArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int sid = blockIdx.x;
     const int j = sid % a.n_planes, k = (sid / a.n_planes) % a.K, b = sid / (a.n_planes * a.K);
-    const fg_real* base = a.ch[k] + (long long)b * a.bstride[k] + (long long)a.planes[j] * a.nx;
+    const fg_real* base = a.t.ch[k] + (long long)b * a.t.bstride[k] + (long long)a.planes[j] * a.nx;
     const int nz = a.nz, nx = a.nx, hx = nx >> 1, lhx = a.lnx - 1, pitch = a.pitch;
     ps_c* x = work + wave * 2 * a.work;
     ps_c* y = x + a.work;
@@ -170,7 +160,7 @@ __global__ __launch_bounds__(256) void k_plane_spectra(PsArgs a) {
         const int npairs = nz > 1 ? nz >> 1 : 1;
         int nb = a.work >> a.lnx;
         nb = nb < npairs ? nb : npairs;
-        const int lvec = a.vec ? (PS_VEC == 4 ? 2 : 1) : 0, lnxv = a.lnx - lvec;
+        const int lvec = a.vec ? (rs::VEC == 4 ? 2 : 1) : 0, lnxv = a.lnx - lvec;
         const int tws = a.nmax >> a.lnx;
         bool bad = false;
         for (int q0 = wave * nb; q0 < npairs; q0 += PS_WAVES * nb) {
@@ -179,7 +169,7 @@ __global__ __launch_bounds__(256) void k_plane_spectra(PsArgs a) {
                 const fg_real* pa = base + (long long)(2 * (q0 + s)) * a.zstride + xe;
                 const fg_real* pb = nz > 1 ? pa + a.zstride : nullptr;
                 ps_c* dst = x + (s << a.lnx) + xe;
-                bad = (a.vec ? ps_stage<PS_VEC>(pa, pb, dst) : ps_stage<1>(pa, pb, dst)) || bad;
+                bad = (a.vec ? ps_stage<rs::VEC>(pa, pb, dst) : ps_stage<1>(pa, pb, dst)) || bad;
             }
             ps_wave_sync();
             const ps_c* X = ps_stockham(x, y, tw, a.lnx, tws, nb << a.lnx, lane);
@@ -269,16 +259,9 @@ extern "C" int fg_plane_spectra(const fg_real* const* channels, const int64_t* b
         FG_REQUIRE(planes[j] >= 0 && planes[j] < ny, FG_ERR_INVALID_ARG, "fg_plane_spectra: plane index outside [0, ny)");
         a.planes[j] = planes[j];
     }
-    const long long field = (long long)nz * ny * nx;
-    bool vec = nx % PS_VEC == 0;
-    for (int k = 0; k < PS_MAX_K; ++k) {
-        a.ch[k] = nullptr; a.bstride[k] = 0;
-        if (k >= K) continue;
-        FG_REQUIRE(channels[k], FG_ERR_INVALID_ARG, "fg_plane_spectra: null channel pointer");
-        FG_REQUIRE(batch_stride[k] >= field, FG_ERR_INVALID_ARG, "fg_plane_spectra: batch stride smaller than nz * ny * nx");
-        a.ch[k] = channels[k]; a.bstride[k] = (long long)batch_stride[k];
-        vec = vec && ((uintptr_t)channels[k] % 16 == 0) && (batch_stride[k] % PS_VEC == 0);
-    }
+    bool vec;
+    const int rc = rs::fill(a.t, vec, "fg_plane_spectra", "channel", channels, batch_stride, K, nz, ny, nx);
+    if (rc != FG_OK) return rc;
     FG_REQUIRE(nx >= 8 && nx <= 512 && (nx & (nx - 1)) == 0, FG_ERR_UNSUPPORTED, "fg_plane_spectra: nx must be a power of two in 8..512");
     FG_REQUIRE(nz == 1 || (nz >= 4 && nz <= 256 && (nz & (nz - 1)) == 0), FG_ERR_UNSUPPORTED,
                "fg_plane_spectra: nz must be 1 or a power of two in 4..256");

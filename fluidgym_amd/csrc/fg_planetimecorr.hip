@@ -18,24 +18,21 @@
 // K = 5 and L = 8 that is 10 sums instead of 50 (100 VGPRs), and the kernel is instantiated 8 times per load width and ownership
 // form instead of 40 times.  A channel's plane is re-read while it is the only thing the workgroup touches.
 //
-// Ownership and order are those of fg_plane_moments (fg_planestats.hip): one workgroup of 256 threads owns a row whose plane has
-// more than PT_WAVE_CELLS cells, one wave of a four-wave workgroup a smaller one.  Every lane adds its cells in ascending order, the
-// lanes combine by the xor butterfly of the wave, the waves in ascending order through LDS: a fixed tree, no floating-point atomic,
-// every accumulator element and every base cell written by exactly one thread.
+// Ownership, order and the loads are those of fg_rowstat.h; every accumulator element and every base cell is written by exactly
+// one thread.
 #include <float.h>
 
-#include "fg_internal.h"
+#include "fg_rowstat.h"
 
 namespace {
 
+namespace rs = fg_rowstat;
+
 constexpr int PT_MAX_K = 5;
 constexpr int PT_MAX_SLOTS = 8;
-constexpr int PT_WAVE_CELLS = 1024;      // planes up to this many cells are reduced by one wave
-constexpr int PT_VEC = FG_F64 ? 2 : 4;   // reals per 16-byte load
 
 struct PtArgs {
-    const fg_real* ch[PT_MAX_K];         // by value: no pointer table in device memory, no copy per call
-    long long bstride[PT_MAX_K];
+    rs::ChannelTable<PT_MAX_K> t;
     long long zstride, rows, field;      // ny * nx; batch * ny; nz * ny * nx
     int nz, ny, nx, K, batch, lags;
     int slot[PT_MAX_SLOTS], lag[PT_MAX_SLOTS];   // the live slots of this sample; with `store`, entry 0 is the slot at lag 0
@@ -44,21 +41,6 @@ struct PtArgs {
     double* base_ss;
     double* acc;
 };
-
-template <int VEC>
-__device__ __forceinline__ void pt_load(const fg_real* p, double (&v)[VEC]) {
-    if constexpr (VEC == 1) {
-        v[0] = (double)p[0];
-    } else {
-#if FG_F64
-        const double2 q = *reinterpret_cast<const double2*>(p);
-        v[0] = q.x; v[1] = q.y;
-#else
-        const float4 q = *reinterpret_cast<const float4*>(p);
-        v[0] = (double)q.x; v[1] = (double)q.y; v[2] = (double)q.z; v[3] = (double)q.w;
-#endif
-    }
-}
 
 // v rounded to fg_real, stored at p and handed back as what a later load will see
 template <int VEC>
@@ -77,42 +59,17 @@ __device__ __forceinline__ void pt_store(fg_real* p, double (&v)[VEC]) {
     }
 }
 
-// the sum of v[q] over the lanes of the wave (WAVE) or of the workgroup, left in every lane: xor butterfly, then the four waves in
-// ascending order
-template <int N, int S, bool WAVE>
-__device__ __forceinline__ void pt_reduce(double (&v)[N], double (&s_red)[4][S], int tid) {
-#pragma unroll
-    for (int q = 0; q < N; ++q) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v[q] += __shfl_xor(v[q], off, 64);
-    }
-    if constexpr (!WAVE) {
-        if ((tid & 63) == 0) {
-#pragma unroll
-            for (int q = 0; q < N; ++q) s_red[tid >> 6][q] = v[q];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < N; ++q) v[q] = ((s_red[0][q] + s_red[1][q]) + s_red[2][q]) + s_red[3][q];
-        __syncthreads();
-    }
-}
-
 template <int L, int VEC, bool WAVE>
 __global__ __launch_bounds__(256) void k_plane_timecorr(PtArgs a) {
     constexpr int M = L + 2;                                 // sum c'^2, sum b'^2 of the slot being stored, L cross terms
     __shared__ double s_red[4][M];
     const int tid = threadIdx.x;
-    const long long row = WAVE ? (long long)blockIdx.x * 4 + (tid >> 6) : (long long)blockIdx.x;
-    if (WAVE && row >= a.rows) return;                       // a whole wave; this form has no barrier
-    const int b = (int)(row / a.ny), y = (int)(row - (long long)b * a.ny);
-    const int nxv = a.nx / VEC, items = a.nz * nxv;
-    const int t0 = WAVE ? (tid & 63) : tid, step = WAVE ? 64 : 256;
+    FG_ROWSTAT_OWN_ROW(a, VEC, WAVE, tid);
     const double cells = (double)a.nz * (double)a.nx;
     const bool store = a.store != 0;
 
     for (int k = 0; k < a.K; ++k) {
-        const fg_real* src = a.ch[k] + (long long)b * a.bstride[k] + (long long)y * a.nx;
+        const fg_real* src = a.t.ch[k] + (long long)b * a.t.bstride[k] + (long long)y * a.nx;
         fg_real* bp[L];
 #pragma unroll
         for (int j = 0; j < L; ++j) bp[j] = a.base + (((long long)a.slot[j] * a.batch + b) * a.K + k) * a.field + (long long)y * a.nx;
@@ -121,24 +78,23 @@ __global__ __launch_bounds__(256) void k_plane_timecorr(PtArgs a) {
         for (int i = t0; i < items; i += step) {
             const int z = i / nxv, xv = i - z * nxv;
             double v[VEC];
-            pt_load<VEC>(src + (long long)z * a.zstride + (long long)xv * VEC, v);
+            rs::load<VEC>(src + (long long)z * a.zstride + (long long)xv * VEC, v);
 #pragma unroll
             for (int j = 0; j < VEC; ++j) mu[0] += v[j];
         }
-        pt_reduce<1, M, WAVE>(mu, s_red, tid);
+        rs::reduce<1, M, WAVE>(mu, s_red, tid);
         const double mean = mu[0] / cells;
 
         double s[M];
 #pragma unroll
         for (int q = 0; q < M; ++q) s[q] = 0.0;
         for (int i = t0; i < items; i += step) {
-            const int z = i / nxv, xv = i - z * nxv;
-            const long long off = (long long)z * a.zstride + (long long)xv * VEC;
+            const long long off = rs::item_offset<VEC>(i, nxv, a.zstride);
             double c[VEC], bv[L][VEC];
-            pt_load<VEC>(src + off, c);
+            rs::load<VEC>(src + off, c);
 #pragma unroll
             for (int j = 0; j < L; ++j) {
-                if (j > 0 || !store) pt_load<VEC>(bp[j] + off, bv[j]);
+                if (j > 0 || !store) rs::load<VEC>(bp[j] + off, bv[j]);
             }
 #pragma unroll
             for (int j = 0; j < VEC; ++j) c[j] -= mean;
@@ -156,7 +112,7 @@ __global__ __launch_bounds__(256) void k_plane_timecorr(PtArgs a) {
                 for (int q = 0; q < L; ++q) s[2 + q] += bv[q][j] * c[j];
             }
         }
-        pt_reduce<M, M, WAVE>(s, s_red, tid);
+        rs::reduce<M, M, WAVE>(s, s_red, tid);
 
         if (t0 == 0) {
             double* ga = a.acc + (row * a.K + k) * (long long)a.lags * 4;
@@ -182,14 +138,9 @@ __global__ __launch_bounds__(256) void k_plane_timecorr(PtArgs a) {
 
 template <int L>
 void pt_launch(const PtArgs& a, bool vec, bool wave, hipStream_t st) {
-    const dim3 grid((unsigned)(wave ? (a.rows + 3) / 4 : a.rows));
-    if (vec) {
-        if (wave) hipLaunchKernelGGL((k_plane_timecorr<L, PT_VEC, true>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((k_plane_timecorr<L, PT_VEC, false>), grid, dim3(256), 0, st, a);
-    } else {
-        if (wave) hipLaunchKernelGGL((k_plane_timecorr<L, 1, true>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((k_plane_timecorr<L, 1, false>), grid, dim3(256), 0, st, a);
-    }
+    rs::launch(a.rows, vec, wave, [&](dim3 grid, auto v, auto w) {
+        hipLaunchKernelGGL((k_plane_timecorr<L, decltype(v)::value, decltype(w)::value>), grid, dim3(256), 0, st, a);
+    });
 }
 
 }  // namespace
@@ -203,19 +154,12 @@ extern "C" int fg_plane_timecorr(const fg_real* const* channels, const int64_t* 
     FG_REQUIRE(lags >= 1, FG_ERR_INVALID_ARG, "fg_plane_timecorr: lags must be positive");
     FG_REQUIRE(n_slots >= 1 && n_slots <= PT_MAX_SLOTS, FG_ERR_INVALID_ARG, "fg_plane_timecorr: n_slots must be 1..8");
     FG_REQUIRE(batch > 0 && nz > 0 && ny > 0 && nx > 0, FG_ERR_INVALID_ARG, "fg_plane_timecorr: batch, nz, ny, nx must be positive");
-    FG_REQUIRE((long long)nz * nx <= (1LL << 30), FG_ERR_INVALID_ARG, "fg_plane_timecorr: a plane of more than 2^30 cells");
-    FG_REQUIRE((long long)batch * ny <= 0x7fffffffLL, FG_ERR_INVALID_ARG, "fg_plane_timecorr: batch * ny too large for one launch");
     const long long field = (long long)nz * ny * nx;
     PtArgs a;
-    bool vec = nx % PT_VEC == 0 && (uintptr_t)base % 16 == 0;
-    for (int k = 0; k < PT_MAX_K; ++k) {
-        a.ch[k] = nullptr; a.bstride[k] = 0;
-        if (k >= K) continue;
-        FG_REQUIRE(channels[k], FG_ERR_INVALID_ARG, "fg_plane_timecorr: null channel pointer");
-        FG_REQUIRE(batch_stride[k] >= field, FG_ERR_INVALID_ARG, "fg_plane_timecorr: batch stride smaller than nz * ny * nx");
-        a.ch[k] = channels[k]; a.bstride[k] = (long long)batch_stride[k];
-        vec = vec && ((uintptr_t)channels[k] % 16 == 0) && (batch_stride[k] % PT_VEC == 0);
-    }
+    bool vec;
+    const int rc = rs::fill_rows(a.t, vec, "fg_plane_timecorr", "channel", channels, batch_stride, K, batch, nz, ny, nx);
+    if (rc != FG_OK) return rc;
+    vec = vec && (uintptr_t)base % 16 == 0;
     // the live slots, the one at lag 0 first
     int live = 0;
     a.store = 0;
@@ -237,7 +181,7 @@ extern "C" int fg_plane_timecorr(const fg_real* const* channels, const int64_t* 
     a.zstride = (long long)ny * nx; a.rows = (long long)batch * ny; a.field = field;
     a.nz = nz; a.ny = ny; a.nx = nx; a.K = K; a.batch = batch; a.lags = lags;
     a.base = base; a.base_ss = base_ss; a.acc = acc;
-    const bool wave = (long long)nz * nx <= PT_WAVE_CELLS;
+    const bool wave = (long long)nz * nx <= rs::WAVE_CELLS;
     hipStream_t st = (hipStream_t)stream;
     switch (live) {
         case 1: pt_launch<1>(a, vec, wave, st); break;

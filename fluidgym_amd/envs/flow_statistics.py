@@ -26,6 +26,26 @@ from ..simulation.plane_stats import CHANNEL_SETS, PlaneMoments
 from ..simulation.plane_timecorr import PlaneTimeCorrelation
 
 
+def _check_start(env, entry: str, every: int, single_block: Optional[str] = None, needs_3d: bool = False) -> None:
+    """The checks every ``start_*`` begins with: reset() done, (``single_block``: what needs one) a single-block domain, (``needs_3d``)
+    a 3-D one, ``every`` at least 1."""
+    if getattr(env, "_domain", None) is None:
+        raise RuntimeError(f"{entry}: reset() the env first (the domain does not exist yet)")
+    if single_block is not None and env._flow_blocks() != 1:
+        raise NotImplementedError(f"{single_block} need a single-block domain")
+    if needs_3d and env._ndims != 3:
+        raise NotImplementedError(f"{single_block} need a 3-D domain")
+    if int(every) < 1:
+        raise ValueError(f"every must be at least 1, got {every}")
+
+
+def _due(env, name: str) -> bool:
+    """Count a sim step for the recorder ``name``; True at every ``every``-th one."""
+    tick = getattr(env, name + "_tick") + 1
+    setattr(env, name + "_tick", tick)
+    return tick % getattr(env, name + "_every") == 0
+
+
 class FlowStatisticsMixin:
     _flow_stats: Optional[PlaneMoments] = None      # None (the default): the step path does nothing for the statistics
     _flow_stats_every: int = 1
@@ -43,12 +63,7 @@ class FlowStatisticsMixin:
 
     def start_flow_statistics(self, order: int = 2, every: int = 1) -> None:
         """Start a fresh record of moments up to ``order``; a sample is taken after every ``every``-th sim step of ``step()``."""
-        if getattr(self, "_domain", None) is None:
-            raise RuntimeError("start_flow_statistics: reset() the env first (the domain does not exist yet)")
-        if self._flow_blocks() != 1:
-            raise NotImplementedError("flow statistics need a single-block domain")
-        if int(every) < 1:
-            raise ValueError(f"every must be at least 1, got {every}")
+        _check_start(self, "start_flow_statistics", every, "flow statistics")
         self._flow_stats = PlaneMoments(self._flow_channels(), order)
         self._flow_stats_every, self._flow_stats_tick = int(every), 0
 
@@ -68,8 +83,7 @@ class FlowStatisticsMixin:
 
     def _record_flow_sample(self) -> None:
         """Called after a sim step while statistics are active."""
-        self._flow_stats_tick += 1
-        if self._flow_stats_tick % self._flow_stats_every:
+        if not _due(self, "_flow_stats"):
             return
         blk = self._domain.getBlock(0)
         self._flow_stats.update(blk.velocity, blk.pressure, blk.passiveScalar if self._flow_stats_scalar else None)
@@ -77,12 +91,7 @@ class FlowStatisticsMixin:
     def start_flow_spectra(self, planes: Sequence[int], every: int = 1, symmetric: bool = True) -> None:
         """Start a fresh record of the wavenumber spectra of the rows ``planes`` (and, ``symmetric``, of their mirror images) of
         the channels of the moments; a sample is taken after every ``every``-th sim step of ``step()``."""
-        if getattr(self, "_domain", None) is None:
-            raise RuntimeError("start_flow_spectra: reset() the env first (the domain does not exist yet)")
-        if self._flow_blocks() != 1:
-            raise NotImplementedError("flow spectra need a single-block domain")
-        if int(every) < 1:
-            raise ValueError(f"every must be at least 1, got {every}")
+        _check_start(self, "start_flow_spectra", every, "flow spectra")
         vel = self._domain.getBlock(0).velocity
         nz, ny, nx = ((1,) + tuple(int(s) for s in vel.shape[2:]))[-3:]
         check_extents(nz, nx, vel.element_size(), "start_flow_spectra")
@@ -100,8 +109,7 @@ class FlowStatisticsMixin:
 
     def _record_spectra_sample(self) -> None:
         """Called after a sim step while spectra are active."""
-        self._flow_spectra_tick += 1
-        if self._flow_spectra_tick % self._flow_spectra_every:
+        if not _due(self, "_flow_spectra"):
             return
         blk = self._domain.getBlock(0)
         self._flow_spectra.update(blk.velocity, blk.pressure, blk.passiveScalar if self._flow_stats_scalar else None)
@@ -110,14 +118,7 @@ class FlowStatisticsMixin:
         """Start a fresh record of the Reynolds-stress budgets; a sample is taken after every ``every``-th sim step of ``step()``.
         The coordinates are the block's cell centres, periodic x / z faces wrap, ``forcing`` defaults to whether the block has a
         velocity source."""
-        if getattr(self, "_domain", None) is None:
-            raise RuntimeError("start_flow_budgets: reset() the env first (the domain does not exist yet)")
-        if self._flow_blocks() != 1:
-            raise NotImplementedError("flow budgets need a single-block domain")
-        if self._ndims != 3:
-            raise NotImplementedError("flow budgets need a 3-D domain")
-        if int(every) < 1:
-            raise ValueError(f"every must be at least 1, got {every}")
+        _check_start(self, "start_flow_budgets", every, "flow budgets", needs_3d=True)
         blk = self._domain.getBlock(0)
         if forcing is None:
             forcing = blk.velocitySource is not None
@@ -136,8 +137,7 @@ class FlowStatisticsMixin:
 
     def _record_budgets_sample(self) -> None:
         """Called after a sim step while budgets are active."""
-        self._flow_budgets_tick += 1
-        if self._flow_budgets_tick % self._flow_budgets_every:
+        if not _due(self, "_flow_budgets"):
             return
         blk = self._domain.getBlock(0)
         self._flow_budgets.update(blk.velocity, blk.pressure, blk.velocitySource if self._flow_budgets.forcing else None)
@@ -147,12 +147,7 @@ class FlowStatisticsMixin:
         """Start a fresh record of the temporal correlations over ``lags`` samples; a sample is taken after every ``every``-th sim
         step of ``step()``.  ``stride`` None: one base at the first sample, as the reference; ``stride = S``: a new base at every
         ``S``-th sample.  ``channels`` default to the velocity components; any channel set of the moments is taken."""
-        if getattr(self, "_domain", None) is None:
-            raise RuntimeError("start_flow_time_correlation: reset() the env first (the domain does not exist yet)")
-        if self._flow_blocks() != 1:
-            raise NotImplementedError("flow time correlations need a single-block domain")
-        if int(every) < 1:
-            raise ValueError(f"every must be at least 1, got {every}")
+        _check_start(self, "start_flow_time_correlation", every, "flow time correlations")
         velocity = ("u", "v") + (("w",) if self._ndims == 3 else ())
         channels = velocity if channels is None else tuple(channels)
         if channels != velocity and (channels not in CHANNEL_SETS or ("w" in channels) != (self._ndims == 3)):
@@ -171,8 +166,7 @@ class FlowStatisticsMixin:
 
     def _record_time_correlation_sample(self) -> None:
         """Called after a sim step while time correlations are active; the sample's time is the simulation's host-side clock."""
-        self._flow_timecorr_tick += 1
-        if self._flow_timecorr_tick % self._flow_timecorr_every:
+        if not _due(self, "_flow_timecorr"):
             return
         blk = self._domain.getBlock(0)
         corr = self._flow_timecorr
@@ -188,10 +182,7 @@ class FieldStatisticsMixin:
     def start_field_statistics(self, every: int = 1, span_average: bool = True) -> None:
         """Start a fresh per-cell record of ``u, v(, w), p``; a sample is taken after every ``every``-th sim step of ``step()``.
         ``span_average`` (3-D): one column per ``(block, y, x)``, averaged over the span; off, every cell is recorded."""
-        if getattr(self, "_domain", None) is None:
-            raise RuntimeError("start_field_statistics: reset() the env first (the domain does not exist yet)")
-        if int(every) < 1:
-            raise ValueError(f"every must be at least 1, got {every}")
+        _check_start(self, "start_field_statistics", every)
         self._field_stats = CellMoments.for_domain(self._domain, span_average)
         self._field_stats_every, self._field_stats_tick = int(every), 0
 
@@ -204,7 +195,6 @@ class FieldStatisticsMixin:
 
     def _record_field_sample(self) -> None:
         """Called after a sim step while field statistics are active; the fields are read, never written."""
-        self._field_stats_tick += 1
-        if self._field_stats_tick % self._field_stats_every:
+        if not _due(self, "_field_stats"):
             return
         self._field_stats.update(self._domain.velocity, self._domain.pressure)

@@ -40,6 +40,7 @@ import numpy as np
 import torch
 
 from .. import _lib as L
+from . import plane_fields as F
 from .plane_stats import merge_moments
 
 MAX_BLOCKS = 8                          # CM_MAX_BLOCKS of csrc/fg_cellstats.hip
@@ -339,11 +340,9 @@ class CellMoments(CellRecord):
                          torch.empty(B, self.P, self.NC, dtype=torch.float64, device=dev))
         elif self._dev[0].shape[0] != B or self._dev[0].device != dev:
             raise ValueError(f"{what}: batch size or device changed between updates")
-        lib = L.load_f64() if velocity.dtype == torch.float64 else L.load()
+        lib = F.library(velocity.dtype)
         mean, cen = self._dev
         with torch.cuda.device(dev):
-            L.check(lib.fg_mb_cell_moments(ctypes.c_void_p(velocity.data_ptr()), ctypes.c_void_p(pressure.data_ptr()), self.dims, B,
-                                           int(velocity.shape[2]), self._table, len(self.blocks), self.samples,
-                                           ctypes.c_void_p(mean.data_ptr()), ctypes.c_void_p(cen.data_ptr()),
-                                           ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), lib=lib)
+            L.check(lib.fg_mb_cell_moments(F.ptr(velocity), F.ptr(pressure), self.dims, B, int(velocity.shape[2]), self._table,
+                                           len(self.blocks), self.samples, F.ptr(mean), F.ptr(cen), F.stream_ptr(dev)), lib=lib)
         self.samples += 1

@@ -31,7 +31,6 @@ ghost position).  The reference's ``_data_grad2`` computes its upper one-sided d
 """
 from __future__ import annotations
 
-import ctypes
 import json
 import os
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -40,6 +39,7 @@ import numpy as np
 import torch
 
 from .. import _lib as L
+from . import plane_fields as F
 
 K_BASE, K_FORCING = 15, 18
 FILE_MOMENTS, FILE_GRAD, FILE_META = "budgets_moments.npz", "budgets_grad_%04d.npz", "plane_budgets.json"
@@ -161,7 +161,7 @@ def merge_budgets(nA, meanA, cenA, nB, meanB, cenB, keys):
     return n, mean, cen
 
 
-class BudgetRecord:
+class BudgetRecord(F.WallUnits):
     """Accessors, merging, wall units and files of a record ``n [B]``, ``mean [B, ny, K]``, ``central [B, ny, M]`` on the rows
     ``y``; the two accumulators below say where the arrays live.  Indices ``i, j, k`` are 0..2; every accessor returns ``[B, ny]``."""
 
@@ -176,8 +176,6 @@ class BudgetRecord:
         self.keys = budget_keys(self.forcing)
         self.M = len(self.keys)
         self._index = {k: q for q, k in enumerate(self.keys)}
-        self.y_centers: Optional[np.ndarray] = None       # wall units: cell centres of the rows, walls at y = -1 and +1
-        self.viscosity: Optional[float] = None
 
     # ---- where the arrays live: overridden by PlaneBudgets
     _n = _mean = _central = None
@@ -203,24 +201,7 @@ class BudgetRecord:
         """A host copy of the current state."""
         return self._like(*(np.array(v) for v in self._state()))
 
-    # ---- wall units (as PlaneRecord): walls at y = -1 and y = +1
-    def set_wall_units(self, y_centers, viscosity: float) -> "BudgetRecord":
-        self.y_centers, self.viscosity = np.asarray(y_centers, np.float64).copy(), float(viscosity)
-        return self
-
-    def _need_wall(self):
-        if self.y_centers is None or self.viscosity is None:
-            raise RuntimeError("wall units need set_wall_units(y_centers, viscosity)")
-        return self.y_centers, self.viscosity
-
-    def u_wall(self) -> np.ndarray:
-        """Friction velocity per env ``[B]`` from the mean-``u`` rows next to the two walls."""
-        y, nu = self._need_wall()
-        u = self._state()[1][..., 0]
-        if len(y) != u.shape[1]:
-            raise RuntimeError("u_wall needs both walls: take it before half_channel()")
-        return np.sqrt(0.5 * (u[:, 0] / (1.0 + y[0]) + u[:, -1] / (1.0 - y[-1])) * nu)
-
+    # ---- wall units: set_wall_units, _need_wall and u_wall of plane_fields.WallUnits
     _u_wall_fixed: Optional[np.ndarray] = None            # set by half_channel(): the fold has lost the upper wall
 
     def _scale(self, vel_order: int, derivatives: int, as_wall: bool):
@@ -468,41 +449,25 @@ class HostPlaneBudgets(BudgetRecord):
         self._set_state(n[:, 0], m, c)
 
 
-class PlaneBudgets(BudgetRecord):
+class PlaneBudgets(F.DeviceState, BudgetRecord):
     """The GPU accumulator.  ``update(velocity, pressure, source=None)`` takes the domain's own tensors (``[B, 3, Z, Y, X]``,
     ``[B, 1, Z, Y, X]``, ``[B, 3, Z, Y, X]``; float32 -> ``libfluidgym_hip.so``, float64 -> the fp64 library), reads their component
     slices in place and runs one launch on the current stream; nothing comes back to the host until an accessor is called."""
 
-    def __init__(self, x, y, z, forcing: bool = False, wrap: Tuple[bool, bool] = (True, True)):
-        super().__init__(x, y, z, forcing, wrap)
-        self._dev = None     # (n [B], mean [B, ny, K], central [B, ny, M], tickets [B], x, y, z) on the device
-        self._shape = None
-
-    def _unset(self) -> bool:
-        return self._dev is None
+    _merge_into = "a HostPlaneBudgets"
+    # _dev: (n [B], mean [B, ny, K], central [B, ny, M], tickets [B], x, y, z) on the device
 
     def _state(self):
-        if self._dev is None:
-            raise RuntimeError("no sample recorded yet")
-        return tuple(t.cpu().numpy() for t in self._dev[:3])
+        return self._read(3)
 
     def _set_state(self, n, mean, central) -> None:
-        if self._dev is None:
-            raise RuntimeError("PlaneBudgets takes a state only after its first update (merge into a HostPlaneBudgets instead)")
-        for t, v in zip(self._dev[:3], (n, mean, central)):
-            t.copy_(torch.as_tensor(np.ascontiguousarray(v, np.float64)).reshape(t.shape))
+        self._write(n, mean, central)
 
     def update(self, velocity: torch.Tensor, pressure: torch.Tensor, source: Optional[torch.Tensor] = None) -> None:
         what = "PlaneBudgets.update"
         if not self.forcing:
             source = None
-        for t in (velocity, pressure) + ((source,) if self.forcing else ()):
-            if not isinstance(t, torch.Tensor) or not t.is_cuda:
-                raise ValueError(f"{what}: the fields must be tensors on the GPU (HostPlaneBudgets takes host arrays)")
-            if t.dtype != velocity.dtype or t.device != velocity.device:
-                raise TypeError(f"{what}: all fields need one dtype and device")
-        if velocity.dtype not in (torch.float32, torch.float64):
-            raise TypeError(f"{what}: float32 or float64 fields, got {velocity.dtype}")
+        F.check_device_fields((velocity, pressure) + ((source,) if self.forcing else ()), what, "HostPlaneBudgets")
         B, _, nz, ny, nx = self._check_fields(velocity, pressure, source, what)
         dev = velocity.device
         if self._dev is None:
@@ -512,20 +477,14 @@ class PlaneBudgets(BudgetRecord):
                          torch.zeros(B, dtype=torch.int64, device=dev)) + tuple(torch.as_tensor(c).to(**f64) for c in (self.x, self.y, self.z))
         elif self._shape != (B, nz, ny, nx, dev):
             raise ValueError(f"{what}: batch size, grid or device changed between updates")
-        cells = nz * ny * nx
-        item = velocity.element_size()
         vel, prs = velocity.contiguous(), pressure.contiguous()
         parts = [(vel, 0), (vel, 1), (vel, 2), (prs, 0)]
         if self.forcing:
             src = source.contiguous()
             parts += [(src, 0), (src, 1), (src, 2)]
-        ptrs = (ctypes.c_void_p * len(parts))(*[t.data_ptr() + c * cells * item for t, c in parts])
-        strides = (ctypes.c_int64 * len(parts))(*[int(t.shape[1]) * cells for t, _ in parts])
-        lib = L.load_f64() if velocity.dtype == torch.float64 else L.load()
+        ptrs, strides = F.channel_table(parts, nz * ny * nx)
+        lib = F.library(velocity.dtype)
         n, mean, cen, tickets, dx, dy, dz = self._dev
         with torch.cuda.device(dev):
-            L.check(lib.fg_plane_budgets(ptrs, strides, len(parts), B, nz, ny, nx, ctypes.c_void_p(dx.data_ptr()),
-                                         ctypes.c_void_p(dy.data_ptr()), ctypes.c_void_p(dz.data_ptr()), int(self.wrap[0]),
-                                         int(self.wrap[1]), ctypes.c_void_p(n.data_ptr()), ctypes.c_void_p(mean.data_ptr()),
-                                         ctypes.c_void_p(cen.data_ptr()), ctypes.c_void_p(tickets.data_ptr()),
-                                         ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), lib=lib)
+            L.check(lib.fg_plane_budgets(ptrs, strides, len(parts), B, nz, ny, nx, F.ptr(dx), F.ptr(dy), F.ptr(dz), int(self.wrap[0]),
+                                         int(self.wrap[1]), F.ptr(n), F.ptr(mean), F.ptr(cen), F.ptr(tickets), F.stream_ptr(dev)), lib=lib)

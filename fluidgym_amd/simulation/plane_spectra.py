@@ -22,6 +22,8 @@ import numpy as np
 import torch
 
 from .. import _lib as L
+from . import plane_fields as F
+from .plane_fields import gather as _gather      # (the correlations take it from here)
 
 CHANNEL_NAMES = ("u", "v", "w", "p", "T")
 MAX_PLANES = 32
@@ -45,22 +47,6 @@ def check_extents(nz: int, nx: int, itemsize: Optional[int] = None, what: str = 
     if itemsize is not None and lds_bytes(nz, nx, itemsize) > LDS_LIMIT:
         raise ValueError(f"{what}: the slab of {nz} x ({nx} / 2 + 1) complex {'doubles' if itemsize == 8 else 'floats'} with its work "
                          f"buffers must fit in 160 KB of LDS, it takes {lds_bytes(nz, nx, itemsize)} bytes")
-
-
-def _gather(channels, velocity, pressure, scalar, what: str):
-    """(tensor, component) of every channel: views of the domain's ``[B, C, (Z,) Y, X]`` tensors."""
-    if velocity.ndim not in (4, 5):
-        raise ValueError(f"{what}: velocity must be [B, d, (Z,) Y, X]; multi-block domains (flat [B, d, N] fields) are not supported")
-    d = velocity.shape[1]
-    if d != velocity.ndim - 2 or ("w" in channels and d != 3):
-        raise ValueError(f"{what}: channels {channels} do not fit a velocity of shape {tuple(velocity.shape)}")
-    if "p" in channels and (pressure is None or tuple(pressure.shape) != (velocity.shape[0], 1) + tuple(velocity.shape[2:])):
-        raise ValueError(f"{what}: pressure must be [B, 1, (Z,) Y, X] on the velocity's grid")
-    if "T" in channels and (scalar is None or scalar.ndim != velocity.ndim or tuple(scalar.shape[2:]) != tuple(velocity.shape[2:])
-                            or scalar.shape[0] != velocity.shape[0]):
-        raise ValueError(f"{what}: channel T needs the passive scalar [B, S, (Z,) Y, X]")
-    src = {"u": (velocity, 0), "v": (velocity, 1), "w": (velocity, 2), "p": (pressure, 0), "T": (scalar, 0)}
-    return [src[c] for c in channels]
 
 
 class SpectraRecord:
@@ -266,47 +252,29 @@ class HostPlaneSpectra(SpectraRecord):
         self.samples += 1
 
 
-class PlaneSpectra(SpectraRecord):
+class PlaneSpectra(F.DeviceState, SpectraRecord):
     """The GPU accumulator.  ``update(velocity, pressure, scalar=None)`` takes the domain's own tensors (``[B, d, (Z,) Y, X]``,
     ``[B, 1, ...]``, ``[B, S, ...]``; float32 -> ``libfluidgym_hip.so``, float64 -> the fp64 library), reads their component slices in
     place and runs one launch on the current stream; nothing comes back to the host until an accessor is called."""
 
-    def __init__(self, channels: Sequence[str] = ("u", "v", "w", "p"), planes: Sequence[int] = (0,), symmetric: bool = True):
-        super().__init__(channels, planes, symmetric)
-        self._dev = None       # (amp, power) [B, K, T, nkz, nkx] on the device
-        self._counts = None    # [B] on the host: the kernel keeps sums, the samples are counted here
-        self._shape = None
-
-    def _unset(self) -> bool:
-        return self._dev is None
+    _merge_into = "a HostPlaneSpectra"
+    # _dev: (amp, power) [B, K, T, nkz, nkx] on the device
+    _counts = None         # [B] on the host: the kernel keeps sums, the samples are counted here
 
     def _state(self):
-        if self._dev is None:
-            raise RuntimeError("no sample recorded yet")
-        return (self._counts,) + tuple(t.cpu().numpy() for t in self._dev)
+        return (self._counts,) + self._read(2)
 
     def _set_state(self, count, amp, power) -> None:
-        if self._dev is None:
-            raise RuntimeError("PlaneSpectra takes a state only after its first update (merge into a HostPlaneSpectra instead)")
+        self._write(amp, power)
         self._counts = np.ascontiguousarray(count, np.float64)
-        for t, v in zip(self._dev, (amp, power)):
-            t.copy_(torch.as_tensor(np.ascontiguousarray(v, np.float64)).reshape(t.shape))
 
     def update(self, velocity: torch.Tensor, pressure: Optional[torch.Tensor] = None, scalar: Optional[torch.Tensor] = None) -> None:
         what = "PlaneSpectra.update"
         used = (velocity,) + ((pressure,) if "p" in self.channels else ()) + ((scalar,) if "T" in self.channels else ())
-        for t in used:
-            if not isinstance(t, torch.Tensor) or not t.is_cuda:
-                raise ValueError(f"{what}: the fields must be tensors on the GPU (HostPlaneSpectra takes host arrays)")
-            if t.dtype != velocity.dtype or t.device != velocity.device:
-                raise TypeError(f"{what}: all fields need one dtype and device")
-        if velocity.dtype not in (torch.float32, torch.float64):
-            raise TypeError(f"{what}: float32 or float64 fields, got {velocity.dtype}")
+        F.check_device_fields(used, what, "HostPlaneSpectra")
         parts = [(t.contiguous(), c) for t, c in _gather(self.channels, velocity, pressure, scalar, what)]
-        B = int(velocity.shape[0])
-        nz, ny, nx = ((1,) + tuple(int(s) for s in velocity.shape[2:]))[-3:]
-        item = velocity.element_size()
-        check_extents(nz, nx, item, what)
+        B, nz, ny, nx = F.grid_of(velocity)
+        check_extents(nz, nx, velocity.element_size(), what)
         table = self.plane_table(ny)
         dev = velocity.device
         if self._dev is None:
@@ -317,15 +285,12 @@ class PlaneSpectra(SpectraRecord):
             self._counts = np.zeros(B)
         elif self._shape != (B, nz, ny, nx, dev):
             raise ValueError(f"{what}: batch size, grid or device changed between updates")
-        cells = nz * ny * nx
-        ptrs = (ctypes.c_void_p * self.K)(*[t.data_ptr() + c * cells * item for t, c in parts])
-        strides = (ctypes.c_int64 * self.K)(*[int(t.shape[1]) * cells for t, _ in parts])
+        ptrs, strides = F.channel_table(parts, nz * ny * nx)
         rows = (ctypes.c_int32 * len(table))(*table)
-        lib = L.load_f64() if velocity.dtype == torch.float64 else L.load()
+        lib = F.library(velocity.dtype)
         amp, power = self._dev
         with torch.cuda.device(dev):
-            L.check(lib.fg_plane_spectra(ptrs, strides, self.K, B, nz, ny, nx, rows, len(table), ctypes.c_void_p(amp.data_ptr()),
-                                         ctypes.c_void_p(power.data_ptr()),
-                                         ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), lib=lib)
+            L.check(lib.fg_plane_spectra(ptrs, strides, self.K, B, nz, ny, nx, rows, len(table), F.ptr(amp), F.ptr(power),
+                                         F.stream_ptr(dev)), lib=lib)
         self._counts = self._counts + 1.0
         self.samples += 1

@@ -20,7 +20,6 @@ data already lives on the host).  Both share the accessors, ``merge`` / ``pooled
 """
 from __future__ import annotations
 
-import ctypes
 import json
 import os
 from typing import List, Optional, Sequence, Tuple, Union
@@ -29,6 +28,7 @@ import numpy as np
 import torch
 
 from .. import _lib as L
+from . import plane_fields as F
 
 CHANNEL_SETS = (("u", "v", "p"), ("u", "v", "p", "T"), ("u", "v", "w", "p"), ("u", "v", "w", "p", "T"))
 # file names of VelocityStats.save_vel_stats (TCF_tools.py:1764-1779)
@@ -96,7 +96,7 @@ def sample_moments(values: np.ndarray, order: int):
     return float(cells), np.moveaxis(mean, 0, -1).copy(), np.stack(cen, axis=-1)
 
 
-class PlaneRecord:
+class PlaneRecord(F.WallUnits):
     """Accessors, merging, wall units and files of a record ``n [B]``, ``mean [B, ny, K]``, ``central [B, ny, M]``; the two
     accumulators below say where the arrays live."""
 
@@ -111,8 +111,6 @@ class PlaneRecord:
         self.keys = moment_keys(self.K, self.order)
         self.M = len(self.keys)
         self._index = {k: q for q, k in enumerate(self.keys)}
-        self.y_centers: Optional[np.ndarray] = None       # wall units: cell centres of the rows, walls at y = -1 and +1
-        self.viscosity: Optional[float] = None
 
     # ---- where the arrays live: overridden by PlaneMoments
     def _state(self):
@@ -225,25 +223,7 @@ class PlaneRecord:
         r.y_centers = None if self.y_centers is None else np.asarray(self.y_centers)[:h]
         return r
 
-    # ---- wall units (VelocityStats, TCF_tools.py:462-482, 1465-1478): walls at y = -1 and y = +1
-    def set_wall_units(self, y_centers, viscosity: float) -> "PlaneRecord":
-        self.y_centers, self.viscosity = np.asarray(y_centers, np.float64).copy(), float(viscosity)
-        return self
-
-    def _need_wall(self):
-        if self.y_centers is None or self.viscosity is None:
-            raise RuntimeError("wall units need set_wall_units(y_centers, viscosity)")
-        return self.y_centers, self.viscosity
-
-    def u_wall(self) -> np.ndarray:
-        """Friction velocity per env ``[B]`` from the mean-``u`` rows next to the two walls (``get_avg_u_wall``)."""
-        y, nu = self._need_wall()
-        if len(y) != self._state()[1].shape[1]:
-            raise RuntimeError("u_wall needs both walls: take it before half_channel()")
-        u = self.mean("u")
-        dudy = 0.5 * (u[:, 0] / (1.0 + y[0]) + u[:, -1] / (1.0 - y[-1]))
-        return np.sqrt(dudy * nu)
-
+    # ---- wall units: set_wall_units, _need_wall and u_wall of plane_fields.WallUnits
     def Re_wall(self) -> np.ndarray:
         return self.u_wall() / self._need_wall()[1]
 
@@ -313,19 +293,8 @@ class PlaneRecord:
 
 
 def _gather(channels, velocity, pressure, scalar, what: str):
-    """The per-channel fields ``[B, (Z,) Y, X]`` (views) of the domain's tensors ``[B, C, (Z,) Y, X]``."""
-    if velocity.ndim not in (4, 5):
-        raise ValueError(f"{what}: velocity must be [B, d, (Z,) Y, X]; multi-block domains (flat [B, d, N] fields) are not supported")
-    d = velocity.shape[1]
-    if d != velocity.ndim - 2 or ("w" in channels) != (d == 3):
-        raise ValueError(f"{what}: channels {channels} do not fit a velocity of shape {tuple(velocity.shape)}")
-    if pressure is None or tuple(pressure.shape) != (velocity.shape[0], 1) + tuple(velocity.shape[2:]):
-        raise ValueError(f"{what}: pressure must be [B, 1, (Z,) Y, X] on the velocity's grid")
-    if "T" in channels:
-        if scalar is None or scalar.ndim != velocity.ndim or tuple(scalar.shape[2:]) != tuple(velocity.shape[2:]):
-            raise ValueError(f"{what}: channel T needs the passive scalar [B, S, (Z,) Y, X]")
-    src = {"u": (velocity, 0), "v": (velocity, 1), "w": (velocity, 2), "p": (pressure, 0), "T": (scalar, 0)}
-    return [src[c] for c in channels]
+    """The moments record u, v(, w) and p of every field: a pressure always, ``w`` exactly in 3-D."""
+    return F.gather(channels, velocity, pressure, scalar, what, pressure_required=True, w_exact=True)
 
 
 class HostPlaneMoments(PlaneRecord):
@@ -349,43 +318,25 @@ class HostPlaneMoments(PlaneRecord):
         self._set_state(n[:, 0], m, c)
 
 
-class PlaneMoments(PlaneRecord):
+class PlaneMoments(F.DeviceState, PlaneRecord):
     """The GPU accumulator.  ``update(velocity, pressure, scalar=None)`` takes the domain's own tensors (``[B, d, (Z,) Y, X]``,
     ``[B, 1, ...]``, ``[B, S, ...]``; float32 -> ``libfluidgym_hip.so``, float64 -> the fp64 library), reads their component slices in
     place and runs one launch on the current stream; nothing comes back to the host until an accessor is called."""
 
-    def __init__(self, channels: Sequence[str] = ("u", "v", "w", "p"), order: int = 2):
-        super().__init__(channels, order)
-        self._dev = None     # (n [B], mean [B, ny, K], central [B, ny, M], tickets [B]) on the device
-        self._shape = None
-
-    def _unset(self) -> bool:
-        return self._dev is None
+    _merge_into = "a HostPlaneMoments"
+    # _dev: (n [B], mean [B, ny, K], central [B, ny, M], tickets [B]) on the device
 
     def _state(self):
-        if self._dev is None:
-            raise RuntimeError("no sample recorded yet")
-        return tuple(t.cpu().numpy() for t in self._dev[:3])
+        return self._read(3)
 
     def _set_state(self, n, mean, central) -> None:
-        if self._dev is None:
-            raise RuntimeError("PlaneMoments takes a state only after its first update (merge into a HostPlaneMoments instead)")
-        for t, v in zip(self._dev[:3], (n, mean, central)):
-            t.copy_(torch.as_tensor(np.ascontiguousarray(v, np.float64)).reshape(t.shape))
+        self._write(n, mean, central)
 
     def update(self, velocity: torch.Tensor, pressure: torch.Tensor, scalar: Optional[torch.Tensor] = None) -> None:
         what = "PlaneMoments.update"
-        for t in (velocity, pressure) + ((scalar,) if "T" in self.channels else ()):
-            if not isinstance(t, torch.Tensor) or not t.is_cuda:
-                raise ValueError(f"{what}: the fields must be tensors on the GPU (HostPlaneMoments takes host arrays)")
-            if t.dtype != velocity.dtype or t.device != velocity.device:
-                raise TypeError(f"{what}: all fields need one dtype and device")
-        if velocity.dtype not in (torch.float32, torch.float64):
-            raise TypeError(f"{what}: float32 or float64 fields, got {velocity.dtype}")
+        F.check_device_fields((velocity, pressure) + ((scalar,) if "T" in self.channels else ()), what, "HostPlaneMoments")
         parts = [(t.contiguous(), c) for t, c in _gather(self.channels, velocity, pressure, scalar, what)]
-        B = int(velocity.shape[0])
-        spatial = tuple(int(s) for s in velocity.shape[2:])
-        nz, ny, nx = ((1,) + spatial)[-3:]
+        B, nz, ny, nx = F.grid_of(velocity)
         dev = velocity.device
         if self._dev is None:
             self._shape = (B, nz, ny, nx, dev)
@@ -393,14 +344,9 @@ class PlaneMoments(PlaneRecord):
                          torch.empty(B, ny, self.M, dtype=torch.float64, device=dev), torch.zeros(B, dtype=torch.int64, device=dev))
         elif self._shape != (B, nz, ny, nx, dev):
             raise ValueError(f"{what}: batch size, grid or device changed between updates")
-        cells = nz * ny * nx
-        item = velocity.element_size()
-        ptrs = (ctypes.c_void_p * self.K)(*[t.data_ptr() + c * cells * item for t, c in parts])
-        strides = (ctypes.c_int64 * self.K)(*[int(t.shape[1]) * cells for t, _ in parts])
-        lib = L.load_f64() if velocity.dtype == torch.float64 else L.load()
+        ptrs, strides = F.channel_table(parts, nz * ny * nx)
+        lib = F.library(velocity.dtype)
         n, mean, cen, tickets = self._dev
         with torch.cuda.device(dev):
-            L.check(lib.fg_plane_moments(ptrs, strides, self.K, B, nz, ny, nx, self.order, ctypes.c_void_p(n.data_ptr()),
-                                         ctypes.c_void_p(mean.data_ptr()), ctypes.c_void_p(cen.data_ptr()),
-                                         ctypes.c_void_p(tickets.data_ptr()),
-                                         ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), lib=lib)
+            L.check(lib.fg_plane_moments(ptrs, strides, self.K, B, nz, ny, nx, self.order, F.ptr(n), F.ptr(mean), F.ptr(cen), F.ptr(tickets),
+                                         F.stream_ptr(dev)), lib=lib)

@@ -34,7 +34,9 @@ import numpy as np
 import torch
 
 from .. import _lib as L
-from .plane_spectra import CHANNEL_NAMES, _gather
+from . import plane_fields as F
+from .plane_fields import gather as _gather
+from .plane_spectra import CHANNEL_NAMES
 from .plane_stats import PlaneRecord
 
 MAX_SLOTS = 8
@@ -333,29 +335,20 @@ class HostPlaneTimeCorrelation(TimeCorrRecord):
             sample_timecorr(v, table, self._base, self._base_ss, self._acc)
 
 
-class PlaneTimeCorrelation(TimeCorrRecord):
+class PlaneTimeCorrelation(F.DeviceState, TimeCorrRecord):
     """The GPU accumulator.  ``update(velocity, pressure=None, scalar=None, time=...)`` takes the domain's own tensors
     (``[B, d, (Z,) Y, X]``, ``[B, 1, ...]``, ``[B, S, ...]``; float32 -> ``libfluidgym_hip.so``, float64 -> the fp64 library), reads
     their component slices in place and runs one launch on the current stream; ``time`` is a host scalar or per-env array, and nothing
     comes back to the host until an accessor is called."""
 
-    def __init__(self, channels: Sequence[str] = ("u", "v", "w"), lags: int = 1, stride: Optional[int] = None):
-        super().__init__(channels, lags, stride)
-        self._dev = None       # (acc [B, ny, K, lags, 4], base [n_slots, B, K, nz, ny, nx], base_ss [n_slots, B, ny, K]) on the device
-        self._shape = None
-
-    def _unset(self) -> bool:
-        return self._dev is None
+    _merge_into = "a record()"
+    # _dev: (acc [B, ny, K, lags, 4], base [n_slots, B, K, nz, ny, nx], base_ss [n_slots, B, ny, K]) on the device
 
     def _state(self) -> np.ndarray:
-        if self._dev is None:
-            raise RuntimeError("no sample recorded yet")
-        return self._dev[0].cpu().numpy()
+        return self._read(1)[0]
 
     def _set_state(self, acc) -> None:
-        if self._dev is None:
-            raise RuntimeError("PlaneTimeCorrelation takes a state only after its first update (merge into a record() instead)")
-        self._dev[0].copy_(torch.as_tensor(np.ascontiguousarray(acc, np.float64)).reshape(self._dev[0].shape))
+        self._write(acc)
 
     def _bases(self):
         self._state()
@@ -365,16 +358,9 @@ class PlaneTimeCorrelation(TimeCorrRecord):
                time=0.0) -> None:
         what = "PlaneTimeCorrelation.update"
         used = (velocity,) + ((pressure,) if "p" in self.channels else ()) + ((scalar,) if "T" in self.channels else ())
-        for t in used:
-            if not isinstance(t, torch.Tensor) or not t.is_cuda:
-                raise ValueError(f"{what}: the fields must be tensors on the GPU (HostPlaneTimeCorrelation takes host arrays)")
-            if t.dtype != velocity.dtype or t.device != velocity.device:
-                raise TypeError(f"{what}: all fields need one dtype and device")
-        if velocity.dtype not in (torch.float32, torch.float64):
-            raise TypeError(f"{what}: float32 or float64 fields, got {velocity.dtype}")
+        F.check_device_fields(used, what, "HostPlaneTimeCorrelation")
         parts = [(t.contiguous(), c) for t, c in _gather(self.channels, velocity, pressure, scalar, what)]
-        B = int(velocity.shape[0])
-        nz, ny, nx = ((1,) + tuple(int(s) for s in velocity.shape[2:]))[-3:]
+        B, nz, ny, nx = F.grid_of(velocity)
         dev = velocity.device
         if self._dev is not None and self._shape != (B, nz, ny, nx, dev, velocity.dtype):
             raise ValueError(f"{what}: batch size, grid, dtype or device changed between updates")
@@ -387,15 +373,10 @@ class PlaneTimeCorrelation(TimeCorrRecord):
                          torch.zeros(self.n_slots, B, ny, self.K, dtype=torch.float64, device=dev))
         if table is None:
             return
-        cells = nz * ny * nx
-        item = velocity.element_size()
-        ptrs = (ctypes.c_void_p * self.K)(*[t.data_ptr() + c * cells * item for t, c in parts])
-        strides = (ctypes.c_int64 * self.K)(*[int(t.shape[1]) * cells for t, _ in parts])
+        ptrs, strides = F.channel_table(parts, nz * ny * nx)
         slots = (ctypes.c_int32 * self.n_slots)(*table)
-        lib = L.load_f64() if velocity.dtype == torch.float64 else L.load()
+        lib = F.library(velocity.dtype)
         acc, base, base_ss = self._dev
         with torch.cuda.device(dev):
-            L.check(lib.fg_plane_timecorr(ptrs, strides, self.K, B, nz, ny, nx, self.lags, self.n_slots, slots,
-                                          ctypes.c_void_p(base.data_ptr()), ctypes.c_void_p(base_ss.data_ptr()),
-                                          ctypes.c_void_p(acc.data_ptr()),
-                                          ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), lib=lib)
+            L.check(lib.fg_plane_timecorr(ptrs, strides, self.K, B, nz, ny, nx, self.lags, self.n_slots, slots, F.ptr(base), F.ptr(base_ss),
+                                          F.ptr(acc), F.stream_ptr(dev)), lib=lib)
