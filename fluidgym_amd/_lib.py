@@ -32,6 +32,8 @@ FG_SOLVER_CG, FG_SOLVER_JACOBI, FG_SOLVER_RBGS, FG_SOLVER_MGCG, FG_SOLVER_FDCG =
 (FG_BUF_A, FG_BUF_C_OFF, FG_BUF_ADV_RHS, FG_BUF_VEL_RESULT, FG_BUF_H, FG_BUF_DIV, FG_BUF_P_RESULT,
  FG_BUF_SCALAR_RESULT) = range(8)
 FG_ERR_UNSUPPORTED = -4
+FG_ERR_INVALID_ARG = -1
+FG_ERR_NOT_BOUND = -2
 # forms_out of the debug preconditioner entries (include/fluidgym_hip.h FG_FORM_*): slots, then the codes per slot
 FG_FORM_SLOTS = 8
 FG_FORM_SLOT_X, FG_FORM_SLOT_Z, FG_FORM_SLOT_TRIDIAG, FG_FORM_SLOT_FACTORS, FG_FORM_SLOT_HELM, FG_FORM_SLOT_LINE = range(6)
@@ -67,6 +69,18 @@ class FgSolveInfo(Structure):
     def __repr__(self):
         return (f"FgSolveInfo(residual={self.final_residual:.3e}, iterations={self.used_iterations}, "
                 f"converged={bool(self.converged)}, finite={bool(self.is_finite)})")
+
+
+class FgEnvSel(Structure):
+    """One record of a per-env restore (``fg_env_sel``): env ``env`` := state ``src`` of the bank, mirrored, then rolled."""
+    _fields_ = [
+        ("env", c_int32),
+        ("src", c_int32),
+        ("flip_x", c_int32),
+        ("flip_z", c_int32),
+        ("shift_x", c_int32),
+        ("shift_z", c_int32),
+    ]
 
 
 class FgStepOptions(Structure):
@@ -175,6 +189,10 @@ SIGNATURES = {
     "fg_make_divergence_free": (c_int, [c_void_p, c_float, c_int, POINTER(FgSolveInfo), c_void_p]),
     "fg_reset_solver_state": (c_int, [c_void_p, c_void_p]),
     "fg_solver_hints": (c_int, [c_void_p, POINTER(c_int32), c_int32]),
+    "fg_env_restore_field": (c_int, [c_void_p, c_int, c_void_p, c_int32, POINTER(FgEnvSel), c_int32, c_int32, c_void_p]),
+    "fg_env_reset_solver_state": (c_int, [c_void_p, POINTER(FgEnvSel), c_int32, c_void_p]),
+    "fg_mb_env_restore_field": (c_int, [c_void_p, c_int, c_void_p, c_int32, POINTER(FgEnvSel), c_int32, c_int32, c_void_p]),
+    "fg_mb_env_reset_solver_state": (c_int, [c_void_p, POINTER(FgEnvSel), c_int32, c_void_p]),
     "fg_set_pressure_refinement": (c_int, [c_void_p, c_int32, c_float, c_float]),
     "fg_get_buffer": (c_int, [c_void_p, c_int, POINTER(c_void_p), POINTER(c_int64)]),
     "fg_read_buffer": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),

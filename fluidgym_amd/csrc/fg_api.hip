@@ -109,6 +109,7 @@ extern "C" int fg_create(const fg_config* cfg, const fg_real* hx, const fg_real*
     FG_HIP_CHECK(hipHostMalloc(&s->diag_pinned, sizeof(fg_real) * 2 * g.B));
     FG_HIP_CHECK(hipHostMalloc(&s->dt_pinned, sizeof(fg_real) * g.B));
     FG_HIP_CHECK(alloc(&s->dt_dev, g.B));
+    FG_HIP_CHECK(hipMalloc(&s->env_sel_dev, sizeof(fg_env_sel) * g.B));
     s->t_rem_dev = nullptr;
 #if !FG_F64
     FG_HIP_CHECK(hipMalloc(&s->t_rem_dev, sizeof(double) * g.B));
@@ -181,7 +182,7 @@ extern "C" int fg_destroy(fg_handle s) {
     (void)hipHostFree(s->info_pinned); (void)hipHostFree(s->flags_pinned);
     fg_prof_destroy(s);
     fg_poll_destroy(&s->poll);
-    (void)hipFree(s->d_bvel_ptrs); (void)hipHostFree(s->diag_pinned); (void)hipHostFree(s->dt_pinned); (void)hipFree(s->dt_dev); (void)hipFree(s->t_rem_dev);
+    (void)hipFree(s->d_bvel_ptrs); (void)hipHostFree(s->diag_pinned); (void)hipHostFree(s->dt_pinned); (void)hipFree(s->dt_dev); (void)hipFree(s->t_rem_dev); (void)hipFree(s->env_sel_dev);
     float* fd[] = {s->fd_Qx, s->fd_QxT, s->fd_Qz, s->fd_QzT, s->fd_lower, s->fd_inv, s->fd_cp};
     for (float* p : fd) if (p) (void)hipFree(p);
     if (s->fd_dct_tw) { (void)hipFree(s->fd_dct_tw); (void)hipFree(s->fd_dct_rot); }

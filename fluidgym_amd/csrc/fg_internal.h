@@ -841,6 +841,7 @@ struct fg_state {
     FgPoll poll;                  // host polls of this handle (fg_poll.hip)
     mutable int maxvel_clean;     // scratch_B rows 1-2 (CFL maximum + arrival counters) are zero: left so by the mirrored k_max_velocity
     FgPrepared prepared;          // kept on the handle: the stepwise entry points (fg_setup_pressure_rhs, then fg_solve_pressure) hand it across calls
+    fg_env_sel* env_sel_dev;      // [B] selection records of the last fg_env_restore_field / fg_env_reset_solver_state (fg_envrestore.hip)
     size_t n_cells() const { return (size_t)grid.n; }
 };
 // THE reader of the handle's viscosity and scalar diffusivities (getViscosity(domain, forPassiveScalar, ch),

@@ -178,6 +178,20 @@ class ChannelJetEnv2D(FluidEnv):
         for _ in range(int(self._np_rng.integers(0, 5))):
             self._sim.single_step()
 
+    def _reset_symmetries(self):
+        """Rolls along the periodic axes -- of which this channel, with its inflow and outflow faces, has none."""
+        return self._periodic_rolls()
+
+    def _reset_envs_noise(self, envs: torch.Tensor) -> None:
+        """The noise of ``_randomize_domain`` (0.05 on u) for the envs ``envs`` only.  Its projection onto divergence-free fields
+        would run a pressure solve for every env of the batch; here the first step's pressure correction does that work."""
+        u = self._block.velocity
+        u.index_add_(0, envs, torch.randn((int(envs.numel()),) + tuple(u.shape[1:]), device=u.device, generator=self._torch_rng_cuda).to(u.dtype) * 0.05)
+
+    def _reset_envs_extra(self, envs: torch.Tensor) -> None:
+        self._current_action = self._current_action.clone()
+        self._current_action[envs] = 0.0      # the action filter of the chosen envs starts from rest
+
     # ---- control --------------------------------------------------------------------------
     def _apply_action(self, action: torch.Tensor) -> None:
         a = action.reshape(self._num_envs, 1, 1, 1)

@@ -610,6 +610,12 @@ class ParallelFluidEnv:
     def set_state(self, state: Any) -> None:
         raise NotImplementedError("set_state is not implemented for ParallelFluidEnv.")
 
+    def reset_envs(self, envs, randomize: Optional[bool] = None):
+        raise NotImplementedError("reset_envs is not implemented for ParallelFluidEnv.")
+
+    def set_state_bank(self, states, env: Optional[int] = None) -> None:
+        raise NotImplementedError("set_state_bank is not implemented for ParallelFluidEnv.")
+
     def save_gif(self, filename: str, output_path=None) -> None:
         raise NotImplementedError("save_gif is not implemented for ParallelFluidEnv.")
 

@@ -239,6 +239,19 @@ class RBCEnvBase(FlowStatisticsMixin, FluidEnv):
         for _ in range(int(sim_time / self._dt)):
             self._sim.single_step()
 
+    def _reset_symmetries(self):
+        """rbc_env_base.py:335-362: mirror and roll along x, and along z in 3-D -- the axes the block holds as periodic."""
+        rolls = self._periodic_rolls()
+        return tuple(k for k in ("flip_x", "flip_z", "shift_x", "shift_z") if "shift_" + k[-1] in rolls)
+
+    def _reset_envs_noise(self, envs: torch.Tensor) -> None:
+        """The noise of ``_randomize_domain`` (0.05 on T, clamped, and on u) for the envs ``envs`` only."""
+        T, u = self._block.passiveScalar, self._block.velocity
+        n = (int(envs.numel()),)
+        T.index_add_(0, envs, torch.randn(n + tuple(T.shape[1:]), device=T.device, generator=self._torch_rng_cuda).to(T.dtype) * 0.05)
+        T.index_copy_(0, envs, T.index_select(0, envs).clamp_(self._T_cold, self._T_hot))
+        u.index_add_(0, envs, torch.randn(n + tuple(u.shape[1:]), device=u.device, generator=self._torch_rng_cuda).to(u.dtype) * 0.05)
+
     # ---- control --------------------------------------------------------------------------
     def _smooth_profile(self, T_action: torch.Tensor) -> torch.Tensor:
         """Cubic blending between neighbouring heaters over 10 % of the heater width along the LAST axis

@@ -269,6 +269,18 @@ class TCF3DBottomEnv(FlowStatisticsMixin, FluidEnv):
         for _ in range(n_steps):
             self._sim.single_step()
 
+    def _reset_symmetries(self):
+        """x and z are periodic (checked against the block): a rolled state is a state of the channel.  No mirror: the reference
+        has none for this family."""
+        return self._periodic_rolls()
+
+    def _reset_envs_noise(self, envs: torch.Tensor) -> None:
+        """The noise of ``_randomize_domain`` (1 % on u and p) for the envs ``envs`` only."""
+        u, p = self._block.velocity, self._block.pressure
+        n = (int(envs.numel()),)
+        u.index_add_(0, envs, 0.01 * torch.randn(n + tuple(u.shape[1:]), device=u.device, generator=self._torch_rng_cuda).to(u.dtype))
+        p.index_add_(0, envs, 0.01 * torch.randn(n + tuple(p.shape[1:]), device=p.device, generator=self._torch_rng_cuda).to(p.dtype))
+
     # ---- actions ----------------------------------------------------------------------------
     def _action_to_control(self, action: torch.Tensor) -> torch.Tensor:
         """``action [B, nax, naz]`` -> wall-normal velocity ``[B, Z, X]`` (tcf_env.py:521-547)."""

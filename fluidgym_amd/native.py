@@ -421,6 +421,19 @@ class NativeSolver:
     def reset_solver_state(self):
         L.check(self.lib.fg_reset_solver_state(self.handle, _stream(self.device)), lib=self.lib)
 
+    def env_restore_field(self, which_field: int, bank: torch.Tensor, sel, signed_components: bool = False):
+        """``fg_env_restore_field``: the envs named in ``sel`` (a ``FgEnvSel`` array, ``simulation.state_bank.build_selection``)
+        of the bound field ``which_field`` become states of ``bank [S, ...]``, mirrored and rolled per record.  One launch."""
+        assert bank.is_cuda and bank.dtype == self.dtype and bank.is_contiguous(), f"a bank is a contiguous {self.dtype} CUDA tensor"
+        self._env_sel = sel       # (the host records stay alive behind the asynchronous upload)
+        L.check(self.lib.fg_env_restore_field(self.handle, int(which_field), _ptr(bank), int(bank.shape[0]), sel, len(sel),
+                                              int(bool(signed_components)), _stream(self.device)), lib=self.lib)
+
+    def env_reset_solver_state(self, sel):
+        """``reset_solver_state`` for the envs named in ``sel`` only (``fg_env_reset_solver_state``); the hints stay."""
+        self._env_sel = sel
+        L.check(self.lib.fg_env_reset_solver_state(self.handle, sel, len(sel), _stream(self.device)), lib=self.lib)
+
     def make_divergence_free(self, tol=1e-5, max_iterations=1000):
         info = self._infos(self.B)
         rc = self.lib.fg_make_divergence_free(self.handle, tol, max_iterations, info, _stream(self.device))

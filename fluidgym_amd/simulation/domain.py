@@ -423,16 +423,18 @@ class Domain:
     def GetBoundaryFluxBalance(self) -> torch.Tensor:
         return self.solver.boundary_flux_balance()
 
-    def Clone(self) -> dict:
-        """State snapshot used by ``FluidEnv.get_state`` (reference: ``Domain.Clone()``)."""
+    def Clone(self, env: Optional[int] = None) -> dict:
+        """State snapshot used by ``FluidEnv.get_state`` (reference: ``Domain.Clone()``); ``env``: that env alone, as a batch of one
+        (an entry of a ``StateBank``)."""
         s = self.solver
-        snap = {"velocity": s.velocity.clone(), "pressure": s.pressure.clone()}
+        c = (lambda t: t.clone()) if env is None else (lambda t: t[int(env): int(env) + 1].clone())
+        snap = {"velocity": c(s.velocity), "pressure": c(s.pressure)}
         if s.scalar is not None:
-            snap["scalar"] = s.scalar.clone()
+            snap["scalar"] = c(s.scalar)
         if s.velocity_source is not None:
-            snap["velocity_source"] = s.velocity_source.clone()
-        snap["bvel"] = {f: t.clone() for f, t in s.bvel.items()}
-        snap["bscal"] = {f: t.clone() for f, t in s.bscal.items()}
+            snap["velocity_source"] = c(s.velocity_source)
+        snap["bvel"] = {f: c(t) for f, t in s.bvel.items()}
+        snap["bscal"] = {f: c(t) for f, t in s.bscal.items()}
         if hasattr(s, "solver_hints"):     # which iteration the next solves run (the sweeps' back-off): part of a bit-exact replay
             snap["solver_hints"] = s.solver_hints()
         return snap
@@ -452,3 +454,37 @@ class Domain:
         if "solver_hints" in snap and hasattr(s, "solver_hints"):
             s.solver_hints(snap["solver_hints"])
         s.copy_velocity_result_from_blocks()
+
+    def RestoreEnvs(self, bank, envs, src, flip_x=None, flip_z=None, shift_x=None, shift_z=None):
+        """Restore the envs ``envs`` -- and no other -- from states of ``bank`` (a ``StateBank``): env ``envs[i]`` becomes state
+        ``src[i]``, mirrored where ``flip_x[i]`` / ``flip_z[i]`` and then rolled by ``shift_x[i]`` / ``shift_z[i]`` cells
+        (``torch.roll(torch.flip(t, [-1]), shift, -1)``; every argument one value or one per chosen env, None = 0).  One
+        ``fg_env_restore_field`` launch per field, then ``fg_env_reset_solver_state`` for the same envs; the solver hints belong
+        to the handle and stay.  Returns the selection records.  The boundary arrays of the FIXED faces get the same transform as the fields.
+
+        A mirrored velocity component changes sign (``rbc_env_base.py:335-362``).  Pressure is transformed like a scalar: the
+        reference's batch-wide randomisation (``_randomize_domain``, unchanged) leaves the pressure as it was, but here the source
+        is a stored state, and a mirrored velocity next to an unmirrored pressure would be an inconsistent one.
+
+        ``ValueError`` for what the library refuses: an index out of range, an env named twice, a shift outside ``[0, n)``, a
+        mirror or roll along an axis that is not periodic (or along z in 2-D), a bank of another layout."""
+        from .state_bank import build_selection
+
+        s, blk = self.solver, self.blocks[0]
+        sel = build_selection(envs, src, flip_x, flip_z, shift_x, shift_z, batch=s.B, n_states=bank.size, dims=self.dims, nx=s.nx,
+                              nz=s.nz, periodic_x=not blk.isFixed(0), periodic_z=self.dims == 3 and not blk.isFixed(4))
+        jobs = [(L.FG_VELOCITY, s.velocity, bank.fields["velocity"], True), (L.FG_PRESSURE, s.pressure, bank.fields["pressure"], False)]
+        if s.scalar is not None and "scalar" in bank.fields:
+            jobs.append((L.FG_SCALAR, s.scalar, bank.fields["scalar"], False))
+        if s.velocity_source is not None and "velocity_source" in bank.fields:
+            jobs.append((L.FG_VELOCITY_SOURCE, s.velocity_source, bank.fields["velocity_source"], True))
+        jobs += [(L.FG_BOUND_VELOCITY + f, s.bvel[f], t, True) for f, t in bank.bvel.items()]
+        jobs += [(L.FG_BOUND_SCALAR + f, s.bscal[f], t, False) for f, t in bank.bscal.items()]
+        for _, dst, src_t, _ in jobs:
+            if tuple(src_t.shape[1:]) != tuple(dst.shape[1:]) or src_t.dtype != dst.dtype or src_t.device != dst.device:
+                raise ValueError(f"RestoreEnvs: a bank entry {tuple(src_t.shape[1:])} {src_t.dtype} on {src_t.device} does not match the "
+                                 f"domain's field {tuple(dst.shape[1:])} {dst.dtype} on {dst.device}")
+        for which, _, src_t, signed in jobs:
+            s.env_restore_field(which, src_t, sel, signed_components=signed)
+        s.env_reset_solver_state(sel)
+        return sel

@@ -381,6 +381,31 @@ int fg_reset_solver_state(fg_handle h, void* stream);
  * solves still to skip after a failure, the failures in a row (csrc/fg_jacobi.hip) -- 12 words that decide which iteration runs.
  * Domain.Clone / Restore carry them (reference: envs/fluid_env.py:1320-1363); fg_reset_solver_state clears them.  set = 0 reads. */
 int fg_solver_hints(fg_handle h, int32_t* hints12, int32_t set);
+
+/* ---- per-env restore from a bank of stored states (csrc/fg_envrestore.hip) ---------------------
+ * One record per env to restore: env `env` of the batch becomes state `src` of the bank, mirrored (flip) and then rolled (shift)
+ * along the periodic axes -- torch.roll(torch.flip(t, [-1]), shift_x, -1) and the same along z -- with the sign change of the
+ * mirrored velocity component (rbc_env_base.py:335-362). */
+typedef struct fg_env_sel {
+    int32_t env, src;          /* destination env in [0, B), source state in [0, S)        */
+    int32_t flip_x, flip_z;    /* 0 / 1                                                     */
+    int32_t shift_x, shift_z;  /* in [0, nx) / [0, nz)                                      */
+} fg_env_sel;
+/* dst[env, c, z, y, x] = sign(c) * bank[src, c, zs, y, xs] for every record, xs = flip_x ? nx-1 - ((x - shift_x) mod nx) :
+ * (x - shift_x) mod nx, zs likewise; dst is the bound field `which_field` (an fg_field id: FG_VELOCITY, FG_PRESSURE, FG_SCALAR,
+ * FG_VELOCITY_SOURCE, FG_BOUND_VELOCITY + face, FG_BOUND_SCALAR + face) and bank [S, C, ...] a device array of S states of that
+ * field's per-env layout.  signed_components (0 / 1; vector fields only): component 0 changes sign under flip_x, component 2 under
+ * flip_z.  A face array has extent 1 along its normal axis, which is a FIXED axis and carries no transform.  Envs not named in sel
+ * are not written.  sel is a HOST array (it is checked here, then uploaded to an array the handle owns and read by the one launch);
+ * the call is asynchronous on `stream`, every value is a copy or a negation (bit-exact).
+ * FG_ERR_INVALID_ARG before any launch: a null pointer, S < 1, n_sel outside 1..B, an env or src out of range, an env named twice,
+ * a flip that is not 0 / 1, a shift outside [0, n), a flip or shift along an axis with FIXED faces, flip_z or shift_z on a 2-D grid,
+ * signed_components on a field that is not a vector field, an unknown field id; FG_ERR_NOT_BOUND: the field is not bound. */
+int fg_env_restore_field(fg_handle h, int which_field, const fg_real* bank, int32_t S, const fg_env_sel* sel, int32_t n_sel,
+                         int32_t signed_components, void* stream);
+/* fg_reset_solver_state for the envs named in sel (only `env` of each record is read): their slice of pressureResult := 0, of
+ * velocityResult := block velocity.  The host-side hints of fg_solver_hints belong to the handle, not to an env, and stay. */
+int fg_env_reset_solver_state(fg_handle h, const fg_env_sel* sel, int32_t n_sel, void* stream);
 int fg_get_buffer(fg_handle h, int which, fg_real** out_ptr, int64_t* out_count);
 /* device-to-device copy of a solver vector into a caller buffer of fg_get_buffer's count */
 int fg_read_buffer(fg_handle h, int which, fg_real* dst, void* stream);
@@ -749,6 +774,10 @@ int fg_mb_debug_cycles(fg_mb_handle h, uint64_t* out12_host);
  * sweeps per non-orthogonal pass -- which decides whether a solve runs the sweeps or BiCGStab.  get_state / set_state of the envs
  * carry these 48 words so that a restored state replays bit for bit (reference: envs/fluid_env.py:1320-1363).  set = 0 reads, 1 writes. */
 int fg_mb_solver_hints(fg_mb_handle h, int32_t* hints48, int32_t set);
+/* A multi-block handle has no per-env restore (its flat cell order has no mirror or roll): both return FG_ERR_UNSUPPORTED. */
+int fg_mb_env_restore_field(fg_mb_handle h, int which_field, const fg_real* bank, int32_t S, const fg_env_sel* sel, int32_t n_sel,
+                            int32_t signed_components, void* stream);
+int fg_mb_env_reset_solver_state(fg_mb_handle h, const fg_env_sel* sel, int32_t n_sel, void* stream);
 /* as fg_solver_counters, for the multi-block path */
 int fg_mb_solver_counters(fg_mb_handle h, int64_t* out13_host, int32_t reset);
 /* The tuning / diagnosis switches a handle runs under (the FG_* environment variables read ONCE at create time, docs/SWITCHES.md,
