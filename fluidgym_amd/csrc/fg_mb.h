@@ -18,12 +18,12 @@
 
 // mb_real: the scalar type of the multi-block translation units -- fields, tables, recurrence scalars, C ABI (the public header
 // declares the same entry points with fg_real): float in libfluidgym_hip.so, double in the fp64 build (libfluidgym_hip_f64.so,
-// -DFG_REAL_DOUBLE).  What is written for 32-bit words -- the four-cells-per-thread CG kernels (float4) and the on-chip / L2 /
-// cluster CG: fg_f32 -- stays compiled and is switched off at run time in that build (fg_mb_create / fg_mb_finalize).  The
-// four-cell BiCGStab kernels (k_mbb_*<DIMS, 4>: packs of mb_real, fg_mb_krylov.hip) and the restrictions fused with the p / s update
-// are well-formed in doubles too, but have not been measured or tested there and stay switched off as well (mb_bicgstab: vec_mask,
-// ml_fused).  The multilevel preconditioner in kernel form (k_ml_*) and the preconditioned
-// CG on it (k_mbc_*_pre) are written in mb_real and serve both builds; fg_mb_set_multilevel installs the tables in either.
+// -DFG_REAL_DOUBLE).  What is written for 32-bit words -- the on-chip / L2 / cluster CG: fg_f32 -- stays compiled and is switched
+// off at run time in that build (fg_mb_create / fg_mb_finalize).  The four-cell BiCGStab and CG kernels (k_mbb_*<DIMS, 4>,
+// k_mbc_*<.., 4, ..>: packs of mb_real, fg_mb_krylov.hip) and the restrictions fused with the p / s update are well-formed in doubles
+// too, but have not been measured or tested there and stay switched off as well (mb_bicgstab: vec_mask, ml_fused; mb_cg:
+// dbg_scalar_cg).  The multilevel preconditioner in kernel form (k_ml_*) and the preconditioned CG on it (k_mbc_ap<.., MBC_PRE>,
+// k_mbc_update<.., true>) are written in mb_real and serve both builds; fg_mb_set_multilevel installs the tables in either.
 // (Until round 4 the fp64 build renamed the keyword `float` for these files.)
 typedef float fg_f32;
 #ifdef FG_REAL_DOUBLE
@@ -121,10 +121,7 @@ struct fg_mb_state {
     mb_real* w[8];   // Krylov work vectors: r, rw, p, v, t | s of the fused BiCGStab kernels | second p and v of their ping-pong pairs
     FgDacc* acc;   // [B d][MB_ACC] order-independent reduction accumulators (fg_internal.h)
     mb_real* sc;
-    int32_t *flags, *best_it, *it_ctr;
-    hipStream_t capture_stream = nullptr;
-    hipGraphExec_t cg_graph_exec = nullptr;   // one chunk of CG iterations + convergence check (fg_mb_step.hip::mb_cg)
-    unsigned char cg_graph_key_storage[256] = {0};
+    int32_t *flags, *best_it;
     int32_t* flags_pinned = nullptr;
     int32_t* sys_map_dev = nullptr;    // [B d] systems of a compacted launch (mb_bicgstab: MbSolve::sys_map); host copy in sys_map_pinned
     int32_t* sys_map_pinned = nullptr;
@@ -204,8 +201,8 @@ struct fg_mb_state {
     double* x64 = nullptr;     // fp64 iterate of the refined BiCGStab (pressure_use_bicgstab = 2)
     // debug switches, read ONCE from the environment at fg_mb_create (never on the step path): FG_MB_BICG_VEC4 (per-kernel mask
     // of the four-cell BiCGStab kernels: 1 p, 2 v, 4 s, 8 t, 16 x; default all), FG_MB_SCALAR_CG=1 (one-cell
-    // CG kernels), FG_MB_GRAPH (CG chunks replayed as a hipGraph), FG_MB_TRACE (residual trace on stderr)
-    int dbg_vec_mask = 0, dbg_scalar_cg = 0, dbg_graph = 0, dbg_trace = 0, dbg_fail = 0;   // dbg_fail: FG_MB_TRACE_FAIL
+    // CG kernels), FG_MB_TRACE (residual trace on stderr)
+    int dbg_vec_mask = 0, dbg_scalar_cg = 0, dbg_trace = 0, dbg_fail = 0;   // dbg_fail: FG_MB_TRACE_FAIL
     // iterations the last BiCGStab solve of the same place in the step took -- [0..3] velocity non-orthogonal pass,
     // [4 + 4 (c & 1) + (ps & 3)] pressure solve ps of corrector c (+ 16 for its multilevel-preconditioned attempt), [31] anything
     // else: where the next solve of that place polls first

@@ -15,8 +15,6 @@
 
 namespace {
 
-struct MbGraphKey { MbSolve q; int vec4, project_mean; hipStream_t stream; };
-
 // (A x) at cell i: xi = the vector at the cell itself, gather(n) = the vector at any other cell
 template <int DIMS, typename G>
 __device__ __forceinline__ mb_real mb_spmv_core(const MbDev& D, const MbSolve& q, int b, int i, mb_real xi, G gather) {
@@ -250,7 +248,7 @@ __device__ __forceinline__ int mbb_half(const MbSolve& q, int sys, const FgDacc*
 }
 
 // W consecutive cells of a thread.  W = 4 (N % 4 == 0): one 128-bit load / store of the cell's own data (256-bit in the fp64
-// build) and the -x / +x neighbours of the stencil from the thread's own cells or a lane shuffle (as in k_mbc_ap4) -- at
+// build) and the -x / +x neighbours of the stencil from the thread's own cells or a lane shuffle -- at
 // 16 envs x 46.7 k cells the one-cell kernels took 51 us per iteration, 2-3x what their bytes need.
 template <int W>
 struct MbPack {
@@ -285,14 +283,20 @@ __device__ __forceinline__ mb_real mb_sum(const MbPack<W>& a) {
     for (int e = 1; e < W; ++e) s += a[e];
     return s;
 }
-// y = A x for the thread's four cells: xi = the vector at the own cells, gather(n) = the vector at any other cell
-template <int DIMS, typename G>
+// y = A x for the thread's four cells: xi = the vector at the own cells, gather(n) = the vector at any other cell.  SKIP = false (the
+// CG's stencil kernel): a prescribed face reads the thread's own cell i against its stored coefficient 0 instead of branching around
+// the term, so the gathers of a thread stay independent; and the sum is rounded as the branch-free form always was -- the diagonal
+// term fused onto the first face's product, every other face fused onto that -- spelled out, because what -ffp-contract=fast makes of
+// a branch-free sum over a pack depends on the vectoriser (packed products, then adds)
+template <int DIMS, bool SKIP, typename G>
 __device__ __forceinline__ void mb_spmv4_core(const MbDev& D, const MbSolve& q, int b, int i, const MbPack<4>& xi, G gather, MbPack<4>& y) {
     constexpr int F = 2 * DIMS;
     const int N = D.N;
     const MbPack<4> d4 = mb_ld<4>(q.diag + (size_t)b * N + i);
+    if constexpr (SKIP) {
 #pragma unroll
-    for (int e = 0; e < 4; ++e) y.v[e] = d4[e] * xi[e];
+        for (int e = 0; e < 4; ++e) y.v[e] = d4[e] * xi[e];
+    }
     const int lane = threadIdx.x & 63;
     const mb_real from_prev = __shfl_up(xi[3], 1), from_next = __shfl_down(xi[0], 1);
 #pragma unroll
@@ -302,21 +306,22 @@ __device__ __forceinline__ void mb_spmv4_core(const MbDev& D, const MbSolve& q, 
         const int nn[4] = {n4.x, n4.y, n4.z, n4.w};
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const int n = nn[e];
-            if (n < 0) continue;  // prescribed face: no matrix entry (as mb_spmv; 0 * x would turn a non-finite x into NaN)
+            const int n = (SKIP || nn[e] >= 0) ? nn[e] : i;
+            if (SKIP && n < 0) continue;  // prescribed face: no matrix entry (as mb_spmv; 0 * x would turn a non-finite x into NaN)
             mb_real xn;
             if (f == 0 && n == i + e - 1 && (e > 0 || lane > 0)) xn = e > 0 ? xi[e > 0 ? e - 1 : 0] : from_prev;
             else if (f == 1 && n == i + e + 1 && (e < 3 || lane < 63)) xn = e < 3 ? xi[e < 3 ? e + 1 : 3] : from_next;
             else xn = gather(n);
-            y.v[e] += oo[e] * xn;
+            if constexpr (SKIP) y.v[e] += oo[e] * xn;
+            else y.v[e] = f == 0 ? fma(d4[e], xi[e], oo[e] * xn) : fma(oo[e], xn, y[e]);
         }
     }
 }
 // y = A x at the thread's W cells behind one entry: the one-cell gather (mb_spmv_core) or the four-cell one
-template <int DIMS, int W, typename G>
+template <int DIMS, int W, bool SKIP = true, typename G>
 __device__ __forceinline__ MbPack<W> mb_apply(const MbDev& D, const MbSolve& q, int b, int i, const MbPack<W>& xi, G gather) {
     MbPack<W> y;
-    if constexpr (W == 4) mb_spmv4_core<DIMS>(D, q, b, i, xi, gather, y);
+    if constexpr (W == 4) mb_spmv4_core<DIMS, SKIP>(D, q, b, i, xi, gather, y);
     else y.v[0] = mb_spmv_core<DIMS>(D, q, b, i, xi[0], gather);
     return y;
 }
@@ -706,231 +711,29 @@ __global__ __launch_bounds__(FG_BLOCK) void k_ml_prolong(MlDev M, const mb_real*
 // on the fly (p ping-pongs between two buffers so that the neighbours' old values are still there), which removes one
 // launch per iteration from a solve that is launch-bound at these mesh sizes (14 k cells x 64 envs).
 // accumulators: rho ring 0..2 (r_k.r_k in slot k % 3) | pAp ping-pong 3,4
-// PM: how the residual is projected -- 0 not at all, 1 onto the complement of the constant (yp = 1/sqrt(N): no loads of
-// yp at all), 2 onto the complement of a general unit vector yp (gathered with every neighbour)
-template <int PM>
-__device__ __forceinline__ mb_real mb_yp(const mb_real* __restrict__ yp, int i, mb_real yc) { return PM == 2 ? yp[i] : yc; }
-template <int DIMS, int PM>
-__global__ __launch_bounds__(FG_BLOCK) void k_mbc_ap(MbDev D, MbSolve q, mb_real* __restrict__ pA, mb_real* __restrict__ pB, int it_arg,
-                                                      int project_mean) {
-    MB_SYS
-    const int it = it_arg >= 0 ? it_arg : q.it_ctr[0];
-    if (leader && sys == 0) q.it_ctr[1] = it + 1;
-    const mb_real* p_old = (it & 1) ? pA : pB;
-    mb_real* p_new = (it & 1) ? pB : pA;
-    if (flag_ld(q.flags + (sys)) != 0) return;
-    // residual with its mean removed (project_mean): rho = |r|^2 - (sum r)^2 / N
-    // residual with its component along the projection vector yp removed (|yp| = 1): rho = |r|^2 - (yp.r)^2
-    const double sum_r = project_mean ? acc_ld(a + (C_SUM + it % 3)) : 0.0;
-    const mb_real cy = (mb_real)sum_r;
-    const double rho = acc_ld(a + (C_RHO + it % 3)) - sum_r * sum_r;
-    const mb_real crit = mb_rms(rho, N);
-    if (!(crit >= q.tol)) { if (leader) mb_mark(q, sys, crit, it); return; }
-    double rho_prev = 1.0;
-    if (it > 0) {
-        const double sp = project_mean ? acc_ld(a + (C_SUM + (it + 2) % 3)) : 0.0;
-        rho_prev = acc_ld(a + (C_RHO + (it + 2) % 3)) - sp * sp;
-    }
-    const bool fresh = (it == q.it_ctr[2]);  // first iteration after the start or a restart: p = r
-    const mb_real beta = fresh ? 0.f : (mb_real)(rho / rho_prev);
-    if (leader) {
-        q.info[sys].final_residual = crit; q.info[sys].used_iterations = it;
-        acc_st(a + (C_RHO + (it + 1) % 3), 0.0);  // accumulated by k_mbc_update of this iteration; nobody reads it here
-        acc_st(a + (C_SUM + (it + 1) % 3), 0.0);
-        // keep x_it when it beats the kept iterate by 2x: k_mbc_update of this iteration stores it before updating x
-        if (q.best_x && (it == 0 || crit < 0.5f * sc_ld(q.sc + (sys * 2)) || (crit < q.accept_factor * q.tol && crit < sc_ld(q.sc + (sys * 2))))) {
-            sc_st(q.sc + (sys * 2), crit); q.best_it[sys] = it;
-        }
-    }
-    mb_real part = 0.f;
-    if (valid) {
-        constexpr int F = 2 * DIMS;
-        const mb_real* r = q.r + vb;
-        const mb_real* po = p_old + vb;
-        const mb_real* yp = D.yproj;
-        const mb_real yc = PM == 1 ? cy * mb_rsqrt((mb_real)N) : 0.f;   // cy * yp for the constant vector
-        auto proj = [&](int c) { return PM == 0 ? r[c] : (PM == 1 ? r[c] - yc : r[c] - cy * yp[c]); };
-        const mb_real pi = fresh ? proj(i) : proj(i) + beta * po[i];
-        mb_real y = q.diag[(size_t)b * N + i] * pi;
-#pragma unroll
-        for (int f = 0; f < F; ++f) {
-            const int n = D.nbr[(size_t)f * N + i];
-            if (n >= 0) y += q.off[((size_t)b * F + f) * N + i] * (fresh ? proj(n) : proj(n) + beta * po[n]);
-        }
-        p_new[vb + i] = pi;
-        q.v[vb + i] = y;
-        part = pi * y;
-    }
-    part = mb_block_sum(part, lds);
-    if (threadIdx.x == 0) acc_add(a + C_PAP + (it & 1), (double)part);
-}
-template <int DIMS>
-__global__ __launch_bounds__(FG_BLOCK) void k_mbc_update(MbDev D, MbSolve q, const mb_real* __restrict__ pA, const mb_real* __restrict__ pB,
-                                                          int it_arg, int project_mean) {
-    MB_SYS
-    const int it = it_arg >= 0 ? it_arg : q.it_ctr[1] - 1;
-    if (leader && sys == 0) q.it_ctr[0] = it + 1;
-    const mb_real* p = (it & 1) ? pB : pA;
-    if (flag_ld(q.flags + (sys)) != 0) return;
-    const double sum_r = project_mean ? acc_ld(a + (C_SUM + it % 3)) : 0.0;
-    const mb_real alpha = (mb_real)((acc_ld(a + (C_RHO + it % 3)) - sum_r * sum_r) / acc_ld(a + (C_PAP + (it & 1))));
-    if (leader) acc_st(a + (C_PAP + ((it + 1) & 1)), 0.0);  // k_mbc_ap of the next iteration accumulates it; not read here
-    mb_real part = 0.f, psum = 0.f;
-    if (valid) {
-        if (q.best_x && q.best_it[sys] == it) q.best_x[vb + i] = q.x[vb + i];
-        q.x[vb + i] += alpha * p[vb + i];
-        const mb_real r = q.r[vb + i] - alpha * q.v[vb + i];
-        q.r[vb + i] = r;
-        part = r * r;
-        psum = r * D.yproj[i];
-    }
-    part = mb_block_sum(part, lds);
-    if (project_mean) psum = mb_block_sum(psum, lds);
-    { const int sl[2] = {C_RHO + (it + 1) % 3, C_SUM + (it + 1) % 3}; const mb_real vv[2] = {part, psum}; const bool on[2] = {true, (bool)project_mean}; mb_acc_tail<2>(a, sl, vv, on); }
-}
-
-// ---- the same two kernels with four consecutive cells per thread (N % 4 == 0): own-cell data moves as 128-bit loads, the
-// 2 x 2d x 4 neighbour gathers of a thread are independent and overlap, and a quarter of the workgroups is launched --
-// at 14 k cells x 64 envs the scalar kernels were bound by gather latency and workgroup turnover, not by bytes.
-template <int DIMS, int PM>
-__global__ __launch_bounds__(FG_BLOCK) void k_mbc_ap4(MbDev D, MbSolve q, mb_real* __restrict__ pA, mb_real* __restrict__ pB,
-                                                       int it_arg, int project_mean) {
-    const int i = (blockIdx.x * FG_BLOCK + threadIdx.x) * 4;
-    const int sys = blockIdx.y, b = sys, N = D.N;
-    const bool valid = i < N, leader = (blockIdx.x == 0 && threadIdx.x == 0);
-    const size_t vb = (size_t)sys * N;
-    FgDacc* a = q.acc + (size_t)sys * MB_ACC;
-    __shared__ mb_real lds[4];
-    const int it = it_arg >= 0 ? it_arg : q.it_ctr[0];
-    if (leader && sys == 0) q.it_ctr[1] = it + 1;
-    const mb_real* p_old = (it & 1) ? pA : pB;
-    mb_real* p_new = (it & 1) ? pB : pA;
-    if (flag_ld(q.flags + (sys)) != 0) return;
-    // residual with its component along the projection vector yp removed (|yp| = 1): rho = |r|^2 - (yp.r)^2
-    const double sum_r = project_mean ? acc_ld(a + (C_SUM + it % 3)) : 0.0;
-    const mb_real cy = (mb_real)sum_r;
-    const double rho = acc_ld(a + (C_RHO + it % 3)) - sum_r * sum_r;
-    const mb_real crit = mb_rms(rho, N);
-    if (!(crit >= q.tol)) { if (leader) mb_mark(q, sys, crit, it); return; }
-    double rho_prev = 1.0;
-    if (it > 0) {
-        const double sp = project_mean ? acc_ld(a + (C_SUM + (it + 2) % 3)) : 0.0;
-        rho_prev = acc_ld(a + (C_RHO + (it + 2) % 3)) - sp * sp;
-    }
-    const bool fresh = (it == q.it_ctr[2]);  // first iteration after the start or a restart: p = r
-    const mb_real beta = fresh ? 0.f : (mb_real)(rho / rho_prev);
-    if (leader) {
-        q.info[sys].final_residual = crit; q.info[sys].used_iterations = it;
-        acc_st(a + (C_RHO + (it + 1) % 3), 0.0);
-        acc_st(a + (C_SUM + (it + 1) % 3), 0.0);
-        if (q.best_x && (it == 0 || crit < 0.5f * sc_ld(q.sc + (sys * 2)) || (crit < q.accept_factor * q.tol && crit < sc_ld(q.sc + (sys * 2))))) {
-            sc_st(q.sc + (sys * 2), crit); q.best_it[sys] = it;
-        }
-    }
-    mb_real part = 0.f;
-    if (valid) {
-        constexpr int F = 2 * DIMS;
-        const mb_real* r = q.r + vb;
-        const mb_real* po = p_old + vb;
-        const float4 r4 = *reinterpret_cast<const float4*>(r + i);
-        const mb_real* yp = D.yproj;
-        const mb_real yc = PM == 1 ? cy * mb_rsqrt((mb_real)N) : 0.f;   // cy * yp for the constant vector
-        mb_real pi[4] = {r4.x - yc, r4.y - yc, r4.z - yc, r4.w - yc};
-        if (PM == 2) {
-            const float4 y4 = *reinterpret_cast<const float4*>(yp + i);
-            pi[0] = r4.x - cy * y4.x; pi[1] = r4.y - cy * y4.y; pi[2] = r4.z - cy * y4.z; pi[3] = r4.w - cy * y4.w;
-        }
-        if (!fresh) {
-            const float4 p4 = *reinterpret_cast<const float4*>(po + i);
-            pi[0] += beta * p4.x; pi[1] += beta * p4.y; pi[2] += beta * p4.z; pi[3] += beta * p4.w;
-        }
-        const float4 d4 = *reinterpret_cast<const float4*>(q.diag + (size_t)b * N + i);
-        mb_real y[4] = {d4.x * pi[0], d4.y * pi[1], d4.z * pi[2], d4.w * pi[3]};
-        // the direction value of a neighbour is the same expression as the cell's own (pi): inside a block row the -x / +x
-        // neighbours are the adjacent cells, i.e. this thread's other three cells or the first / last cell of the adjacent
-        // lane -- taken from registers / a lane shuffle instead of two gathers each (a third to a half of all gathers)
-        const int lane = threadIdx.x & 63;
-        const mb_real from_prev = __shfl_up(pi[3], 1), from_next = __shfl_down(pi[0], 1);
-        auto gather = [&](int n) {
-            mb_real pn = PM == 2 ? r[n] - cy * yp[n] : r[n] - yc;
-            if (!fresh) pn += beta * po[n];
-            return pn;
-        };
-#pragma unroll
-        for (int f = 0; f < F; ++f) {
-            const int4 n4 = *reinterpret_cast<const int4*>(D.nbr + (size_t)f * N + i);
-            const float4 o4 = *reinterpret_cast<const float4*>(q.off + ((size_t)b * F + f) * N + i);
-            const int nn[4] = {n4.x, n4.y, n4.z, n4.w};
-            const mb_real oo[4] = {o4.x, o4.y, o4.z, o4.w};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int n = nn[e] >= 0 ? nn[e] : i;  // prescribed face: coefficient is 0, read something valid
-                mb_real pn;
-                if (f == 0 && n == i + e - 1 && (e > 0 || lane > 0)) pn = e > 0 ? pi[e > 0 ? e - 1 : 0] : from_prev;
-                else if (f == 1 && n == i + e + 1 && (e < 3 || lane < 63)) pn = e < 3 ? pi[e < 3 ? e + 1 : 3] : from_next;
-                else pn = gather(n);
-                y[e] += oo[e] * pn;
-            }
-        }
-        *reinterpret_cast<float4*>(p_new + vb + i) = make_float4(pi[0], pi[1], pi[2], pi[3]);
-        *reinterpret_cast<float4*>(q.v + vb + i) = make_float4(y[0], y[1], y[2], y[3]);
-        part = pi[0] * y[0] + pi[1] * y[1] + pi[2] * y[2] + pi[3] * y[3];
-    }
-    part = mb_block_sum(part, lds);
-    if (threadIdx.x == 0) acc_add(a + C_PAP + (it & 1), (double)part);
-}
-__global__ __launch_bounds__(FG_BLOCK) void k_mbc_update4(int N, MbSolve q, const mb_real* __restrict__ pA, const mb_real* __restrict__ pB,
-                                                           int it_arg, int project_mean, const mb_real* __restrict__ yp) {
-    const int i = (blockIdx.x * FG_BLOCK + threadIdx.x) * 4;
-    const int sys = blockIdx.y;
-    const bool valid = i < N, leader = (blockIdx.x == 0 && threadIdx.x == 0);
-    const size_t vb = (size_t)sys * N;
-    FgDacc* a = q.acc + (size_t)sys * MB_ACC;
-    __shared__ mb_real lds[4];
-    const int it = it_arg >= 0 ? it_arg : q.it_ctr[1] - 1;
-    if (leader && sys == 0) q.it_ctr[0] = it + 1;
-    const mb_real* p = (it & 1) ? pB : pA;
-    if (flag_ld(q.flags + (sys)) != 0) return;
-    const double sum_r = project_mean ? acc_ld(a + (C_SUM + it % 3)) : 0.0;
-    const mb_real alpha = (mb_real)((acc_ld(a + (C_RHO + it % 3)) - sum_r * sum_r) / acc_ld(a + (C_PAP + (it & 1))));
-    if (leader) acc_st(a + (C_PAP + ((it + 1) & 1)), 0.0);
-    mb_real part = 0.f, psum = 0.f;
-    if (valid) {
-        float4 x4 = *reinterpret_cast<const float4*>(q.x + vb + i);
-        if (q.best_x && q.best_it[sys] == it) *reinterpret_cast<float4*>(q.best_x + vb + i) = x4;
-        const float4 p4 = *reinterpret_cast<const float4*>(p + vb + i);
-        const float4 v4 = *reinterpret_cast<const float4*>(q.v + vb + i);
-        float4 r4 = *reinterpret_cast<const float4*>(q.r + vb + i);
-        x4.x += alpha * p4.x; x4.y += alpha * p4.y; x4.z += alpha * p4.z; x4.w += alpha * p4.w;
-        r4.x -= alpha * v4.x; r4.y -= alpha * v4.y; r4.z -= alpha * v4.z; r4.w -= alpha * v4.w;
-        *reinterpret_cast<float4*>(q.x + vb + i) = x4;
-        *reinterpret_cast<float4*>(q.r + vb + i) = r4;
-        part = r4.x * r4.x + r4.y * r4.y + r4.z * r4.z + r4.w * r4.w;
-        const float4 y4 = *reinterpret_cast<const float4*>(yp + i);
-        psum = r4.x * y4.x + r4.y * y4.y + r4.z * y4.z + r4.w * y4.w;
-    }
-    part = mb_block_sum(part, lds);
-    if (project_mean) psum = mb_block_sum(psum, lds);
-    { const int sl[2] = {C_RHO + (it + 1) % 3, C_SUM + (it + 1) % 3}; const mb_real vv[2] = {part, psum}; const bool on[2] = {true, (bool)project_mean}; mb_acc_tail<2>(a, sl, vv, on); }
-}
-
-// ---- the same CG with the multilevel preconditioner in kernel form (the recurrence of k_mbc_onchip's PRE branch, restated in NumPy as
+// Both kernels exist for W = 1 and W = 4 cells per thread (MB_SYSW, MbPack; mb_cg picks): with four, own-cell data moves as 128-bit
+// loads, the 2 x 2d x 4 neighbour gathers of a thread are independent and overlap, and a quarter of the workgroups is launched --
+// at 14 k cells x 64 envs the one-cell kernels were bound by gather latency and workgroup turnover, not by bytes.
+// SRC: what the direction is built on.  0..2 = PM, how the residual is projected -- 0 not at all, 1 onto the complement of the
+// constant (yp = 1/sqrt(N): no loads of yp at all), 2 onto the complement of a general unit vector yp (gathered with every
+// neighbour); MBC_PRE = the multilevel-preconditioned recurrence (the one of k_mbc_onchip's PRE branch, restated in NumPy as
 // tests/test_multilevel_precond.py::_pcg):  z = M (r - mean r),  rz = (r - mean r) . z,  p = (z - mean z) + (rz / rz_prev) p,
 // alpha = rz / p.Ap,  criterion RMS(r - mean r).  Five launches per iteration, in this order:
 //   k_ml_restrict, k_ml_coarse   the aggregate sums of the RAW residual and the coarse solve on them (mb_ml_apply's own kernels)
 //   k_ml_prolong_cg              z, with the mean of r taken out by linearity (MlDev::cnt4 / g8: no pass over r for it), and the
 //                                sums r.z and sum z in the same pass
-//   k_mbc_ap_pre                 p of the cell and of its neighbours on the fly from z and the other p buffer, v = A p, p.Ap
-//   k_mbc_update_pre             x += alpha p, r -= alpha v, |r|^2 and sum r of the next iteration
-// accumulators next to the plain recurrence's (C_RHO ring, C_PAP pair, C_SUM ring): C_RZ pair 5, 7 (r.z of iteration it in slot
-// 5 + 2 (it & 1), the other one is rz_prev) and C_ZS 11 (sum z); each is cleared by k_mbc_update_pre, after its last reader and before the
-// next prolongation adds to it.  Every sum is a fixed-order workgroup tree into FgDacc: replays repeat bit for bit.
+//   k_mbc_ap<.., MBC_PRE>        p of the cell and of its neighbours on the fly from z and the other p buffer, v = A p, p.Ap
+//   k_mbc_update<.., true>       x += alpha p, r -= alpha v, |r|^2 and sum r of the next iteration
+// Its accumulators next to the plain recurrence's (C_RHO ring, C_PAP pair, C_SUM ring): C_RZ pair 5, 7 (r.z of iteration it in slot
+// 5 + 2 (it & 1), the other one is rz_prev) and C_ZS 11 (sum z); each is cleared by k_mbc_update, after its last reader and before the
+// next prolongation adds to it.  Every sum is a fixed-order workgroup tree into FgDacc: a solve repeats bit for bit.
+// `it` is the iteration index, `it_fresh` the iteration the recurrence (re)starts at -- 0, or that of the last restart: p = its base.
 constexpr int C_RZ = 5, C_ZS = 11;   // (slot 6 is A_RR: k_mbs_init adds |r|^2 there)
-__global__ __launch_bounds__(FG_BLOCK) void k_ml_prolong_cg(MlDev M, MbSolve q, int N, int it_arg, int project_mean, mb_real* __restrict__ z) {
+constexpr int MBC_PRE = 3;
+__global__ __launch_bounds__(FG_BLOCK) void k_ml_prolong_cg(MlDev M, MbSolve q, int N, int it, int project_mean, mb_real* __restrict__ z) {
     const int i = blockIdx.x * FG_BLOCK + threadIdx.x, sys = blockIdx.y;   // (pressure systems: nc == 1, system = env)
     __shared__ mb_real lds[8];
     if (flag_ld(q.flags + sys) != 0) return;
-    const int it = it_arg >= 0 ? it_arg : q.it_ctr[0];
     FgDacc* a = q.acc + (size_t)sys * MB_ACC;
     const mb_real rm = project_mean ? (mb_real)acc_ld(a + (C_SUM + it % 3)) * mb_rsqrt((mb_real)N) : (mb_real)0;   // mean of r (yp = 1 / sqrt(N))
     mb_real part[2] = {0.f, 0.f};
@@ -947,72 +750,120 @@ __global__ __launch_bounds__(FG_BLOCK) void k_ml_prolong_cg(MlDev M, MbSolve q, 
     mb_block_sums<2>(part, lds);
     { const int sl[2] = {C_RZ + 2 * (it & 1), C_ZS}; const bool on[2] = {true, true}; mb_acc_tail<2>(a, sl, part, on); }
 }
-template <int DIMS>
-__global__ __launch_bounds__(FG_BLOCK) void k_mbc_ap_pre(MbDev D, MbSolve q, mb_real* __restrict__ pA, mb_real* __restrict__ pB, const mb_real* __restrict__ z,
-                                                          int it_arg, int project_mean) {
-    MB_SYS
-    const int it = it_arg >= 0 ? it_arg : q.it_ctr[0];
-    if (leader && sys == 0) q.it_ctr[1] = it + 1;
-    const mb_real* p_old = (it & 1) ? pA : pB;
-    mb_real* p_new = (it & 1) ? pB : pA;
-    if (flag_ld(q.flags + (sys)) != 0) return;
+
+// Head of k_mbc_ap: flag check, the projected rho = |r|^2 - (yp.r)^2 (|yp| = 1; project_mean: yp.r sits in the C_SUM ring) and the
+// verdict on it, beta -- from the C_RHO ring, or the C_RZ pair of the preconditioned recurrence -- and the leader's bookkeeping.
+// go == false: the system does not iterate (any more), nothing else is set.  cy = yp.r
+struct MbcHead { bool go, fresh; mb_real beta, cy; };
+template <bool PRE>
+__device__ __forceinline__ MbcHead mbc_ap_head(const MbSolve& q, int sys, FgDacc* a, int N, bool leader, int it, int it_fresh, int project_mean) {
+    MbcHead h = {false, false, 0.f, 0.f};
+    if (flag_ld(q.flags + (sys)) != 0) return h;
     const double sum_r = project_mean ? acc_ld(a + (C_SUM + it % 3)) : 0.0;
-    const double rho = acc_ld(a + (C_RHO + it % 3)) - sum_r * sum_r;   // |r - mean r|^2
+    h.cy = (mb_real)sum_r;
+    const double rho = acc_ld(a + (C_RHO + it % 3)) - sum_r * sum_r;
     const mb_real crit = mb_rms(rho, N);
-    if (!(crit >= q.tol)) { if (leader) mb_mark(q, sys, crit, it); return; }
-    const bool fresh = (it == q.it_ctr[2]);  // first iteration after the start or a restart: p = z
-    const mb_real beta = fresh ? (mb_real)0 : (mb_real)(acc_ld(a + (C_RZ + 2 * (it & 1))) / acc_ld(a + (C_RZ + 2 * ((it + 1) & 1))));
-    const mb_real zbar = project_mean ? (mb_real)(acc_ld(a + C_ZS) / (double)N) : (mb_real)0;
+    if (!(crit >= q.tol)) { if (leader) mb_mark(q, sys, crit, it); return h; }
+    h.fresh = (it == it_fresh);
+    if constexpr (PRE) {
+        h.beta = h.fresh ? (mb_real)0 : (mb_real)(acc_ld(a + (C_RZ + 2 * (it & 1))) / acc_ld(a + (C_RZ + 2 * ((it + 1) & 1))));
+    } else {
+        double rho_prev = 1.0;
+        if (it > 0) {
+            const double sp = project_mean ? acc_ld(a + (C_SUM + (it + 2) % 3)) : 0.0;
+            rho_prev = acc_ld(a + (C_RHO + (it + 2) % 3)) - sp * sp;
+        }
+        h.beta = h.fresh ? 0.f : (mb_real)(rho / rho_prev);
+    }
     if (leader) {
         q.info[sys].final_residual = crit; q.info[sys].used_iterations = it;
-        acc_st(a + (C_RHO + (it + 1) % 3), 0.0);  // accumulated by k_mbc_update_pre of this iteration; nobody reads it here
+        acc_st(a + (C_RHO + (it + 1) % 3), 0.0);  // accumulated by k_mbc_update of this iteration; nobody reads it here
         acc_st(a + (C_SUM + (it + 1) % 3), 0.0);
+        // keep x_it when it beats the kept iterate by 2x: k_mbc_update of this iteration stores it before updating x
         if (q.best_x && (it == 0 || crit < 0.5f * sc_ld(q.sc + (sys * 2)) || (crit < q.accept_factor * q.tol && crit < sc_ld(q.sc + (sys * 2))))) {
             sc_st(q.sc + (sys * 2), crit); q.best_it[sys] = it;
         }
     }
+    h.go = true;
+    return h;
+}
+// What the direction is built on at a cell c: v[c] (KIND 0), v[c] - s (1) or v[c] - s yp[c] (2); p_it[c] = that, + beta p_{it-1}[c]
+// unless the recurrence starts here -- for the thread's own cells (own) and for any other cell (operator()) alike
+template <int KIND>
+struct MbcBase {
+    const mb_real* v; const mb_real* yp; mb_real s;
+    __device__ __forceinline__ mb_real term(mb_real vc, mb_real yc) const { return KIND == 0 ? vc : (KIND == 1 ? vc - s : vc - s * yc); }
+    __device__ __forceinline__ mb_real operator()(int c) const { return term(v[c], KIND == 2 ? yp[c] : (mb_real)0); }
+    template <int W>
+    __device__ __forceinline__ MbPack<W> own(int i) const {
+        const MbPack<W> v4 = mb_ld<W>(v + i), y4 = KIND == 2 ? mb_ld<W>(yp + i) : v4;
+        return mb_map<W>([&](int e) { return term(v4[e], y4[e]); });
+    }
+};
+template <int DIMS, int W, int SRC>
+__global__ __launch_bounds__(FG_BLOCK) void k_mbc_ap(MbDev D, MbSolve q, mb_real* __restrict__ pA, mb_real* __restrict__ pB, const mb_real* __restrict__ z,
+                                                      int it, int it_fresh, int project_mean) {
+    MB_SYSW(W)
+    constexpr bool PRE = SRC == MBC_PRE;
+    const mb_real* p_old = (it & 1) ? pA : pB;
+    mb_real* p_new = (it & 1) ? pB : pA;
+    const MbcHead h = mbc_ap_head<PRE>(q, sys, a, N, leader, it, it_fresh, project_mean);
+    if (!h.go) return;
+    const mb_real zbar = (PRE && project_mean) ? (mb_real)(acc_ld(a + C_ZS) / (double)N) : (mb_real)0;
     mb_real part = 0.f;
     if (valid) {
-        constexpr int F = 2 * DIMS;
-        const mb_real* zz = z + vb;
         const mb_real* po = p_old + vb;
-        auto dir = [&](int c) { return fresh ? zz[c] - zbar : (zz[c] - zbar) + beta * po[c]; };
-        const mb_real pi = dir(i);
-        mb_real y = q.diag[(size_t)b * N + i] * pi;
-#pragma unroll
-        for (int f = 0; f < F; ++f) {
-            const int n = D.nbr[(size_t)f * N + i];
-            if (n >= 0) y += q.off[((size_t)b * F + f) * N + i] * dir(n);
+        const bool fresh = h.fresh;
+        const mb_real beta = h.beta;
+        // s: the mean of z | cy yp for the constant vector (PM 1) | cy (PM 2)
+        const MbcBase<PRE ? 1 : SRC> base = {(PRE ? z : q.r) + vb, D.yproj, PRE ? zbar : (SRC == 1 ? h.cy * mb_rsqrt((mb_real)N) : h.cy)};
+        MbPack<W> pi = base.template own<W>(i);
+        if (!fresh) {
+            const MbPack<W> p4 = mb_ld<W>(po + i);
+            pi = mb_map<W>([&](int e) { return pi[e] + beta * p4[e]; });
         }
-        p_new[vb + i] = pi;
-        q.v[vb + i] = y;
-        part = pi * y;
+        // (four cells: inside a block row the -x / +x neighbours are the thread's other cells or the adjacent lane's -- mb_spmv4_core
+        //  takes them from registers / a lane shuffle, a third to a half of all gathers -- in its form without a branch around a
+        //  prescribed face, SKIP = false: the rounding this kernel has always had)
+        const MbPack<W> y = mb_apply<DIMS, W, false>(D, q, b, i, pi, [=](int n) -> mb_real { return fresh ? base(n) : base(n) + beta * po[n]; });
+        mb_st<W>(p_new + vb + i, pi);
+        mb_st<W>(q.v + vb + i, y);
+        // p . A p, the FMAs onto the first product spelled out: left to -ffp-contract=fast (mb_dot), the vectoriser pairs the four
+        // products of W = 4 in this kernel before they can fuse, and two packed multiplies and three adds round differently
+        part = pi[0] * y[0];
+#pragma unroll
+        for (int e = 1; e < W; ++e) part = fma(pi[e], y[e], part);
     }
     part = mb_block_sum(part, lds);
     if (threadIdx.x == 0) acc_add(a + C_PAP + (it & 1), (double)part);
 }
-template <int DIMS>
-__global__ __launch_bounds__(FG_BLOCK) void k_mbc_update_pre(MbDev D, MbSolve q, const mb_real* __restrict__ pA, const mb_real* __restrict__ pB,
-                                                              int it_arg, int project_mean) {
-    MB_SYS
-    const int it = it_arg >= 0 ? it_arg : q.it_ctr[1] - 1;
-    if (leader && sys == 0) q.it_ctr[0] = it + 1;
+template <int W, bool PRE>
+__global__ __launch_bounds__(FG_BLOCK) void k_mbc_update(MbDev D, MbSolve q, const mb_real* __restrict__ pA, const mb_real* __restrict__ pB, int it,
+                                                          int project_mean) {
+    MB_SYSW(W)
     const mb_real* p = (it & 1) ? pB : pA;
     if (flag_ld(q.flags + (sys)) != 0) return;
-    const mb_real alpha = (mb_real)(acc_ld(a + (C_RZ + 2 * (it & 1))) / acc_ld(a + (C_PAP + (it & 1))));
+    double num;   // of alpha: r.z, or the projected rho
+    if constexpr (PRE) num = acc_ld(a + (C_RZ + 2 * (it & 1)));
+    else {
+        const double sum_r = project_mean ? acc_ld(a + (C_SUM + it % 3)) : 0.0;
+        num = acc_ld(a + (C_RHO + it % 3)) - sum_r * sum_r;
+    }
+    const mb_real alpha = (mb_real)(num / acc_ld(a + (C_PAP + (it & 1))));
     if (leader) {   // idle until the next iteration's kernels add to them; none is read in this launch
         acc_st(a + (C_PAP + ((it + 1) & 1)), 0.0);
-        acc_st(a + (C_RZ + 2 * ((it + 1) & 1)), 0.0);
-        acc_st(a + C_ZS, 0.0);
+        if constexpr (PRE) { acc_st(a + (C_RZ + 2 * ((it + 1) & 1)), 0.0); acc_st(a + C_ZS, 0.0); }
     }
     mb_real part = 0.f, psum = 0.f;
     if (valid) {
-        if (q.best_x && q.best_it[sys] == it) q.best_x[vb + i] = q.x[vb + i];
-        q.x[vb + i] += alpha * p[vb + i];
-        const mb_real r = q.r[vb + i] - alpha * q.v[vb + i];
-        q.r[vb + i] = r;
-        part = r * r;
-        psum = r * D.yproj[i];
+        const MbPack<W> x = mb_ld<W>(q.x + vb + i);
+        if (q.best_x && q.best_it[sys] == it) mb_st<W>(q.best_x + vb + i, x);
+        const MbPack<W> p4 = mb_ld<W>(p + vb + i), v4 = mb_ld<W>(q.v + vb + i), r0 = mb_ld<W>(q.r + vb + i);
+        mb_st<W>(q.x + vb + i, mb_map<W>([&](int e) { return x[e] + alpha * p4[e]; }));
+        const MbPack<W> r = mb_map<W>([&](int e) { return r0[e] - alpha * v4[e]; });
+        mb_st<W>(q.r + vb + i, r);
+        part = mb_dot<W>(r, r);
+        psum = mb_dot<W>(r, mb_ld<W>(D.yproj + i));
     }
     part = mb_block_sum(part, lds);
     if (project_mean) psum = mb_block_sum(psum, lds);
@@ -1023,7 +874,6 @@ __global__ __launch_bounds__(FG_BLOCK) void k_mbc_update_pre(MbDev D, MbSolve q,
 // iterations, cg_solver_kernel.cu:281-300): slots of iteration `it` are cleared by k_mbc_clear, then refilled here
 __global__ void k_mbc_clear(MbSolve q, int nsys, int it) {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s == 0) q.it_ctr[2] = it;
     if (s >= nsys) return;
     acc_st(q.acc + ((size_t)s * MB_ACC + C_RHO + it % 3), 0.0);
     acc_st(q.acc + ((size_t)s * MB_ACC + C_SUM + it % 3), 0.0);
@@ -1072,12 +922,6 @@ __global__ void k_mbs_check(MbSolve q, fg_solve_info* __restrict__ mirror, int32
     __shared__ uint32_t stage[64 * 3];
     const int first = blockIdx.x * blockDim.x, s = first + threadIdx.x;
     const bool valid = s < nsys;
-    if (it < 0) {  // graph-replayed CG: iteration index and accumulator slots from the device counter
-        it = q.it_ctr[0] - 1;
-        rr_slot = C_RHO + (it + 1) % 3;
-        if (sum_slot != -1) sum_slot = C_SUM + (it + 1) % 3;
-        final_pass = (it + 1 >= q.max_iterations);
-    }
     if (valid && flag_ld(q.flags + (s)) == 4) flag_st(q.flags + (s), 1);
     if (valid && flag_ld(q.flags + (s)) == 0) {
         double rr = acc_ld(q.acc + ((size_t)s * MB_ACC + rr_slot));
@@ -1286,12 +1130,12 @@ int mb_finish(fg_mb_state* s, int nsys, fg_solve_info* info_host, int* max_it) {
 
 MbSolve mb_solve_ptrs(fg_mb_state* s, const mb_real* diag, const mb_real* off, const mb_real* rhs, mb_real* x, int nc, mb_real tol) {
     MbSolve q;
-    memset(&q, 0, sizeof(q));  // the struct doubles as (part of) the key of the cached CG graph: no stray padding bytes
+    memset(&q, 0, sizeof(q));
     q.diag = diag; q.off = off; q.rhs = rhs; q.x = x;
     q.r = s->w[0]; q.rw = s->w[1]; q.p = s->w[2]; q.v = s->w[3]; q.t = s->w[4];
     q.acc = s->acc; q.sc = s->sc; q.flags = s->flags; q.info = s->info_dev; q.nc = nc; q.tol = tol;
     q.best_x = nullptr; q.best_it = nullptr; q.stall_limit = 0;
-    q.it_ctr = s->it_ctr; q.max_iterations = 0;
+    q.max_iterations = 0;
     q.accept_factor = 0.f; q.accept_window = 0;
     q.project = 0;
     return q;
@@ -1861,7 +1705,7 @@ int mb_pressure_bicgstab(fg_mb_state* s, const mb_real* dt, mb_real tol, int max
 int mb_cg(fg_mb_state* s, const mb_real* dt, const mb_real* diag, const mb_real* off, const mb_real* rhs, mb_real* x, mb_real tol,
           int max_iterations, int use_x0, int project_mean, mb_real stall_accept, int* max_it, hipStream_t st) {
     const int nsys = s->B, n = s->N;
-    // the multilevel preconditioner in kernel form (k_ml_prolong_cg / k_mbc_ap_pre / k_mbc_update_pre): what the fp64 build runs once
+    // the multilevel preconditioner in kernel form (k_ml_prolong_cg / k_mbc_ap<.., MBC_PRE> / k_mbc_update<.., true>): what the fp64 build runs once
     // the tables are installed, and in the fp32 build the debug form FG_MB_PCG_KERNEL=1 of the on-chip / cluster kernels' recurrence.
     // Pressure systems of 2-D meshes; the residual projected onto the complement of the constant, or not at all
     const bool pre = (FG_MB_F64 || s->dbg_pcg_kernel) && s->ml_on && s->ml_a4 != nullptr && s->ml_mp != nullptr && s->d == 2 &&
@@ -1887,12 +1731,10 @@ int mb_cg(fg_mb_state* s, const mb_real* dt, const mb_real* diag, const mb_real*
     const MlDev ML = mb_ml_dev(s);
     if (pre) { mb_ml_scale(s, diag, st); s->ml_cg_solves += 1; }
     bool done = false;
-    // CG_CHUNK iterations + the convergence check are one hipGraph: at 14 k cells x 64 envs a kernel runs 5-10 us, about
-    // what the host needs to enqueue it, so the loop was launch-bound.  The kernels take their iteration index from a
-    // device counter (q.it_ctr) so that one captured chunk serves every replay.
+    // CG_CHUNK iterations are enqueued between two convergence checks (one poll of the host per chunk); every launch gets its
+    // iteration index, and the iteration the recurrence last started at, as arguments
     constexpr int CG_CHUNK = 20, CG_RESTART = 100;
     q.max_iterations = ((max_iterations + CG_CHUNK - 1) / CG_CHUNK) * CG_CHUNK;
-    FG_HIP_CHECK(hipMemsetAsync(s->it_ctr, 0, 3 * sizeof(int32_t), st));
     int active_now = 0;  // systems still iterating, from the poll before this chunk (all active ones at chunk 0)
     auto prof_collect = [&]() -> int {
         for (int k = 0; k < s->prof_used; ++k) {
@@ -1912,83 +1754,62 @@ int mb_cg(fg_mb_state* s, const mb_real* dt, const mb_real* diag, const mb_real*
         return FG_OK;
     };
     const int pm_mode = project_mean ? (s->yproj_const ? 1 : 2) : 0;
-    auto enqueue_chunk = [&](bool sample, FgPollOut po) {   // po: sequence words of the poll that follows ({nullptr, 0} inside a captured graph)
+    int it_fresh = 0;   // iteration the recurrence started at: 0, then that of the last restart
+    // one launch of a recurrence kernel, between the pair `e` of the live profiler's events when the iteration is sampled
+#define MBC_LAUNCH(K, g, e, ...)                                                                                                  \
+    do {                                                                                                                          \
+        if (ev) hipExtLaunchKernelGGL(K, g, blk, 0, st, s->prof_ev[2 * (e)], s->prof_ev[2 * (e) + 1], 0, __VA_ARGS__);            \
+        else hipLaunchKernelGGL(K, g, blk, 0, st, __VA_ARGS__);                                                                   \
+    } while (0)
+    auto enqueue_chunk = [&](int it0, bool sample, FgPollOut po) {   // po: sequence words of the poll that follows
+        const mb_real* pA = s->w[1];
+        const mb_real* pB = s->w[2];
+        const mb_real* z = pre ? s->ml_mp : nullptr;   // z = M (r - mean r) of the preconditioned recurrence
         MB_DISPATCH_PM(s, pm_mode, {
-            for (int k = 0; k < CG_CHUNK && pre; ++k) {   // z = M (r - mean r) in s->ml_mp, then the two recurrence kernels on it
-                mb_ml_restrict_coarse(s, q, ML, q.r, st, 0, 0);
-                hipLaunchKernelGGL(k_ml_prolong_cg, grid, blk, 0, st, ML, q, n, -1, project_mean, s->ml_mp);
-                hipLaunchKernelGGL(k_mbc_ap_pre<DIMS>, grid, blk, 0, st, s->dev, q, s->w[1], s->w[2], (const mb_real*)s->ml_mp, -1, project_mean);
-                hipLaunchKernelGGL(k_mbc_update_pre<DIMS>, grid, blk, 0, st, s->dev, q, (const mb_real*)s->w[1], (const mb_real*)s->w[2], -1, project_mean);
-            }
-            for (int k = 0; k < CG_CHUNK && !pre; ++k) {
-                const bool ev = sample && k == 0 && s->prof_used + 2 <= 32;
+            for (int k = 0; k < CG_CHUNK; ++k) {
+                const int li = it0 + k;
+                const bool ev = !pre && sample && k == 0 && s->prof_used + 2 <= 32;   // (the live profiler samples the plain recurrence)
                 const int e0 = s->prof_used;
                 if (ev) {
                     s->prof_kind[e0] = 0; s->prof_kind[e0 + 1] = 1;
                     s->prof_active[e0] = s->prof_active[e0 + 1] = active_now;
                     s->prof_used += 2;
                 }
+                if (pre) {
+                    mb_ml_restrict_coarse(s, q, ML, q.r, st, 0, 0);
+                    hipLaunchKernelGGL(k_ml_prolong_cg, grid, blk, 0, st, ML, q, n, li, project_mean, s->ml_mp);
+                    MBC_LAUNCH((k_mbc_ap<DIMS, 1, MBC_PRE>), grid, e0, s->dev, q, s->w[1], s->w[2], z, li, it_fresh, project_mean);
+                    MBC_LAUNCH((k_mbc_update<1, true>), grid, e0 + 1, s->dev, q, pA, pB, li, project_mean);
+                    continue;
+                }
                 s->prof_launches[0] += 1; s->prof_launches[1] += 1;
                 if (vec4) {
-                    if (ev) {
-                        hipExtLaunchKernelGGL(HIP_KERNEL_NAME(k_mbc_ap4<DIMS, PM>), grid4, blk, 0, st, s->prof_ev[2 * e0], s->prof_ev[2 * e0 + 1], 0, s->dev, q, s->w[1], s->w[2], -1, project_mean);
-                        hipExtLaunchKernelGGL(k_mbc_update4, grid4, blk, 0, st, s->prof_ev[2 * e0 + 2], s->prof_ev[2 * e0 + 3], 0, n, q, (const mb_real*)s->w[1], (const mb_real*)s->w[2], -1, project_mean, s->dev.yproj);
-                    } else {
-                        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mbc_ap4<DIMS, PM>), grid4, blk, 0, st, s->dev, q, s->w[1], s->w[2], -1, project_mean);
-                        hipLaunchKernelGGL(k_mbc_update4, grid4, blk, 0, st, n, q, (const mb_real*)s->w[1], (const mb_real*)s->w[2], -1, project_mean, s->dev.yproj);
-                    }
+                    MBC_LAUNCH((k_mbc_ap<DIMS, 4, PM>), grid4, e0, s->dev, q, s->w[1], s->w[2], z, li, it_fresh, project_mean);
+                    MBC_LAUNCH((k_mbc_update<4, false>), grid4, e0 + 1, s->dev, q, pA, pB, li, project_mean);
                 } else {
-                    if (ev) {
-                        hipExtLaunchKernelGGL(HIP_KERNEL_NAME(k_mbc_ap<DIMS, PM>), grid, blk, 0, st, s->prof_ev[2 * e0], s->prof_ev[2 * e0 + 1], 0, s->dev, q, s->w[1], s->w[2], -1, project_mean);
-                        hipExtLaunchKernelGGL(k_mbc_update<DIMS>, grid, blk, 0, st, s->prof_ev[2 * e0 + 2], s->prof_ev[2 * e0 + 3], 0, s->dev, q, (const mb_real*)s->w[1], (const mb_real*)s->w[2], -1, project_mean);
-                    } else {
-                        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mbc_ap<DIMS, PM>), grid, blk, 0, st, s->dev, q, s->w[1], s->w[2], -1, project_mean);
-                        hipLaunchKernelGGL(k_mbc_update<DIMS>, grid, blk, 0, st, s->dev, q, (const mb_real*)s->w[1], (const mb_real*)s->w[2], -1, project_mean);
-                    }
+                    MBC_LAUNCH((k_mbc_ap<DIMS, 1, PM>), grid, e0, s->dev, q, s->w[1], s->w[2], z, li, it_fresh, project_mean);
+                    MBC_LAUNCH((k_mbc_update<1, false>), grid, e0 + 1, s->dev, q, pA, pB, li, project_mean);
                 }
             }
         });
-        hipLaunchKernelGGL(k_mbs_check, sg, sb, 0, st, q, s->info_pinned, s->flags_pinned, 0, -1, n, nsys, 0, project_mean ? 0 : -1, po);
+        const int last = it0 + CG_CHUNK - 1;   // the check reads what the update kernel of the chunk's last iteration summed
+        hipLaunchKernelGGL(k_mbs_check, sg, sb, 0, st, q, s->info_pinned, s->flags_pinned, C_RHO + (last + 1) % 3, last, n, nsys,
+                           (int)(last + 1 >= q.max_iterations), project_mean ? C_SUM + (last + 1) % 3 : -1, po);
     };
-    // the chunk can be replayed as a hipGraph (FG_MB_GRAPH=1); since the four-cells-per-thread kernels the loop is no
-    // longer enqueue-bound and plain launches are as fast, so that is the default (and what the live profiler samples)
-    const bool use_graph = s->dbg_graph && !s->prof_on;
+#undef MBC_LAUNCH
     const bool trace = s->dbg_trace != 0;
-    if (use_graph) {
-        MbGraphKey key;
-        memset(&key, 0, sizeof(key));
-        key.q = q; key.vec4 = (vec4 ? 1 : 0) | (pre ? 2 : 0); key.project_mean = pm_mode; key.stream = st;
-        static_assert(sizeof(MbGraphKey) <= sizeof(s->cg_graph_key_storage), "graph key storage too small");
-        MbGraphKey& stored = *reinterpret_cast<MbGraphKey*>(s->cg_graph_key_storage);
-        if (!s->cg_graph_exec || memcmp(&key, &stored, sizeof(key)) != 0) {
-            if (s->cg_graph_exec) { (void)hipGraphExecDestroy(s->cg_graph_exec); s->cg_graph_exec = nullptr; }
-            hipGraph_t graph = nullptr;
-            // captured on a private stream (the caller's may be the legacy default stream, which cannot capture); the
-            // instantiated graph is then launched on the caller's stream
-            if (!s->capture_stream) FG_HIP_CHECK(hipStreamCreateWithFlags(&s->capture_stream, hipStreamNonBlocking));
-            const hipStream_t run_stream = st;
-            st = s->capture_stream;
-            FG_HIP_CHECK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-            enqueue_chunk(false, FgPollOut{nullptr, 0});
-            FG_HIP_CHECK(hipStreamEndCapture(st, &graph));
-            st = run_stream;
-            FG_HIP_CHECK(hipGraphInstantiate(&s->cg_graph_exec, graph, nullptr, nullptr, 0));
-            (void)hipGraphDestroy(graph);
-            memcpy(&stored, &key, sizeof(key));
-        }
-    }
     int recoveries = 0;
     bool need_restart = false;
     for (int it = 0; it < q.max_iterations && !done; it += CG_CHUNK) {
         if (it > 0 && (it % CG_RESTART == 0 || need_restart)) {
             need_restart = false;
+            it_fresh = it;
             hipLaunchKernelGGL(k_mbc_clear, sg, sb, 0, st, q, nsys, it);
             MB_DISPATCH(s, hipLaunchKernelGGL(k_mbc_restart<DIMS>, grid, blk, 0, st, s->dev, q, it, project_mean););
         }
         if (it == 0) { active_now = 0; for (int i = 0; i < nsys; ++i) active_now += 1; }  // inactive envs exit in k_mbs_begin's flags; counted below after the first poll
-        const FgPollOut po = use_graph ? FgPollOut{nullptr, 0} : fg_poll_next(&s->poll);
-        if (use_graph) FG_HIP_CHECK(hipGraphLaunch(s->cg_graph_exec, st));
-        else enqueue_chunk(s->prof_on && (s->prof_chunk++ % 4 == 0), po);
+        const FgPollOut po = fg_poll_next(&s->poll);
+        enqueue_chunk(it, s->prof_on && (s->prof_chunk++ % 4 == 0), po);
         if (int rc = mb_poll(s, nsys, st, done, po, true)) return rc;
         active_now = 0;
         for (int i = 0; i < nsys; ++i) active_now += s->flags_pinned[i] == 0;

@@ -28,8 +28,7 @@ struct MbSolve {
     // best-iterate tracking of the CG pressure solve (returnBestResult, cg_solver_kernel.cu:345-361): sc[2 sys] holds the
     // residual of the kept iterate, best_it the iteration it belongs to, best_x the iterate itself
     mb_real* best_x; int32_t* best_it; int stall_limit;
-    // device-side iteration index of the graph-replayed CG: ctr[0] read by k_mbc_ap*, ctr[1] - 1 by k_mbc_update*
-    int32_t* it_ctr; int max_iterations;
+    int max_iterations;   // chunked CG (mb_cg): the iteration cap rounded up to whole chunks
     int it_base;  // BiCGStab: iteration index of the last restart (kernels run on the index since then, reports add this)
     // stall acceptance (off when 0): a system whose kept iterate is within accept_factor * tol and has not improved for
     // accept_window iterations ends with that iterate and counts as converged

@@ -480,7 +480,6 @@ extern "C" int fg_mb_create(int32_t dims, int32_t batch, int32_t device, fg_mb_h
         e = getenv("FG_MB_ML_FUSE"); s->dbg_ml_fuse = e ? atoi(e) : 1;
         s->dbg_ml_sb = 0;          // (FG_MB_ML_SB until round 5) systems per workgroup of k_ml_coarse: by batch size
         e = getenv("FG_MB_ML_TRY_CAP"); if (e && atoi(e) > 0) s->dbg_ml_cap = atoi(e);
-        s->dbg_graph = 0;          // (FG_MB_GRAPH until round 5: the chunked CG replayed as a hipGraph -- no mesh of the envs takes the chunked CG any more)
         s->dbg_trace = getenv("FG_MB_TRACE") != nullptr;
         if (const char* e = getenv("FG_MB_COMPACT")) s->dbg_compact = atoi(e);
         if (const char* e = getenv("FG_MB_OC_RTG_NT")) s->oc_rtg_nt = atoi(e);   // 1: the register-resident form on 16-24 k cells instead of k_mbc_l2
@@ -497,8 +496,9 @@ extern "C" int fg_mb_create(int32_t dims, int32_t batch, int32_t device, fg_mb_h
         e = getenv("FG_MB_OC_VARIANT"); s->oc_variant = e ? atoi(e) : 0;   // bit 0: no compiler fences in the stencil pass; bit 1: split [F][N] coefficient layout
     }
 #if FG_MB_F64
-    // the fp64 build runs the one-cell-per-thread kernels: the four-cell forms (float4) and the on-chip / cluster CG are written for
-    // 32-bit words (fg_mb.h); the multilevel preconditioner runs in kernel form there once fg_mb_set_multilevel has installed it
+    // the fp64 build runs the one-cell-per-thread kernels: the four-cell forms are well-formed in doubles but neither measured nor
+    // tested there, the on-chip / cluster CG are written for 32-bit words (fg_mb.h); the multilevel preconditioner runs in kernel
+    // form there once fg_mb_set_multilevel has installed it
     s->dbg_vec_mask = 0; s->dbg_scalar_cg = 1; s->onchip_mode = 0; s->dbg_oc_agg = 0; s->cl_mode = 0;
 #endif
     *out = s;
@@ -510,11 +510,11 @@ extern "C" int fg_mb_config_dump(fg_mb_handle s, char* buf, int n) {
     char tmp[2048];
     const int len = snprintf(tmp, sizeof(tmp),
         "{\"FG_MB_BICG_VEC4\": %d, \"FG_MB_SCALAR_CG\": %d, \"FG_MB_BICG_FUSE\": %d, \"FG_MB_PRED\": %d, \"FG_MB_ML_FUSE\": %d, \"FG_MB_ML_SB\": %d, "
-        "\"FG_MB_ML_TRY_CAP\": %d, \"FG_MB_ML_WARMUP\": %d, \"FG_MB_GRAPH\": %d, \"FG_MB_TRACE\": %d, \"FG_MB_COMPACT\": %d, \"FG_MB_OC_RTG_NT\": %d, "
+        "\"FG_MB_ML_TRY_CAP\": %d, \"FG_MB_ML_WARMUP\": %d, \"FG_MB_GRAPH\": 0, \"FG_MB_TRACE\": %d, \"FG_MB_COMPACT\": %d, \"FG_MB_OC_RTG_NT\": %d, "
         "\"FG_MB_ONCHIP\": %d, \"FG_MB_OC_AGG\": %d, \"FG_MB_RUNG_ILU\": %d, \"FG_MB_OC_VARIANT\": %d, \"FG_MB_CLUSTER\": %d, \"FG_MB_PCG_KERNEL\": %d, \"multilevel_on\": %d, \"multilevel_cg_solves\": %lld, "
         "\"cluster_on\": %d, \"cluster_members_per_thread\": %d, \"cluster_threads\": %d, \"cluster_halo_max\": %d, \"cluster_solves\": %lld, \"cluster_fallbacks\": %lld, \"cluster_jacobi_solves\": %lld}",
         (int)s->dbg_vec_mask, (int)s->dbg_scalar_cg, (int)s->dbg_fuse_st, (int)s->dbg_pred, (int)s->dbg_ml_fuse, (int)s->dbg_ml_sb, (int)s->dbg_ml_cap,
-        (int)s->dbg_ml_warmup, (int)s->dbg_graph, (int)s->dbg_trace, (int)s->dbg_compact, (int)s->oc_rtg_nt, (int)s->onchip_mode, (int)s->dbg_oc_agg,
+        (int)s->dbg_ml_warmup, (int)s->dbg_trace, (int)s->dbg_compact, (int)s->oc_rtg_nt, (int)s->onchip_mode, (int)s->dbg_oc_agg,
         (int)s->dbg_rung_ilu, (int)s->oc_variant, (int)s->cl_mode, (int)s->dbg_pcg_kernel, (int)((s->ml_on && s->ml_a4 != nullptr) ? 1 : 0), s->ml_cg_solves,
         (int)(mb_cluster_wanted(s) ? 1 : 0), (int)s->cl_cpt, (int)s->cl_nt, (int)s->cl_n_halo_max,
         s->cl_solves, s->cl_fallbacks, s->cl_jacobi_solves);
@@ -525,10 +525,8 @@ extern "C" int fg_mb_config_dump(fg_mb_handle s, char* buf, int n) {
 
 extern "C" int fg_mb_destroy(fg_mb_handle s) {
     if (!s) return FG_OK;
-    if (s->cg_graph_exec) (void)hipGraphExecDestroy(s->cg_graph_exec);
     if (s->prof_ev[0]) for (int k = 0; k < 64; ++k) (void)hipEventDestroy(s->prof_ev[k]);
     if (s->prof_ev_oc[0]) for (int k = 0; k < 2; ++k) (void)hipEventDestroy(s->prof_ev_oc[k]);
-    if (s->capture_stream) (void)hipStreamDestroy(s->capture_stream);
     for (void* p : s->owned) (void)hipFree(p);
     if (s->info_pinned) (void)hipHostFree(s->info_pinned);
     if (s->red_pinned) (void)hipHostFree(s->red_pinned);
@@ -658,7 +656,6 @@ extern "C" int fg_mb_finalize(fg_mb_handle s) {
         s->dev.yproj = s->yproj;
     }
     if (int rc = mb_alloc(s, &s->red2, 2 * B)) return rc;
-    if (int rc = mb_alloc(s, &s->it_ctr, 4)) return rc;
     if (int rc = mb_alloc(s, &s->dt_dev, B)) return rc;
     if (int rc = mb_alloc(s, &s->dt_step, B)) return rc;
     if (int rc = mb_alloc(s, &s->oc_dbg, (size_t)16)) return rc;
@@ -1072,8 +1069,6 @@ extern "C" int fg_mb_set_multilevel(fg_mb_handle s, int32_t n4, int32_t n8, cons
         FG_HIP_CHECK(hipMemcpy(s->ml_g8, g8.data(), sizeof(mb_real) * n8, hipMemcpyHostToDevice));
     }
     s->ml_n4 = n4; s->ml_n8 = n8; s->ml_geom_diag_sum = geom_diag_sum; s->ml_on = enable != 0;
-    // a captured CG chunk (mb_cg, FG_MB_GRAPH) has the table and work-array pointers baked in: it is rebuilt after a new install
-    if (s->cg_graph_exec) { (void)hipGraphExecDestroy(s->cg_graph_exec); s->cg_graph_exec = nullptr; }
     s->oc_agg = false;
     if (FG_MB_F64) return FG_OK;   // the slot-ordered and cluster layouts below belong to the fp32 on-chip / cluster kernels
     // ---- aggregate-owned layout of the on-chip CG (fg_mb.h): thread 4 A + c owns child c of 8 x 8 aggregate A

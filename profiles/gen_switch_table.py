@@ -76,7 +76,7 @@ NOTES = {
     "FLUIDGYM_AMD_PRESSURE_MULTILEVEL": ("bits", "multilevel preconditioner of the multi-block pressure CG"),
     "FLUIDGYM_AMD_PRESSURE_MULTILEVEL_BICGSTAB": ("bits", "multilevel trial of the airfoil's refined BiCGStab"),
     "FLUIDGYM_AMD_PRESSURE_MULTILEVEL_FP64": ("bits", "policy pressure_multilevel_fp64 (default 0): float64 cylinder / airfoil envs on 2-D meshes install the multilevel preconditioner in the fp64 build (kernel-form preconditioned CG, unfused BiCGStab trial) instead of the plain recurrences"),
-    "FG_MB_PCG_KERNEL": ("bits", "1 (fp32 build, debugging): the multilevel-preconditioned pressure CG as the kernel-form loop of mb_cg (five launches per iteration: what the fp64 build runs) instead of the on-chip / cluster kernels; 0 (default)"),
+    "FG_MB_PCG_KERNEL": ("bits", "1 (fp32 build, debugging): the multilevel-preconditioned pressure CG as the kernel-form loop of mb_cg (five launches per iteration, `k_mbc_ap<.., MBC_PRE>` / `k_mbc_update<.., true>`: what the fp64 build runs) instead of the on-chip / cluster kernels; 0 (default)"),
     "FLUIDGYM_AMD_PRESSURE_BICGSTAB_LARGE_MESHES": ("bits", "3-D multi-block ids take the refined BiCGStab"),
     "FLUIDGYM_AMD_NATIVE_WALL_FORCING": ("bits", "policy native_wall_forcing: the TCF forcing hook runs inside the library"),
     "FLUIDGYM_COLLECTIVE_TIMEOUT_S": ("no", "timeout of ParallelFluidEnv's process group (600 s)"),

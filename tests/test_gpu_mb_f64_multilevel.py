@@ -1,6 +1,6 @@
 """The multilevel preconditioner in the fp64 build (``MultiBlockDomain(dtype=torch.float64).set_pressure_multilevel(fp64=True)``,
 policy ``pressure_multilevel_fp64``): the apply kernels in doubles against the NumPy formula, the kernel-form preconditioned CG
-(csrc/fg_mb_krylov.hip: k_ml_prolong_cg / k_mbc_ap_pre / k_mbc_update_pre) against its CPU replay, whole PISO steps against the
+(csrc/fg_mb_krylov.hip: k_ml_prolong_cg / k_mbc_ap<.., MBC_PRE> / k_mbc_update<.., true>) against its CPU replay, whole PISO steps against the
 oracle's direct solves, off-means-off, replay, and the float64 envs under the policy."""
 import ctypes
 
@@ -188,7 +188,7 @@ def test_preconditioned_cg_iteration_counts_against_the_cpu_replay():
 
 def test_fp32_library_reaches_the_same_loop_through_its_debug_switch(monkeypatch):
     """FG_MB_PCG_KERNEL=1 (read at fg_mb_create, off by default): the fp32 library runs the preconditioned pressure CG as the
-    kernel-form loop -- the fp32 instances of k_ml_prolong_cg / k_mbc_ap_pre / k_mbc_update_pre -- instead of its on-chip / cluster
+    kernel-form loop -- the fp32 instances of k_ml_prolong_cg / k_mbc_ap<.., MBC_PRE> / k_mbc_update<.., true> -- instead of its on-chip / cluster
     kernels.  Same system, tolerance 1e-3 (the fp32 recurrence residual of this matrix, entries ~1e-2 .. 1, is good to ~1e-6), from the
     loaded buffers: the count against the CPU replay and against the fp64 build's 95.  Another summation order and fp32 rounding of
     the dot products move a CG count by one or two (the bound tests/test_gpu_mb.py holds its kernel forms to among each other).
