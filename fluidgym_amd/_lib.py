@@ -42,6 +42,17 @@ FG_FORM_SLOT_X, FG_FORM_SLOT_Z, FG_FORM_SLOT_TRIDIAG, FG_FORM_SLOT_FACTORS, FG_F
 FG_FORM_FAC_GRID, FG_FORM_FAC_ROWMEAN, FG_FORM_FAC_MADE = 1, 2, 3
 FG_FORM_HELM_ARRAY, FG_FORM_HELM_ROW32, FG_FORM_HELM_ROW64 = 1, 2, 3
 FG_FORM_LINE_LDS, FG_FORM_LINE_STREAM = 1, 2
+# kinds of fg_flow_diagnostic / fg_mb_flow_diagnostic (include/fluidgym_hip.h FG_DIAG_*)
+FG_DIAG_GRADIENT, FG_DIAG_VORTICITY, FG_DIAG_VORTICITY_MAGNITUDE, FG_DIAG_Q, FG_DIAG_STRAIN_NORM = range(5)
+
+
+def diagnostic_channels(dims: int, kind: int) -> int:
+    """Channels K of a flow diagnostic ``[B, K, ...]``: d d for the gradient, 1 (2-D) or 3 (3-D) for the vorticity, else 1."""
+    if kind not in range(5):
+        raise ValueError(f"unknown flow diagnostic kind {kind!r} (FG_DIAG_*)")
+    if kind == FG_DIAG_GRADIENT:
+        return dims * dims
+    return 3 if (kind == FG_DIAG_VORTICITY and dims == 3) else 1
 
 
 class FgConfig(Structure):
@@ -283,6 +294,8 @@ SIGNATURES = {
     "fg_debug_apply_pressure_preconditioner": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, POINTER(ctypes.c_double),
                                                        POINTER(c_int32), c_void_p]),
     "fg_sgs_smagorinsky": (c_int, [c_void_p, c_float, c_void_p, c_void_p]),
+    "fg_flow_diagnostic": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
+    "fg_mb_flow_diagnostic": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     "fg_set_fd_helmholtz": (c_int, [c_void_p, POINTER(c_float)]),
     "fg_advection_retries": (c_int, [c_void_p, POINTER(c_int64), c_int32]),
     "fg_advection_solver_form": (c_int, [c_void_p, c_int, POINTER(c_int32)]),

@@ -339,6 +339,11 @@ class AirfoilEnvBase(CylinderEnvBase):
         u[..., torch.as_tensor(self._airfoil_mask, device=u.device)] = 0.0
         return u
 
+    def _diagnostic_to_view(self, cells: torch.Tensor) -> torch.Tensor:
+        v = self._resampler(cells)
+        v[..., torch.as_tensor(self._airfoil_mask, device=v.device)] = 0.0
+        return v
+
 
 class AirfoilEnv2D(AirfoilEnvBase):
     """``AirfoilEnv2D`` (airfoil_env_2d.py:27-190): one agent drives the three jets; the mean of the action is removed so

@@ -239,6 +239,9 @@ class CylinderEnvBase(FieldStatisticsMixin, FlowStatisticsMixin, FluidEnv):     
     def get_pressure(self) -> torch.Tensor:
         return self._resampler(self._domain.pressure)
 
+    def _diagnostic_to_view(self, cells: torch.Tensor) -> torch.Tensor:
+        return self._resampler(cells)
+
     def _get_drag_and_lift(self):
         """[B] in 2-D; [B, NZ] per spanwise layer in 3-D (face area = edge length x D / resolution, :676-689)."""
         f = self._ring.forces(self._domain, self._nu_forces, layer_height=self.D / self._circle_resolution_angular)

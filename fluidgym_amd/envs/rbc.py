@@ -324,6 +324,9 @@ class RBCEnvBase(FlowStatisticsMixin, FluidEnv):
         """Pressure on the render grid ``[B, (oz,) oy, ox]`` (fluid_env.py:683-706, batched)."""
         return self._resampler(self._block.pressure)[:, 0]
 
+    def _diagnostic_to_view(self, cells: torch.Tensor) -> torch.Tensor:
+        return self._resampler(cells)
+
     def _get_global_obs(self):
         """rbc_env_2d.py:175-194 / rbc_env_3d.py:291-330 with a leading env axis."""
         B, d = self._num_envs, self._ndims

@@ -188,6 +188,17 @@ class NativeSolver:
         L.check(self.lib.fg_sgs_smagorinsky(self.handle, float(coefficient), _ptr(out), _stream(self.device)), lib=self.lib)
         return out
 
+    def flow_diagnostic(self, kind: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """A velocity-gradient diagnostic of the bound velocity, ``[B, K, *grid]`` (``fg_flow_diagnostic``; ``kind`` = ``FG_DIAG_*``
+        of ``fluidgym_amd._lib``, K = ``diagnostic_channels(dims, kind)``): one launch over the batch on the current stream."""
+        shape = (self.B, L.diagnostic_channels(self.dims, kind)) + tuple(self.spatial)
+        if out is None:
+            out = torch.empty(shape, dtype=self.dtype, device=self.device)
+        elif tuple(out.shape) != shape or out.dtype != self.dtype or not out.is_contiguous() or out.device != self.device:
+            raise ValueError(f"flow_diagnostic: out must be a contiguous {shape} tensor of the solver's dtype on its device")
+        L.check(self.lib.fg_flow_diagnostic(self.handle, int(kind), _ptr(out), _stream(self.device)), lib=self.lib)
+        return out
+
     def set_boundary_velocity(self, face, t):
         self.bvel[face] = t
         self.bind(L.FG_BOUND_VELOCITY + face, t)

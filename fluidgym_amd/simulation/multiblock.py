@@ -334,6 +334,21 @@ class MultiBlockDomain:
         L.check(self.lib.fg_mb_max_velocity(self.handle, out, ctypes.c_void_p(st)))
         return np.array(out[:], dtype=self._np)
 
+    def flow_diagnostic(self, kind: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """A velocity-gradient diagnostic of the current velocity, ``[B, K, N]`` in the flat cell order (``fg_mb_flow_diagnostic``;
+        ``kind`` = ``FG_DIAG_*`` of ``fluidgym_amd._lib``, K = ``diagnostic_channels(dims, kind)``): one launch over the batch on the
+        current stream.  ``MBBlock.cells`` views a block of it."""
+        if not self.prepared:
+            raise RuntimeError("PrepareSolve() first")
+        shape = (self.batch, L.diagnostic_channels(self.dims, kind), self.n_cells)
+        if out is None:
+            out = torch.empty(shape, dtype=self.dtype, device=self.device)
+        elif tuple(out.shape) != shape or out.dtype != self.dtype or not out.is_contiguous() or out.device != self.device:
+            raise ValueError(f"flow_diagnostic: out must be a contiguous {shape} tensor of the domain's dtype on its device")
+        st = torch.cuda.current_stream(self.device).cuda_stream
+        L.check(self.lib.fg_mb_flow_diagnostic(self.handle, int(kind), ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(st)), lib=self.lib)
+        return out
+
     def buffer(self, which: int) -> torch.Tensor:
         """Copy of an intermediate buffer of the last step (tests)."""
         ptr, cnt = ctypes.c_void_p(), ctypes.c_int64()

@@ -205,6 +205,23 @@ int fg_set_advection_preconditioner(fg_handle h, int mode);
  * |S| = sqrt(2 S:S) from the gradients of the bound velocity (getBlockDataGradient, :2997-3040: central differences, a Dirichlet face
  * counts as half a cell) and Delta^2 = the largest squared cell extent.  Asynchronous on `stream`. */
 int fg_sgs_smagorinsky(fg_handle h, fg_real coefficient, fg_real* out_BN, void* stream);
+/* Velocity-gradient diagnostics of the bound velocity (ComputeSpatialVelocityGradients = getBlockDataGradient per component,
+ * PISO_multiblock_cuda_kernel.cu:2997-3040, 6460-6553; csrc/fg_flowdiag.hip): out[B, K, (nz,) ny, nx], one launch over the whole batch,
+ * asynchronous on `stream`, nothing returns to the host, the bound fields are only read.  With g[i][j] = d u_i / d x_j (central
+ * differences of the neighbour values, a Dirichlet face counts as half a cell, times Minv), S = sym(g), Omega = skew(g), d = dims:
+ *   FG_DIAG_GRADIENT             K = d d   g[i][j] in channel i d + j
+ *   FG_DIAG_VORTICITY            K = 1 (2-D): g[1][0] - g[0][1];  K = 3 (3-D): (g[2][1] - g[1][2], g[0][2] - g[2][0], g[1][0] - g[0][1])
+ *   FG_DIAG_VORTICITY_MAGNITUDE  K = 1     its Euclidean norm (absolute value in 2-D)
+ *   FG_DIAG_Q                    K = 1     0.5 (|Omega|^2 - |S|^2), Frobenius norms
+ *   FG_DIAG_STRAIN_NORM          K = 1     sqrt(2 S:S), the |S| of fg_sgs_smagorinsky
+ * Before any launch: FG_ERR_INVALID_ARG for a null handle or out or an unknown kind, FG_ERR_NOT_BOUND when the velocity (or the
+ * boundary velocity of a FIXED face) is not bound. */
+#define FG_DIAG_GRADIENT 0
+#define FG_DIAG_VORTICITY 1
+#define FG_DIAG_VORTICITY_MAGNITUDE 2
+#define FG_DIAG_Q 3
+#define FG_DIAG_STRAIN_NORM 4
+int fg_flow_diagnostic(fg_handle h, int kind, fg_real* out, void* stream);
 /* Test / diagnosis entry, never on a step path: z = M^-1 r [B, nc, N] with the preconditioner of `mode` (1: y-line, 3: the separable
  * Helmholtz operator of the velocity system, I/dt - nu Laplacian with the dt of the last velocity fg_setup_advection, applied by the
  * dispatch the BiCGStab runs; 4: ILU(0)) built from the advection-diffusion matrix currently assembled (fg_setup_advection).
@@ -821,6 +838,10 @@ int fg_mb_get_boundary_tables(fg_mb_handle h, int32_t* cell, int32_t* face, fg_r
 int fg_mb_get_cell_transforms(fg_mb_handle h, fg_real* transform);
 /* max |Minv u| over cells and boundary faces per env (Domain.getMaxVelocity(True, True)); synchronises */
 int fg_mb_max_velocity(fg_mb_handle h, fg_real* out_B_host, void* stream);
+/* fg_flow_diagnostic on a multi-block domain: out[B, K, N] in the flat cell order, g[i][j] = sum_a c[i][a] Minv[a][j] with the cell's
+ * Minv; across a connection only the neighbour's VALUE is used (no axis mapping), across a FIXED face the slot's boundary velocity.
+ * Same kinds and codes; a host-only handle (created with device < 0) answers FG_ERR_UNSUPPORTED. */
+int fg_mb_flow_diagnostic(fg_mb_handle h, int kind, fg_real* out, void* stream);
 /* pressure_project_mean keeps the CG residuals orthogonal to a unit vector: the constant by default, or y_host [N] (any scale).
  * fg_mb_unit_pressure_matrix leaves the pressure matrix for A = 1 in the P buffers so that a host routine can compute its left
  * near-null vector, the choice that removes the residual floor of non-orthogonal meshes */
