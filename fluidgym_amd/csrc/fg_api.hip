@@ -11,6 +11,7 @@
 #include <stdlib.h>
 
 #include "fg_internal.h"
+#include "fg_bicg.h"
 
 static thread_local std::string g_last_error;
 void fg_set_error(const std::string& msg) { g_last_error = msg; }
@@ -438,22 +439,10 @@ extern "C" int fg_advection_retries(fg_handle s, int64_t* out, int32_t reset) {
     return FG_OK;
 }
 
-#if !FG_F64
-bool fg_bicg3_ok(const fg_state* s, int nc, int* zc_out);
-#endif
 extern "C" int fg_advection_solver_form(fg_handle s, int nc, int32_t* out) {
     FG_REQUIRE(s && out, FG_ERR_INVALID_ARG, "null argument");
-    int form = 0;
-    if (s->bicg_fused) {
-        int zc = 0;
-#if !FG_F64
-        if (s->grid.dims == 3 && (s->bicg3_mix & 3) == 3 && fg_bicg3_ok(s, nc, &zc)) form = 2;
-        else
-#endif
-        if (s->grid.dims == 2 || s->bicg_fused >= 2) form = 1;
-        (void)zc;
-    }
-    *out = form;
+    const BicgForm f = fg_bicg_form(s, nc, 0);
+    *out = (f.za && f.zb) ? 2 : (f.kind == BICG_FIVE ? 0 : 1);
     return FG_OK;
 }
 

@@ -166,6 +166,13 @@ __device__ __forceinline__ BicgDecB fg_bicgf_decide_b(const FgGrid& g, const Bic
 }
 #endif
 
+// Which iteration an advection-diffusion solve with nc systems per env and FgBicgArgs::precond runs (fg_bicgstab.hip): the five
+// kernels, the two kernels as brick launches, the two kernels with one (za / zb: kernel a / b) or both as z-marching launches of zc
+// planes per chunk, or the six launches of the Helmholtz-preconditioned form.  keep_init: a zero start still runs the init kernel.
+enum BicgFormKind { BICG_FIVE, BICG_TWO_BRICK, BICG_TWO_ZMARCH, BICG_HELM_SIX };
+struct BicgForm { BicgFormKind kind; bool za, zb; int zc; bool keep_init; };
+BicgForm fg_bicg_form(const fg_state* s, int nc, int precond);
+
 // z-marching two-kernel iteration in 3-D (fg_bicgstab3d.hip).  fg_bicg3_ok: the grid fits the tiles (every thread valid) and fills
 // the chip; zc_out = planes per z-chunk
 bool fg_bicg3_ok(const fg_state* s, int nc, int* zc_out);

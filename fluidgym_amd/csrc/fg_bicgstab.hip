@@ -24,26 +24,6 @@ constexpr int A_RHO = 0, A_RV = 2, A_SS = 3, A_TS = 4, A_TT = 5, A_RR = 6;
 // fg_mb_krylov.hip mbb_p_head: an exact rho = 0 or rw.v = 0 at the fp32 rounding level must not turn into inf / NaN)
 constexpr int A_RHOE = 10;
 
-template <int DIMS, int VEC>
-__device__ __forceinline__ FgVec<VEC> fg_spmv(const fg_real* __restrict__ diag, const fg_real* __restrict__ off,
-                                              const fg_real* __restrict__ x, const FgCtx<DIMS, VEC>& c, size_t N) {
-    // diag/off already offset to the env; x offset to the system
-    const FgNbr<DIMS, VEC> X = fg_gather<DIMS, VEC>(x, c);
-    const FgVec<VEC> d = fg_load<VEC>(diag + c.idx);
-    FgVec<VEC> o[2 * DIMS];
-#pragma unroll
-    for (int f = 0; f < 2 * DIMS; ++f) o[f] = fg_load<VEC>(off + f * N + c.idx);
-    FgVec<VEC> y;
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) {
-        fg_real v = d.v[e] * X.c.v[e] + o[0].v[e] * X.xm.v[e] + o[1].v[e] * X.xp.v[e] + o[2].v[e] * X.ym.v[e] +
-                  o[3].v[e] * X.yp.v[e];
-        if constexpr (DIMS == 3) v += o[4].v[e] * X.zm.v[e] + o[5].v[e] * X.zp.v[e];
-        y.v[e] = v;
-    }
-    return y;
-}
-
 struct SysCtx {
     int sys;       // b * nc + comp
     int comp;
@@ -77,25 +57,20 @@ __device__ __forceinline__ FgStencilRow<DIMS, VEC> fg_load_row(const fg_real* __
     for (int f = 0; f < 2 * DIMS; ++f) m.o[f] = fg_load<VEC>(off + f * N + c.idx);
     return m;
 }
+// the row applied to a cell's gathered values (and, in the two-kernel form, to values recomputed at the neighbours)
+template <int DIMS, int VEC>
+__device__ __forceinline__ FgVec<VEC> fg_apply_nbr(const FgStencilRow<DIMS, VEC>& m, const FgNbr<DIMS, VEC>& X);
 template <int DIMS, int VEC>
 __device__ __forceinline__ FgVec<VEC> fg_apply_row(const FgStencilRow<DIMS, VEC>& m, const fg_real* __restrict__ x,
                                                    const FgCtx<DIMS, VEC>& c) {
-    const FgNbr<DIMS, VEC> X = fg_gather<DIMS, VEC>(x, c);
-    FgVec<VEC> y;
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) {
-        fg_real v = m.d.v[e] * X.c.v[e] + m.o[0].v[e] * X.xm.v[e] + m.o[1].v[e] * X.xp.v[e] + m.o[2].v[e] * X.ym.v[e] +
-                  m.o[3].v[e] * X.yp.v[e];
-        if constexpr (DIMS == 3) v += m.o[4].v[e] * X.zm.v[e] + m.o[5].v[e] * X.zp.v[e];
-        y.v[e] = v;
-    }
-    return y;
+    return fg_apply_nbr<DIMS, VEC>(m, fg_gather<DIMS, VEC>(x, c));
 }
 
-// init: r = rhs - C x0 ; rw = r ; p = r ; rho_0 = rr = r.r        (grid.y = 1: loops over the nc systems of the env)
+// init of both forms: r = rhs - C x0 ; rw = r ; p_0 = r into `p0` ; r.r into the accumulator words `word_a` and, if >= 0, `word_b`
+// (five kernels: rho_0 and rr; two kernels: rr_0 alone)        (grid.y = 1: loops over the nc systems of the env)
 template <int DIMS, int VEC>
-__global__ __launch_bounds__(FG_BLOCK) void k_bicg_init(FgGrid g, BicgPtrs q, int use_x0, int tiles_x, int tiles_y,
-                                                         int tiles) {
+__global__ __launch_bounds__(FG_BLOCK) void k_bicg_init(FgGrid g, BicgPtrs q, fg_real* p0, int word_a, int word_b, int use_x0,
+                                                         int tiles_x, int tiles_y, int tiles) {
     const FgCtx<DIMS, VEC> c = fg_make_ctx<DIMS, VEC>(g, tiles_x, tiles_y, tiles);
     const size_t N = g.n;
     bool any = false;
@@ -123,15 +98,15 @@ __global__ __launch_bounds__(FG_BLOCK) void k_bicg_init(FgGrid g, BicgPtrs q, in
             }
             fg_store<VEC>(q.r + vb + c.idx, r);
             fg_store<VEC>(q.rw + vb + c.idx, r);
-            fg_store<VEC>(q.p + vb + c.idx, r);
+            fg_store<VEC>(p0 + vb + c.idx, r);
 #pragma unroll
             for (int e = 0; e < VEC; ++e) part[0] += r.v[e] * r.v[e];
         }
         fg_block_sum<1>(part, lds);
         if (threadIdx.x == 0) {
             FgDacc* a = q.acc + (size_t)sys * FG_ACC_DOUBLES;
-            acc_add(a + A_RHO, (double)part[0]);
-            acc_add(a + A_RR, (double)part[0]);
+            acc_add(a + word_a, (double)part[0]);
+            if (word_b >= 0) acc_add(a + word_b, (double)part[0]);
         }
         __syncthreads();
     }
@@ -401,47 +376,6 @@ __device__ __forceinline__ void fg_nbr_scale_add(FgNbr<DIMS, VEC>& a, fg_real ca
     }
 }
 
-// init: r = rhs - C x0 ; rw = r ; p_0 = r ; rr_0 = r.r        (grid.y = 1: loops over the nc systems of the env)
-template <int DIMS, int VEC>
-__global__ __launch_bounds__(FG_BLOCK) void k_bicgf_init(FgGrid g, BicgPtrs q, BicgFused w, int use_x0, int tiles_x, int tiles_y,
-                                                          int tiles) {
-    const FgCtx<DIMS, VEC> c = fg_make_ctx<DIMS, VEC>(g, tiles_x, tiles_y, tiles);
-    const size_t N = g.n;
-    bool any = false;
-    for (int comp = 0; comp < q.nc; ++comp) any = any || (flag_ld(q.flags + (c.b * q.nc + comp)) == 0);
-    if (!any) return;
-    FgStencilRow<DIMS, VEC> m;
-    if (use_x0 && c.valid) m = fg_load_row<DIMS, VEC>(q.diag + (size_t)c.b * N, q.off + (size_t)c.b * 2 * DIMS * N, c, N);
-    __shared__ fg_real lds[4];
-    for (int comp = 0; comp < q.nc; ++comp) {
-        const int sys = c.b * q.nc + comp;
-        if (flag_ld(q.flags + (sys)) != 0) continue;
-        const size_t vb = (size_t)sys * N;
-        fg_real part[1] = {0.f};
-        if (c.valid) {
-            FgVec<VEC> r = fg_load<VEC>(q.rhs + vb + c.idx);
-            if (use_x0) {
-                const FgVec<VEC> y = fg_apply_row<DIMS, VEC>(m, q.x + vb, c);
-#pragma unroll
-                for (int e = 0; e < VEC; ++e) r.v[e] -= y.v[e];
-            } else {
-                FgVec<VEC> z;
-#pragma unroll
-                for (int e = 0; e < VEC; ++e) z.v[e] = 0.f;
-                fg_store<VEC>(q.x + vb + c.idx, z);
-            }
-            fg_store<VEC>(q.r + vb + c.idx, r);
-            fg_store<VEC>(q.rw + vb + c.idx, r);
-            fg_store<VEC>(w.p[0] + vb + c.idx, r);
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) part[0] += r.v[e] * r.v[e];
-        }
-        fg_block_sum<1>(part, lds);
-        if (threadIdx.x == 0) acc_add(q.acc + (size_t)sys * FG_ACC_DOUBLES + F_RR, (double)part[0]);
-        __syncthreads();
-    }
-}
-
 // k_bicgf_a(it): finish iteration it - 1 (x, r, p) and start iteration it (v = C p, rw.v, r.r)      (grid.y = 1)
 template <int DIMS, int VEC>
 __global__ __launch_bounds__(FG_BLOCK) __attribute__((amdgpu_waves_per_eu(DIMS == 2 ? 4 : 3))) void k_bicgf_a(FgGrid g, BicgPtrs q, BicgFused w, int it, int tiles_x, int tiles_y,
@@ -607,18 +541,26 @@ __global__ __launch_bounds__(FG_BLOCK) void k_bicgf_b(FgGrid g, BicgPtrs q, Bicg
     }
 }
 
-// poll after k_bicgf_a(it + 1), i.e. after iteration `it` completed: judges r_{it+1} exactly as k_bicg_check does (the next
-// k_bicgf_b would come to the same verdict from the same accumulator) and mirrors info for the host
-__global__ void k_bicgf_check(FgDacc* __restrict__ acc, int32_t* __restrict__ flags, fg_solve_info* __restrict__ info,
-                              fg_solve_info* __restrict__ mirror, fg_real tol, int it, int n, int nsys, int final_pass, FgPollOut poll,
-                              int sys0 = 0) {
-    // systems sys0 .. sys0 + nsys - 1 (a sub-batch of envs: the systems behind it have not started and must not be judged)
+__global__ void k_bicg_begin(const fg_real* __restrict__ dt, FgDacc* __restrict__ acc, fg_real* __restrict__ sc,
+                             int32_t* __restrict__ flags, fg_solve_info* __restrict__ info, int nsys, int nc) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= nsys) return;
+    const FgBicgBegin q = {acc, sc, flags, info, nc};
+    fg_bicg_begin_sys(q, dt, s);     // (fg_internal.h: shared with k_adv_build, which prepares the solve that follows an assembly)
+}
+
+// the polled verdict after iteration `it` completed, on systems sys0 .. sys0 + nsys - 1 (a sub-batch of envs: the systems behind it have
+// not started and must not be judged): r.r from accumulator word `word` -- A_RR of the five kernels; F_RR + ((it + 1) & 1) behind
+// k_bicgf_a(it + 1), where the next k_bicgf_b would come to the same verdict from the same word -- and the infos to the host
+__global__ void k_bicg_check(FgDacc* __restrict__ acc, int32_t* __restrict__ flags, fg_solve_info* __restrict__ info,
+                             fg_solve_info* __restrict__ mirror, fg_real tol, int it, int n, int nsys, int final_pass, FgPollOut poll,
+                             int word, int sys0) {
     __shared__ uint32_t stage[2 * 64];
     const int first = sys0 + blockIdx.x * blockDim.x, s = first + threadIdx.x;
     const bool valid = s < sys0 + nsys;
     if (valid && flag_ld(flags + (s)) == 4) flag_st(flags + (s), 1);
     if (valid && flag_ld(flags + (s)) == 0) {
-        const fg_real crit = (fg_real)sqrt(acc_ld(acc + ((size_t)s * FG_ACC_DOUBLES + F_RR + ((it + 1) & 1))) / (double)n);
+        const fg_real crit = (fg_real)sqrt(acc_ld(acc + ((size_t)s * FG_ACC_DOUBLES + word)) / (double)n);
         info[s].final_residual = crit;
         info[s].used_iterations = it + 1;
         if (!(crit >= tol)) {
@@ -631,36 +573,6 @@ __global__ void k_bicgf_check(FgDacc* __restrict__ acc, int32_t* __restrict__ fl
         }
     }
     fg_poll_publish_infos(poll, mirror, info, s, valid, first, min((int)blockDim.x, sys0 + nsys - first), stage);
-}
-
-__global__ void k_bicg_begin(const fg_real* __restrict__ dt, FgDacc* __restrict__ acc, fg_real* __restrict__ sc,
-                             int32_t* __restrict__ flags, fg_solve_info* __restrict__ info, int nsys, int nc) {
-    const int s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= nsys) return;
-    const FgBicgBegin q = {acc, sc, flags, info, nc};
-    fg_bicg_begin_sys(q, dt, s);     // (fg_internal.h: shared with k_adv_build, which prepares the solve that follows an assembly)
-}
-
-__global__ void k_bicg_check(FgDacc* __restrict__ acc, int32_t* __restrict__ flags, fg_solve_info* __restrict__ info,
-                             fg_solve_info* __restrict__ mirror, fg_real tol, int it, int n, int nsys, int final_pass, FgPollOut poll) {
-    __shared__ uint32_t stage[2 * 64];
-    const int first = blockIdx.x * blockDim.x, s = first + threadIdx.x;
-    const bool valid = s < nsys;
-    if (valid && flag_ld(flags + (s)) == 4) flag_st(flags + (s), 1);
-    if (valid && flag_ld(flags + (s)) == 0) {
-        const fg_real crit = (fg_real)sqrt(acc_ld(acc + ((size_t)s * FG_ACC_DOUBLES + A_RR)) / (double)n);
-        info[s].final_residual = crit;
-        info[s].used_iterations = it + 1;
-        if (!(crit >= tol)) {
-            const bool finite = isfinite(crit);
-            flag_st(flags + (s), finite ? 1 : 2);
-            info[s].converged = finite ? 1 : 0;
-            info[s].is_finite = finite ? 1 : 0;
-        } else if (final_pass) {
-            info[s].converged = 0;
-        }
-    }
-    fg_poll_publish_infos(poll, mirror, info, s, valid, first, min((int)blockDim.x, nsys - first), stage);
 }
 
 }  // namespace
@@ -717,9 +629,52 @@ int fg_bicgstab_solve(fg_state* s, const FgBicgArgs& a, fg_solve_info* info_host
     return bicgstab_krylov(s, a, info_host, st, false);
 }
 
-static int bicgstab_krylov(fg_state* s, const FgBicgArgs& a, fg_solve_info* info_host, hipStream_t st, bool begun) {
-    const int B = s->grid.B, n = s->grid.n, nsys = B * a.nc;
+namespace {
+// what the parts of bicgstab_krylov share
+struct BicgRun {
     BicgPtrs q;
+    BicgFused w;
+    BicgForm form;
+    bool done = false, info_fresh = false;
+    // first convergence poll where the previous solve finished (kernels of converged systems exit at once,
+    // so over-launching costs ~2 us per kernel while every poll costs a stream sync), then every 2 iterations
+    int next_poll;
+    // per-launch figures of the profiler: cells of a system, matrix bytes per cell and system (the (1 + 2d) fields are shared by the
+    // nc right-hand sides), flops of one matrix row
+    double cells, mat, fl;
+};
+}  // namespace
+
+// one launch of the brick kernel KERNEL<DIMS, VEC>(GSUB, c.q, ..., tiles) over the envs of the grid GSUB (all of them, or a sub-batch:
+// FgGrid::b0, B), grid.y = NY, sampled by the profiler when SLOT >= 0
+#define BICG_LAUNCH(GSUB, NY, SLOT, KERNEL, ...)                                                                              \
+    FG_DISPATCH(s, {                                                                                                          \
+        FgLaunch L = fg_launch_geometry<DIMS, VEC>(GSUB); L.grid.y = (NY);                                                    \
+        FG_LAUNCH_P(s, SLOT, (KERNEL<DIMS, VEC>), L.grid, dim3(FG_BLOCK), 0, st, GSUB, c.q, __VA_ARGS__, L.tiles_x, L.tiles_y, L.tiles); \
+    })
+
+// Which iteration a solve runs.  Two kernels (k_bicgf_a / k_bicgf_b) without a preconditioner in 2-D; in 3-D as z-marching LDS-ring
+// kernels (fg_bicgstab3d.hip) when the grid fits their tiles and fills the chip -- the brick form's neighbour recomputation of four
+// fields across six faces costs more than the two saved passes there (TCF 128 x 64 x 64: 299 us per iteration against 260 us), so
+// without them the five kernels stay unless FG_BICG_FUSED >= 2.  FG_BICG3_MIX picks the z-marching form per kernel (the two forms
+// share buffers and accumulators) and, with bit 2 or the two kernels in different forms, keeps the init kernel of a zero start.
+BicgForm fg_bicg_form(const fg_state* s, int nc, int precond) {
+    BicgForm f = {BICG_FIVE, false, false, 0, false};
+    bool zmarch3 = false;
+#if !FG_F64
+    zmarch3 = s->bicg_fused && !precond && s->grid.dims == 3 && fg_bicg3_ok(s, nc, &f.zc);
+    f.za = zmarch3 && (s->bicg3_mix & 1); f.zb = zmarch3 && (s->bicg3_mix & 2);
+    f.keep_init = (s->bicg3_mix & 4) || f.za != f.zb;
+    if (precond == 2 && fg_fbicg_ok(s)) f.kind = BICG_HELM_SIX;
+#endif
+    if (s->bicg_fused && !precond && (s->grid.dims == 2 || s->bicg_fused >= 2 || zmarch3)) f.kind = (f.za || f.zb) ? BICG_TWO_ZMARCH : BICG_TWO_BRICK;
+    return f;
+}
+
+// begin: the pointer bundle, the preconditioner's factors, the solve's device state
+static int bicg_begin_run(fg_state* s, const FgBicgArgs& a, BicgRun& c, hipStream_t st, bool begun) {
+    const int B = s->grid.B;
+    BicgPtrs& q = c.q;
     q.diag = a.diag; q.off = a.off; q.rhs = a.rhs; q.x = a.x;
     q.r = s->w[0]; q.rw = s->w[1]; q.p = s->w[2]; q.v = s->w[3]; q.t = s->w[4];
     q.acc = s->acc; q.sc = s->scratch_B + 4 * B;  // scratch_B holds 4*B floats of env scalars first
@@ -729,7 +684,6 @@ static int bicgstab_krylov(fg_state* s, const FgBicgArgs& a, fg_solve_info* info
         if (int rc = (a.precond == 3 ? fg_ilu_alloc(s) : fg_line_alloc(s))) return rc;
         q.mp = s->w[5]; q.ms = s->w[6];   // free during a BiCGStab solve (the CG's z and second p buffer)
     }
-    const dim3 sg((nsys + 63) / 64), sb(64);
     bicg_begin(s, a, st, begun);
     if (a.precond == 2) {
         FG_REQUIRE(s->fd_lam != nullptr, FG_ERR_INVALID_ARG, "Helmholtz preconditioner requested but fg_set_fd_helmholtz was not called");
@@ -739,215 +693,196 @@ static int bicgstab_krylov(fg_state* s, const FgBicgArgs& a, fg_solve_info* info
     } else if (a.precond) {
         if (int rc = fg_line_factor(s, a.diag, a.off, a.nc, st)) return rc;
     }
-    auto precondition = [&](const fg_real* in, fg_real* out) -> int {
-        if (a.precond == 3) return fg_ilu_apply(s, a.diag, a.off, a.nc, in, out, st);
-        return a.precond == 2 ? fg_fd_helmholtz_apply(s, a.nc, in, out, st) : fg_line_apply(s, a.diag, a.off, a.nc, in, out, st);
-    };
+    c.form = fg_bicg_form(s, a.nc, a.precond);
+    c.next_poll = s->pred_bicg[a.kind & 3] > 1 ? s->pred_bicg[a.kind & 3] : 1;
+    c.cells = (double)s->grid.n; c.mat = 4.0 * (1 + 2 * s->grid.dims) / a.nc; c.fl = 2.0 * (1 + 2 * s->grid.dims);
+    return FG_OK;
+}
 
-    FgGrid gsub = s->grid;     // the envs a launch covers: all of them, or a sub-batch (b0, B) in the two-kernel 2-D form below
-#define FG_BICG_LAUNCH_Y(NY, SLOT, KERNEL, ...)                                                                          \
-    do {                                                                                                     \
-        if (s->grid.dims == 2) {                                                                             \
-            if (s->vec == 4) {                                                                               \
-                FgLaunch L = fg_launch_geometry<2, 4>(gsub); L.grid.y = (NY);                             \
-                FG_LAUNCH_P(s, SLOT, (KERNEL<2, 4>), L.grid, dim3(FG_BLOCK), 0, st, gsub, q, __VA_ARGS__, L.tiles_x, L.tiles_y, L.tiles); \
-            } else {                                                                                         \
-                FgLaunch L = fg_launch_geometry<2, 1>(gsub); L.grid.y = (NY);                             \
-                FG_LAUNCH_P(s, SLOT, (KERNEL<2, 1>), L.grid, dim3(FG_BLOCK), 0, st, gsub, q, __VA_ARGS__, L.tiles_x, L.tiles_y, L.tiles); \
-            }                                                                                                \
-        } else {                                                                                             \
-            if (s->vec == 4) {                                                                               \
-                FgLaunch L = fg_launch_geometry<3, 4>(gsub); L.grid.y = (NY);                             \
-                FG_LAUNCH_P(s, SLOT, (KERNEL<3, 4>), L.grid, dim3(FG_BLOCK), 0, st, gsub, q, __VA_ARGS__, L.tiles_x, L.tiles_y, L.tiles); \
-            } else {                                                                                         \
-                FgLaunch L = fg_launch_geometry<3, 1>(gsub); L.grid.y = (NY);                             \
-                FG_LAUNCH_P(s, SLOT, (KERNEL<3, 1>), L.grid, dim3(FG_BLOCK), 0, st, gsub, q, __VA_ARGS__, L.tiles_x, L.tiles_y, L.tiles); \
-            }                                                                                                \
-        }                                                                                                    \
-    } while (0)
+// the poll round behind iteration `it` of systems [sys0, sys0 + nsys): the verdict on accumulator word `word`, `ahead` (what the GPU is
+// to run during the host's round trip) behind it, the wait; sets c.done
+template <typename Ahead>
+static int bicg_poll(fg_state* s, const FgBicgArgs& a, BicgRun& c, int it, int word, int sys0, int nsys, hipStream_t st, Ahead ahead) {
+    c.next_poll = it + 1 + 2;
+    const int final_pass = (it + 1 == a.max_iterations);
+    fg_prof_prefetch(s, st);       // (in front of the polled kernel: its completion then covers the copy)
+    const FgPollOut po = fg_poll_next(&s->poll);
+    hipLaunchKernelGGL(k_bicg_check, dim3((nsys + 63) / 64), dim3(64), 0, st, c.q.acc, c.q.flags, c.q.info, s->info_pinned, a.tol, it, s->grid.n, nsys,
+                       final_pass, po, word, sys0);
+    if (int rc = ahead()) return rc;
+    // one read-back serves the poll and the result (nothing is launched after the last poll)
+    const int active = fg_poll_wait_active(&s->poll, po, sys0, nsys, s->info_pinned, st);
+    if (active < 0) return active;
+    c.info_fresh = true;
+    c.done = (active == 0);
+    return FG_OK;
+}
+static int bicg_poll(fg_state* s, const FgBicgArgs& a, BicgRun& c, int it, int word, int sys0, int nsys, hipStream_t st) {
+    return bicg_poll(s, a, c, it, word, sys0, nsys, st, [] { return FG_OK; });
+}
 
-#define FG_BICG_LAUNCH(SLOT, KERNEL, ...) FG_BICG_LAUNCH_Y(a.nc, SLOT, KERNEL, __VA_ARGS__)
-    bool done = false, info_fresh = false;
-    // first convergence poll where the previous solve finished (kernels of converged systems exit at once,
-    // so over-launching costs ~2 us per kernel while every poll costs a stream sync), then every 2 iterations
-    int next_poll = s->pred_bicg[a.kind & 3] > 1 ? s->pred_bicg[a.kind & 3] : 1;
-    const double cells = (double)n, mat = 4.0 * (1 + 2 * s->grid.dims) / a.nc, fl = 2.0 * (1 + 2 * s->grid.dims);
-    // (3-D: the neighbour recomputation of four fields across six faces costs more than the two saved passes -- measured on TCF
-    //  128 x 64 x 64: 299 us per iteration against 260 us -- so the five kernels stay there)
-    int zc3 = 0;
-#if FG_F64
-    const bool zmarch3 = false; (void)zc3;
-#else
-    // 3-D: the two-kernel form as z-marching LDS-ring kernels (fg_bicgstab3d.hip) when the grid fits its tiles and fills the chip
-    const bool zmarch3 = s->bicg_fused && !a.precond && s->grid.dims == 3 && fg_bicg3_ok(s, a.nc, &zc3);
-#endif
-    if (s->bicg_fused && !a.precond && (s->grid.dims == 2 || s->bicg_fused >= 2 || zmarch3)) {
-        // two-kernel iteration (k_bicgf_a / k_bicgf_b above): per system and cell, a reads x, p, s, t, v, rw + the matrix and writes
-        // x, r, p, v (40 + mat B); b reads r, v, rw + the matrix and writes s, t (20 + mat B)
-        BicgFused w;
-        w.s = s->w[7]; w.p[0] = s->w[2]; w.p[1] = s->w[5]; w.v[0] = s->w[3]; w.v[1] = s->w[6];
-        w.fold0 = a.use_x0 ? 0 : 1;      // zero start vector: r_0 = p_0 = rw = rhs, no init kernel (fg_bicg.h BicgFused::fold0)
+// Sub-batches of envs (2-D brick kernels): when the working set of the solve -- nine vectors per system, the matrix, the
+// right-hand sides -- is far beyond the 256 MB Infinity Cache, the envs are solved in groups whose set fits it (the systems are
+// independent), so that the iterations of a group stream from the cache instead of HBM: `large_env` (512 x 256 x 64, 839 MB)
+// runs its launches at the headline's size and efficiency (k_bicgf_a 0.56 -> ~0.68 of the HBM figure) -- FG_BICG_SUB=0 / N
+static int bicg_sub_batch(const fg_state* s, int nc) {
+    const int B = s->grid.B, n = s->grid.n;
+    if (s->grid.dims != 2) return B;
+    const double per_env = (double)n * sizeof(fg_real) * (nc * 9.0 + (1 + 2 * s->grid.dims) + nc);
+    if (s->bicg_sub > 0) return s->bicg_sub < B ? s->bicg_sub : B;
+    if (!(s->bicg_sub < 0 && per_env * B > 400e6)) return B;
+    int nb_sub = (int)(220e6 / per_env);
+    const int tiles_env = (int)((n / (s->vec == 4 ? 4 : 1) + FG_BLOCK - 1) / FG_BLOCK);
+    while (nb_sub < B && (long)nb_sub * tiles_env < 1024) ++nb_sub;     // keep the chip filled
+    if (nb_sub < 1) nb_sub = 1;
+    if (nb_sub >= B) return B;
+    return (B + (B + nb_sub - 1) / nb_sub - 1) / ((B + nb_sub - 1) / nb_sub);   // even groups
+}
+
+// r_0 = rhs - C x0, rw = p_0 = r_0 with p_0 into `p0`, r.r into the accumulator words word_a and (>= 0) word_b
+// (defined in front of the other launches: the kernel templates are instantiated in the order the host code names them, and the
+//  register allocation of k_bicgf_a has been seen to follow that order)
+static void bicg_launch_init(fg_state* s, BicgRun& c, const FgGrid& gsub, fg_real* p0, int word_a, int word_b, int use_x0, hipStream_t st) {
+    BICG_LAUNCH(gsub, 1, -1, k_bicg_init, p0, word_a, word_b, use_x0);
+}
+
+// the two kernels of the two-kernel form over the envs of gsub, each as a brick or a z-marching launch (BicgForm::za / zb)
+static int bicg_two_a(fg_state* s, BicgRun& c, const FgGrid& gsub, int it, int slot, hipStream_t st) {
 #if !FG_F64
-        const bool za = zmarch3 && (s->bicg3_mix & 1), zb = zmarch3 && (s->bicg3_mix & 2);   // (FG_BICG3_MIX: the two forms share buffers and accumulators)
-        // start vector zero on the z-marching kernels: r_0 = p_0 = rw = rhs, no init kernel (fg_bicg.h BicgFused::fold0; FG_BICG3_MIX & 4 keeps it)
-        w.fold0 = (!a.use_x0 && !(s->bicg3_mix & 4) && (za == zb)) ? 1 : 0;     // (brick and z-marching kernels alike; not when the two are mixed)
+    if (c.form.za) return fg_bicg3_launch_a(s, c.q, c.w, it, c.form.zc, slot, st);
 #endif
-        // Sub-batches of envs (2-D brick kernels): when the working set of the solve -- nine vectors per system, the matrix, the
-        // right-hand sides -- is far beyond the 256 MB Infinity Cache, the envs are solved in groups whose set fits it (the systems are
-        // independent), so that the iterations of a group stream from the cache instead of HBM: `large_env` (512 x 256 x 64, 839 MB)
-        // runs its launches at the headline's size and efficiency (k_bicgf_a 0.56 -> ~0.68 of the HBM figure) -- FG_BICG_SUB=0 / N
-        int nb_sub = B;
+    BICG_LAUNCH(gsub, 1, slot, k_bicgf_a, c.w, it);
+    return FG_OK;
+}
+static int bicg_two_b(fg_state* s, BicgRun& c, const FgGrid& gsub, int it, int slot, hipStream_t st) {
 #if !FG_F64
-        if (s->grid.dims == 2 && !za && !zb) {
-#else
-        if (s->grid.dims == 2) {
+    if (c.form.zb) return fg_bicg3_launch_b(s, c.q, c.w, it, c.form.zc, slot, st);
 #endif
-            const double per_env = (double)n * sizeof(fg_real) * (a.nc * 9.0 + (1 + 2 * s->grid.dims) + a.nc);
-            if (s->bicg_sub > 0) nb_sub = s->bicg_sub < B ? s->bicg_sub : B;
-            else if (s->bicg_sub < 0 && per_env * B > 400e6) {
-                nb_sub = (int)(220e6 / per_env);
-                const int tiles_env = (int)((n / (s->vec == 4 ? 4 : 1) + FG_BLOCK - 1) / FG_BLOCK);
-                while (nb_sub < B && (long)nb_sub * tiles_env < 1024) ++nb_sub;     // keep the chip filled
-                if (nb_sub < 1) nb_sub = 1;
-                if (nb_sub >= B) nb_sub = B;
-                else nb_sub = (B + (B + nb_sub - 1) / nb_sub - 1) / ((B + nb_sub - 1) / nb_sub);   // even groups
-            }
-        }
-        const int pred0 = next_poll;
-        int started_b0 = -1;      // group whose first kernels were launched ahead, behind the previous group's poll (see below)
-        for (int b0 = 0; b0 < B; b0 += nb_sub) {
-        gsub.b0 = b0; gsub.B = (b0 + nb_sub <= B) ? nb_sub : B - b0;
+    BICG_LAUNCH(gsub, 1, slot, k_bicgf_b, c.w, it);
+    return FG_OK;
+}
+// the first kernels of a group: r_0 (unless the start is folded into kernel a: BicgFused::fold0) and kernel a(0)
+static int bicg_two_start(fg_state* s, const FgBicgArgs& a, BicgRun& c, const FgGrid& gsub, hipStream_t st) {
+    if (!c.w.fold0) bicg_launch_init(s, c, gsub, c.w.p[0], F_RR, -1, a.use_x0, st);
+    return bicg_two_a(s, c, gsub, 0, -1, st);
+}
+
+// two-kernel iteration (k_bicgf_a / k_bicgf_b above): per system and cell, a reads x, p, s, t, v, rw + the matrix and writes
+// x, r, p, v (40 + mat B); b reads r, v, rw + the matrix and writes s, t (20 + mat B).  Each group of envs goes through all its
+// iterations and polls before the next.
+static int bicg_iterate_two(fg_state* s, const FgBicgArgs& a, BicgRun& c, hipStream_t st) {
+    const int B = s->grid.B;
+    BicgFused& w = c.w;
+    w.s = s->w[7]; w.p[0] = s->w[2]; w.p[1] = s->w[5]; w.v[0] = s->w[3]; w.v[1] = s->w[6];
+    // start vector zero: r_0 = p_0 = rw = rhs, no init kernel (fg_bicg.h BicgFused::fold0; brick and z-marching kernels alike)
+    w.fold0 = (!a.use_x0 && !c.form.keep_init) ? 1 : 0;
+    const int nb_sub = bicg_sub_batch(s, a.nc), pred0 = c.next_poll;
+    auto group = [&](int b0) { FgGrid g = s->grid; g.b0 = b0; g.B = (b0 + nb_sub <= B) ? nb_sub : B - b0; return g; };
+    int started_b0 = -1;      // group whose first kernels were launched ahead, behind the previous group's poll (see below)
+    for (int b0 = 0; b0 < B; b0 += nb_sub) {
+        const FgGrid gsub = group(b0);
         const int sys0 = b0 * a.nc, nsys_sub = gsub.B * a.nc;
-        done = false; next_poll = pred0;
-        if (started_b0 != b0) {
-        if (!w.fold0) FG_BICG_LAUNCH_Y(1, -1, k_bicgf_init, w, a.use_x0);
-#if !FG_F64
-        if (za) { if (int rc = fg_bicg3_launch_a(s, q, w, 0, zc3, -1, st)) return rc; }
-        else
-#endif
-        FG_BICG_LAUNCH_Y(1, -1, k_bicgf_a, w, 0);
-        }
-        for (int it = 0; it < a.max_iterations && !done; ++it) {
-#if !FG_F64
-            if (zb) { if (int rc = fg_bicg3_launch_b(s, q, w, it, zc3, fg_prof_slot(s, FG_PK_BICGF_B, q.flags + sys0, nsys_sub, cells * (20.0 + mat), cells * (fl + 12.0), st), st)) return rc; }
-            else
-#endif
-            FG_BICG_LAUNCH_Y(1, fg_prof_slot(s, FG_PK_BICGF_B, q.flags + sys0, nsys_sub, cells * (20.0 + mat), cells * (fl + 12.0), st), k_bicgf_b, w, it);
-#if !FG_F64
-            if (za) { if (int rc = fg_bicg3_launch_a(s, q, w, it + 1, zc3, fg_prof_slot(s, FG_PK_BICGF_A, q.flags + sys0, nsys_sub, cells * (40.0 + mat), cells * (fl + 14.0), st), st)) return rc; }
-            else
-#endif
-            FG_BICG_LAUNCH_Y(1, fg_prof_slot(s, FG_PK_BICGF_A, q.flags + sys0, nsys_sub, cells * (40.0 + mat), cells * (fl + 14.0), st), k_bicgf_a, w, it + 1);
-            if (it + 1 >= next_poll || it + 1 == a.max_iterations) {
-                next_poll = it + 1 + 2;
-                const int final_pass = (it + 1 == a.max_iterations);
-                fg_prof_prefetch(s, st);       // (in front of the polled kernel: its completion then covers the copy)
-                const FgPollOut po = fg_poll_next(&s->poll);
-                hipLaunchKernelGGL(k_bicgf_check, dim3((nsys_sub + 63) / 64), sb, 0, st, q.acc, q.flags, q.info, s->info_pinned, a.tol, it, n, nsys_sub,
-                                   final_pass, po, sys0);
-                if (nb_sub < B && b0 + nb_sub < B && started_b0 != b0 + nb_sub) {
-                    // the next group's first kernels go out behind this group's check, so that the GPU has work during the host's round
-                    // trip (polls are placed where solves usually end); the groups share nothing, whatever this poll says
-                    const FgGrid keep = gsub;
-                    gsub.b0 = b0 + nb_sub; gsub.B = (gsub.b0 + nb_sub <= B) ? nb_sub : B - gsub.b0;
-                    if (!w.fold0) FG_BICG_LAUNCH_Y(1, -1, k_bicgf_init, w, a.use_x0);
-                    FG_BICG_LAUNCH_Y(1, -1, k_bicgf_a, w, 0);
-                    gsub = keep;
-                    started_b0 = b0 + nb_sub;
-                }
-                if (int rc = fg_poll_wait_infos(&s->poll, po, sys0, nsys_sub, s->info_pinned, st)) return rc;
-                info_fresh = true;
-                done = true;
-                for (int i = sys0; i < sys0 + nsys_sub; ++i) done = done && (s->info_pinned[i].converged || !s->info_pinned[i].is_finite);
+        c.done = false; c.next_poll = pred0;
+        if (started_b0 != b0)
+            if (int rc = bicg_two_start(s, a, c, gsub, st)) return rc;
+        for (int it = 0; it < a.max_iterations && !c.done; ++it) {
+            const int slot_b = fg_prof_slot(s, FG_PK_BICGF_B, c.q.flags + sys0, nsys_sub, c.cells * (20.0 + c.mat), c.cells * (c.fl + 12.0), st);
+            if (int rc = bicg_two_b(s, c, gsub, it, slot_b, st)) return rc;
+            const int slot_a = fg_prof_slot(s, FG_PK_BICGF_A, c.q.flags + sys0, nsys_sub, c.cells * (40.0 + c.mat), c.cells * (c.fl + 14.0), st);
+            if (int rc = bicg_two_a(s, c, gsub, it + 1, slot_a, st)) return rc;
+            if (it + 1 >= c.next_poll || it + 1 == a.max_iterations) {
+                // the next group's first kernels go out behind this group's check, so that the GPU has work during the host's round
+                // trip (polls are placed where solves usually end); the groups share nothing, whatever this poll says
+                const bool ahead = b0 + nb_sub < B && started_b0 != b0 + nb_sub;
+                if (int rc = bicg_poll(s, a, c, it, F_RR + ((it + 1) & 1), sys0, nsys_sub, st,
+                                       [&] { return ahead ? bicg_two_start(s, a, c, group(b0 + nb_sub), st) : FG_OK; })) return rc;
+                if (ahead) started_b0 = b0 + nb_sub;
             }
         }
-        }   // sub-batches
-        gsub = s->grid;
     }
+    return FG_OK;
+}
+
 #if !FG_F64
-    else if (a.precond == 2 && fg_fbicg_ok(s)) {
-        // Helmholtz-preconditioned iteration in SIX launches (fg_fftbicg.hip): the vector updates ride in the forward transforms, the
-        // matrix is applied by the inverse transforms, decisions and accumulators are those of the two-kernel form (fg_bicg.h)
-        BicgFused w;
-        w.s = q.r; w.p[0] = q.p; w.p[1] = q.p; w.v[0] = q.v; w.v[1] = q.v;
-        w.fold0 = a.use_x0 ? 0 : 1;
-        float* t1 = s->w[7];
-        if (!w.fold0) FG_BICG_LAUNCH_Y(1, -1, k_bicgf_init, w, a.use_x0);      // r = rhs - C x0, rw = p_0 = r, r.r
-        if (int rc = fg_fbicg_forward(s, q, 1, 0, w.fold0, st)) return rc;
+// Helmholtz-preconditioned iteration in SIX launches (fg_fftbicg.hip): the vector updates ride in the forward transforms, the
+// matrix is applied by the inverse transforms, decisions and accumulators are those of the two-kernel form (fg_bicg.h)
+static int bicg_iterate_helm(fg_state* s, const FgBicgArgs& a, BicgRun& c, hipStream_t st) {
+    const BicgPtrs& q = c.q;
+    const int nsys = s->grid.B * a.nc;
+    BicgFused& w = c.w;
+    w.s = q.r; w.p[0] = q.p; w.p[1] = q.p; w.v[0] = q.v; w.v[1] = q.v;
+    w.fold0 = a.use_x0 ? 0 : 1;
+    float* t1 = s->w[7];
+    if (!w.fold0) bicg_launch_init(s, c, s->grid, w.p[0], F_RR, -1, a.use_x0, st);
+    if (int rc = fg_fbicg_forward(s, q, 1, 0, w.fold0, st)) return rc;
+    if (int rc = fg_helm_apply(s, a.nc, t1, t1, st)) return rc;
+    if (int rc = fg_fbicg_inverse(s, q, 1, 0, st)) return rc;
+    for (int it = 0; it < a.max_iterations && !c.done; ++it) {
+        if (int rc = fg_fbicg_forward(s, q, 0, it, w.fold0, st)) return rc;
         if (int rc = fg_helm_apply(s, a.nc, t1, t1, st)) return rc;
-        if (int rc = fg_fbicg_inverse(s, q, 1, 0, st)) return rc;
-        for (int it = 0; it < a.max_iterations && !done; ++it) {
-            if (int rc = fg_fbicg_forward(s, q, 0, it, w.fold0, st)) return rc;
+        if (int rc = fg_fbicg_inverse(s, q, 0, it, st)) return rc;
+        if (int rc = fg_fbicg_forward(s, q, 1, it + 1, w.fold0, st)) return rc;
+        if (it + 1 >= c.next_poll || it + 1 == a.max_iterations) {
+            if (int rc = bicg_poll(s, a, c, it, F_RR + ((it + 1) & 1), 0, nsys, st)) return rc;
+            if (c.done) break;
+        }
+        if (it + 1 < a.max_iterations) {
             if (int rc = fg_helm_apply(s, a.nc, t1, t1, st)) return rc;
-            if (int rc = fg_fbicg_inverse(s, q, 0, it, st)) return rc;
-            if (int rc = fg_fbicg_forward(s, q, 1, it + 1, w.fold0, st)) return rc;
-            if (it + 1 >= next_poll || it + 1 == a.max_iterations) {
-                next_poll = it + 1 + 2;
-                const int final_pass = (it + 1 == a.max_iterations);
-                fg_prof_prefetch(s, st);
-                const FgPollOut po = fg_poll_next(&s->poll);
-                hipLaunchKernelGGL(k_bicgf_check, sg, sb, 0, st, q.acc, q.flags, q.info, s->info_pinned, a.tol, it, n, nsys, final_pass, po, 0);
-                if (int rc = fg_poll_wait_infos(&s->poll, po, 0, nsys, s->info_pinned, st)) return rc;
-                info_fresh = true;
-                done = true;
-                for (int i = 0; i < nsys; ++i) done = done && (s->info_pinned[i].converged || !s->info_pinned[i].is_finite);
-                if (done) break;
-            }
-            if (it + 1 < a.max_iterations) {
-                if (int rc = fg_helm_apply(s, a.nc, t1, t1, st)) return rc;
-                if (int rc = fg_fbicg_inverse(s, q, 1, it + 1, st)) return rc;
-            }
+            if (int rc = fg_fbicg_inverse(s, q, 1, it + 1, st)) return rc;
         }
     }
+    return FG_OK;
+}
 #endif
-    else {
-    FG_BICG_LAUNCH_Y(1, -1, k_bicg_init, a.use_x0);
-    for (int it = 0; it < a.max_iterations && !done; ++it) {
-        // algorithmic bytes per system and cell: Kp r,v,p -> p (16; the first iteration only checks) | Kv p,rw -> v + the
-        // (1 + 2d) matrix fields shared by the nc right-hand sides | Ks r,v -> s (12) | Kt s -> t + matrix |
-        // Kx x,p,s,t,rw -> x,r (28)
-        if (it > 0) FG_BICG_LAUNCH(fg_prof_slot(s, FG_PK_BICG_P, q.flags, nsys, cells * 16.0, cells * 4.0, st), k_bicg_p, it);
-        else FG_BICG_LAUNCH(-1, k_bicg_p, it);
+
+static int bicg_precondition(fg_state* s, const FgBicgArgs& a, const fg_real* in, fg_real* out, hipStream_t st) {
+    if (a.precond == 3) return fg_ilu_apply(s, a.diag, a.off, a.nc, in, out, st);
+    return a.precond == 2 ? fg_fd_helmholtz_apply(s, a.nc, in, out, st) : fg_line_apply(s, a.diag, a.off, a.nc, in, out, st);
+}
+
+// the five kernels, right-preconditioned when a.precond.  Algorithmic bytes per system and cell: Kp r,v,p -> p (16; the first
+// iteration only checks) | Kv p,rw -> v + the (1 + 2d) matrix fields shared by the nc right-hand sides | Ks r,v -> s (12) |
+// Kt s -> t + matrix | Kx x,p,s,t,rw -> x,r (28)
+static int bicg_iterate_five(fg_state* s, const FgBicgArgs& a, BicgRun& c, hipStream_t st) {
+    const BicgPtrs& q = c.q;
+    const int nsys = s->grid.B * a.nc;
+    const double cells = c.cells, mat = c.mat, fl = c.fl;
+    bicg_launch_init(s, c, s->grid, q.p, A_RHO, A_RR, a.use_x0, st);      // (rho_0 = rr = r.r)
+    for (int it = 0; it < a.max_iterations && !c.done; ++it) {
+        BICG_LAUNCH(s->grid, a.nc, it > 0 ? fg_prof_slot(s, FG_PK_BICG_P, q.flags, nsys, cells * 16.0, cells * 4.0, st) : -1, k_bicg_p, it);
         if (a.precond)
-            if (int rc = precondition(q.p, s->w[5])) return rc;
-        FG_BICG_LAUNCH_Y(1, fg_prof_slot(s, FG_PK_BICG_V, q.flags, nsys, cells * (12.0 + mat), cells * (fl + 2.0), st), k_bicg_v, it);
-        FG_BICG_LAUNCH(fg_prof_slot(s, FG_PK_BICG_S, q.flags, nsys, cells * 12.0, cells * 4.0, st), k_bicg_s, it);
+            if (int rc = bicg_precondition(s, a, q.p, s->w[5], st)) return rc;
+        BICG_LAUNCH(s->grid, 1, fg_prof_slot(s, FG_PK_BICG_V, q.flags, nsys, cells * (12.0 + mat), cells * (fl + 2.0), st), k_bicg_v, it);
+        BICG_LAUNCH(s->grid, a.nc, fg_prof_slot(s, FG_PK_BICG_S, q.flags, nsys, cells * 12.0, cells * 4.0, st), k_bicg_s, it);
         if (a.precond)
-            if (int rc = precondition(q.r, s->w[6])) return rc;
-        FG_BICG_LAUNCH_Y(1, fg_prof_slot(s, FG_PK_BICG_T, q.flags, nsys, cells * (8.0 + mat), cells * (fl + 4.0), st), k_bicg_t, it);
-        FG_BICG_LAUNCH(fg_prof_slot(s, FG_PK_BICG_X, q.flags, nsys, cells * 28.0, cells * 10.0, st), k_bicg_x, it);
-        if (it + 1 >= next_poll || it + 1 == a.max_iterations) {
-            next_poll = it + 1 + 2;
-            const int final_pass = (it + 1 == a.max_iterations);
-            // one read-back serves the poll and the result (nothing is launched after the last poll)
-            fg_prof_prefetch(s, st);
-            const FgPollOut po = fg_poll_next(&s->poll);
-            hipLaunchKernelGGL(k_bicg_check, sg, sb, 0, st, q.acc, q.flags, q.info, s->info_pinned, a.tol, it, n, nsys, final_pass, po);
-            if (int rc = fg_poll_wait_infos(&s->poll, po, 0, nsys, s->info_pinned, st)) return rc;
-            info_fresh = true;
-            done = true;
-            for (int i = 0; i < nsys; ++i) done = done && (s->info_pinned[i].converged || !s->info_pinned[i].is_finite);
-        }
+            if (int rc = bicg_precondition(s, a, q.r, s->w[6], st)) return rc;
+        BICG_LAUNCH(s->grid, 1, fg_prof_slot(s, FG_PK_BICG_T, q.flags, nsys, cells * (8.0 + mat), cells * (fl + 4.0), st), k_bicg_t, it);
+        BICG_LAUNCH(s->grid, a.nc, fg_prof_slot(s, FG_PK_BICG_X, q.flags, nsys, cells * 28.0, cells * 10.0, st), k_bicg_x, it);
+        if (it + 1 >= c.next_poll || it + 1 == a.max_iterations)
+            if (int rc = bicg_poll(s, a, c, it, A_RR, 0, nsys, st)) return rc;
     }
-    }
-#undef FG_BICG_LAUNCH
-#undef FG_BICG_LAUNCH_Y
-    if (!info_fresh) {
-        FG_HIP_CHECK(hipMemcpyAsync(s->info_pinned, s->info_dev, sizeof(fg_solve_info) * nsys, hipMemcpyDeviceToHost, st));
-        FG_HIP_CHECK(hipStreamSynchronize(st));
-    }
-    if (int prc = fg_prof_collect(s, st)) return prc;
-    int rc = FG_OK;
-    int used_max = 0;
-    for (int i = 0; i < nsys; ++i) used_max = s->info_pinned[i].used_iterations > used_max ? s->info_pinned[i].used_iterations : used_max;
-    s->pred_bicg[a.kind & 3] = used_max;
-    for (int i = 0; i < nsys; ++i) {
-        if (info_host) info_host[i] = s->info_pinned[i];
-        if (!s->info_pinned[i].is_finite) rc = FG_ERR_NOT_FINITE;
-        else if (!s->info_pinned[i].converged && rc == FG_OK) rc = FG_ERR_NOT_CONVERGED;
-    }
-    FG_HIP_CHECK(hipGetLastError());
-    return rc;
+    return FG_OK;
+}
+#undef BICG_LAUNCH
+
+// finish: info read-back, predictor update, status
+static int bicg_finish(fg_state* s, const FgBicgArgs& a, const BicgRun& c, fg_solve_info* info_host, hipStream_t st) {
+    const int nsys = s->grid.B * a.nc;
+    if (int rc = fg_solve_infos_settle(s, nsys, c.info_fresh, st)) return rc;
+    return fg_solve_infos_report(s, nsys, info_host, &s->pred_bicg[a.kind & 3]);
+}
+
+static int bicgstab_krylov(fg_state* s, const FgBicgArgs& a, fg_solve_info* info_host, hipStream_t st, bool begun) {
+    BicgRun c;
+    if (int rc = bicg_begin_run(s, a, c, st, begun)) return rc;
+    int rc;
+    if (c.form.kind == BICG_FIVE) rc = bicg_iterate_five(s, a, c, st);
+#if !FG_F64
+    else if (c.form.kind == BICG_HELM_SIX) rc = bicg_iterate_helm(s, a, c, st);
+#endif
+    else rc = bicg_iterate_two(s, a, c, st);
+    if (rc) return rc;
+    return bicg_finish(s, a, c, info_host, st);
 }
 
 #if !FG_F64

@@ -163,7 +163,7 @@ __global__ __launch_bounds__(256) void k_fbicg_fwd(FbicgArgs a) {
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // Inverse kernels: p^ / s^ = Qx u of eight rows (+ the halo pair), the advection-diffusion matrix on them, the dot products.
-// Five waves; grid (ceil(rows / 8), nsys).  The matrix rows are fg_spmv's (fg_bicgstab.hip): y = d x_c + sum_f o_f x_{N_f}, the
+// Five waves; grid (ceil(rows / 8), nsys).  The matrix rows are fg_apply_nbr's (fg_bicgstab.hip): y = d x_c + sum_f o_f x_{N_f}, the
 // off-diagonal of a prescribed face being zero in the assembled matrix (k_adv_build).
 // ---------------------------------------------------------------------------------------------------------------------------
 template <int N, int KIND>     // KIND 0: IT (t = C s^; t.s, t.t, rw.t)   1: IV (v = C p^; rw.v)

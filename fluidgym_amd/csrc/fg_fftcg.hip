@@ -347,13 +347,8 @@ __global__ __launch_bounds__(64 * CHECK_WAVES) void k_fcg_check0(FgDacc* __restr
         }
     }
     if (valid && lane == 0) lazy[b] = lz;
-    if (!mirror) return;
-    if (poll.gran) {      // (the verdicts travel in the words the host spins on: no release, no L2 write-back -- FgPollOut, fg_internal.h)
-        uint32_t w[2] = {0u, 0u};
-        const bool writer = valid && lane == 0;
-        if (writer) { const fg_solve_info v = info[b]; w[0] = __float_as_uint(v.final_residual); w[1] = fg_info_word(v); }
-        fg_poll_publish_records<2>(poll, b0, min(CHECK_WAVES, B - b0), wave, w, writer, stage);
-    } else if (valid && lane == 0) { mirror[b] = info[b]; fg_poll_publish(poll, b); }
+    // (the verdicts travel in the words the host spins on where the poll has them: no release, no L2 write-back -- FgPollOut, fg_internal.h)
+    fg_poll_publish_infos_waves(poll, mirror, info, b, valid, b0, min(CHECK_WAVES, B - b0), stage);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------

@@ -570,6 +570,12 @@ struct FgProf {
 // poll_latency.hip): kernel -> host -> next kernel costs 6 us this way against 11.5 us through hipStreamSynchronize, 4-5 times per
 // PISO step.  Streams are in order, so "the polled kernel has finished" still means everything launched before it has.
 struct FgJacHist { int sweeps, skip, fails; };
+// the history of a solve kind's sweeps, shared by their drivers (fg_jacobi.hip, fg_linepre.hip).  enter: false while the kind sits out
+// the solves its last give-up cost it | gave_up: back off (8, 16, ... 256, then 512 solves) | solved: `sweeps` is what the next solve
+// of the kind enqueues ahead of its first poll
+inline bool fg_sweeps_enter(FgJacHist& H) { if (H.skip > 0) { --H.skip; return false; } return true; }
+inline void fg_sweeps_gave_up(FgJacHist& H) { H.fails += 1; H.skip = H.fails > 6 ? 512 : (4 << H.fails); H.sweeps = 0; }
+inline void fg_sweeps_solved(FgJacHist& H, int sweeps) { H.fails = 0; H.sweeps = sweeps; }
 // Round 6: result WORDS.  A kernel that publishes through the release above pays a write-back of its XCD's L2 (the 4-5 us the one-wave
 // verdict kernels took were that write-back, and the host saw the verdict that much later).  A result that fits 32 bits can instead
 // travel IN the word the host spins on: one 8-byte system-scope store {payload, sequence number} per result -- a single store is
@@ -613,6 +619,12 @@ __device__ __forceinline__ void fg_poll_publish_infos(const FgPollOut& p, fg_sol
         fg_poll_publish(p, sys);      // (after the entry: the host spins on this word instead of synchronising the stream)
     }
 }
+// the same end for a verdict kernel with one WAVE per system (fg_acc_total is a wave's shuffle tree): lane 0 is the system's thread;
+// mirror == nullptr: nothing is published.  `stage`: 2 words of LDS per wave.
+__device__ __forceinline__ void fg_poll_publish_infos_waves(const FgPollOut& p, fg_solve_info* mirror, const fg_solve_info* info, int sys, bool valid,
+                                                            int first, int n, uint32_t* stage) {
+    if (mirror) fg_poll_publish_infos(p, mirror, info, sys, valid && (threadIdx.x & 63) == 0, first, n, stage);
+}
 __device__ __forceinline__ void fg_poll_publish(const FgPollOut& p, int i) {
     // system-scope release: the results stored before it (by this thread, or by threads it synchronised with) are visible to the
     // host once the word is.  It writes the L2 back, so a kernel calls it from as few threads as possible, and after all its
@@ -635,6 +647,15 @@ int fg_poll_wait(FgPoll* P, const FgPollOut& out, int first, int count, hipStrea
 int fg_poll_wait_words(FgPoll* P, const FgPollOut& out, int first, int count, hipStream_t st);
 // infos of systems [first, first + count) into `pinned` (where the mirror form leaves them): result words when the poll has them
 int fg_poll_wait_infos(FgPoll* P, const FgPollOut& out, int first, int count, fg_solve_info* pinned, hipStream_t st);
+// the wait of a solver's poll round (the caller has launched its verdict kernel with `out`, and whatever it wants to run during the
+// round trip): fg_poll_wait_infos, then how many of the systems still iterate (neither converged nor non-finite); < 0: an error code
+int fg_poll_wait_active(FgPoll* P, const FgPollOut& out, int first, int count, fg_solve_info* pinned, hipStream_t st);
+// the end of a Krylov solve over systems [0, count) (fg_poll.hip).  fg_solve_infos_settle: the infos into s->info_pinned unless a poll
+// left them there (`fresh`), and the profiler's samples folded in (the stream is idle afterwards).  fg_solve_infos_report: the infos
+// to the caller, the solve's status, *used_max = the largest used_iterations (what the iteration predictors remember)
+struct fg_state;
+int fg_solve_infos_settle(fg_state* s, int count, bool fresh, hipStream_t st);
+int fg_solve_infos_report(const fg_state* s, int count, fg_solve_info* info_host, int* used_max);
 inline uint32_t fg_poll_word(const FgPoll* P, int i) { return (uint32_t)(__atomic_load_n(P->gran + i, __ATOMIC_RELAXED) & 0xffffffffull); }
 inline float fg_poll_word_float(const FgPoll* P, int i) { const uint32_t u = fg_poll_word(P, i); float f; memcpy(&f, &u, 4); return f; }
 inline void fg_poll_info(const FgPoll* P, int sys, fg_solve_info* out) {

@@ -585,7 +585,7 @@ static int jacobi_stream_solve(fg_state* s, const FgBicgArgs& a, fg_solve_info* 
 int fg_jacobi_solve(fg_state* s, const FgBicgArgs& a, fg_solve_info* info_host, hipStream_t st, FgSweepOutcome* outcome) {
     *outcome = FG_SWEEP_NOT_TRIED;
     FgJacHist& H = s->jac_hist[a.kind & 3];
-    if (H.skip > 0) { --H.skip; return FG_OK; }
+    if (!fg_sweeps_enter(H)) return FG_OK;
     *outcome = FG_SWEEP_GAVE_UP;
     if (!jac_onchip_ok(s, a)) return jacobi_stream_solve(s, a, info_host, st, outcome);
     const FgGrid& G = s->grid;
@@ -703,7 +703,7 @@ int fg_jacobi_solve(fg_state* s, const FgBicgArgs& a, fg_solve_info* info_host, 
     if (int prc = fg_prof_collect(s, st)) return prc;
     if (!ok) {
         // not the regime of the sweeps (or a non-finite system): the Krylov solver decides, and this kind waits before it tries again
-        H.fails += 1; H.skip = H.fails > 6 ? 512 : (4 << H.fails); H.sweeps = 0;
+        fg_sweeps_gave_up(H);
         return FG_OK;
     }
     // where did every env's last iterate land?  pass p wrote the result vector iff (p & 1) == last_parity; an env that stopped with
@@ -716,8 +716,7 @@ int fg_jacobi_solve(fg_state* s, const FgBicgArgs& a, fg_solve_info* info_host, 
     if (spec && settle) { fg_set_error("fg_jacobi_solve: speculated corrector kernels with an iterate outside the result vector"); return FG_ERR_HIP; }
     if (settle)
         hipLaunchKernelGGL(k_jac_settle, dim3(32, B), dim3(256), 0, st, (const float*)work, a.x, (const fg_solve_info*)s->info_dev, S, last_parity, 2 * n);
-    H.fails = 0;
-    H.sweeps = used_max > 0 ? used_max : S;
+    fg_sweeps_solved(H, used_max > 0 ? used_max : S);
     for (int i = 0; i < nsys; ++i)
         if (info_host) info_host[i] = s->info_pinned[i];
     FG_HIP_CHECK(hipGetLastError());
@@ -818,7 +817,7 @@ static int jacobi_stream_solve(fg_state* s, const FgBicgArgs& a, fg_solve_info* 
     }
     if (int prc = fg_prof_collect(s, st)) return prc;
     if (!ok) {
-        H.fails += 1; H.skip = H.fails > 6 ? 512 : (4 << H.fails); H.sweeps = 0;
+        fg_sweeps_gave_up(H);
         return FG_OK;      // (*outcome stays FG_SWEEP_GAVE_UP)
     }
     int used_max = 0;
@@ -828,7 +827,7 @@ static int jacobi_stream_solve(fg_state* s, const FgBicgArgs& a, fg_solve_info* 
         // released by the fp32-floor rule: converged with a measured residual at or above the tolerance (reported, not hidden: fg_config_dump)
         if (s->info_pinned[i].converged && s->info_pinned[i].used_iterations >= 0 && s->info_pinned[i].final_residual >= a.tol) s->jac_floor_released += 1;
     }
-    H.fails = 0; H.sweeps = used_max > 0 ? used_max : FIRST;
+    fg_sweeps_solved(H, used_max > 0 ? used_max : FIRST);
     *outcome = FG_SWEEP_SOLVED;
     return FG_OK;
 }

@@ -809,7 +809,7 @@ bool fg_linesweep_ok(const fg_state* s, const FgBicgArgs& a) {
 int fg_linesweep_solve(fg_state* s, const FgBicgArgs& a, fg_solve_info* info_host, hipStream_t st, FgSweepOutcome* outcome) {
     *outcome = FG_SWEEP_NOT_TRIED;
     FgJacHist& H = s->jac_hist[a.kind & 3];
-    if (H.skip > 0) { --H.skip; return FG_OK; }
+    if (!fg_sweeps_enter(H)) return FG_OK;
     *outcome = FG_SWEEP_GAVE_UP;
     if (!line_use_lds(s)) return FG_OK;
     if (int rc = fg_line_alloc(s)) return rc;
@@ -874,7 +874,7 @@ int fg_linesweep_solve(fg_state* s, const FgBicgArgs& a, fg_solve_info* info_hos
     }
     if (int prc = fg_prof_collect(s, st)) return prc;
     if (!ok) {
-        H.fails += 1; H.skip = H.fails > 6 ? 512 : (4 << H.fails); H.sweeps = 0;
+        fg_sweeps_gave_up(H);
         return FG_OK;
     }
     int used_max = 0;
@@ -882,7 +882,7 @@ int fg_linesweep_solve(fg_state* s, const FgBicgArgs& a, fg_solve_info* info_hos
         used_max = s->info_pinned[i].used_iterations > used_max ? s->info_pinned[i].used_iterations : used_max;
         if (info_host) info_host[i] = s->info_pinned[i];
     }
-    H.fails = 0; H.sweeps = used_max > 0 ? used_max : FIRST;
+    fg_sweeps_solved(H, used_max > 0 ? used_max : FIRST);
     *outcome = FG_SWEEP_SOLVED;
     return FG_OK;
 }

@@ -321,16 +321,7 @@ __global__ __launch_bounds__(64 * CG_CHECK_WAVES) void k_cg_check(FgDacc* __rest
             }
         }
     }
-    if (!mirror) return;
-    const bool writer = valid && lane == 0;
-    if (poll.gran) {
-        uint32_t w[2] = {0u, 0u};
-        if (writer) { const fg_solve_info v = info[b]; w[0] = __float_as_uint((float)v.final_residual); w[1] = fg_info_word(v); }
-        fg_poll_publish_records<2>(poll, b0, min(CG_CHECK_WAVES, B - b0), wave, w, writer, stage);
-    } else if (writer) {
-        mirror[b] = info[b];
-        fg_poll_publish(poll, b);      // (after the entry: the host spins on this word instead of synchronising the stream)
-    }
+    fg_poll_publish_infos_waves(poll, mirror, info, b, valid, b0, min(CG_CHECK_WAVES, B - b0), stage);
 }
 
 __global__ void k_cg_begin(const fg_real* __restrict__ dt, FgCgBegin q, int B) {
@@ -515,8 +506,8 @@ static int cg_iterate_fused(fg_state* s, const FgCgArgs& a, CgRun& c, FgCgOutcom
         // ended after one iteration: if every env ends here nothing is left to do but write x_1 = alpha z -- or not even that
         // (lazy_ok: the corrector reads alpha z itself)
         const bool poll0 = c.next_poll <= 1;
-        const FgPollOut po = poll0 ? fg_poll_next(&s->poll) : FgPollOut{nullptr, 0};
         if (poll0) fg_prof_prefetch(s, st);
+        const FgPollOut po = poll0 ? fg_poll_next(&s->poll) : FgPollOut{nullptr, 0};
         if (int rc = fg_fcg_check0(s, a.tol, ns, st, po, &o.marks_valid)) return rc;
         bool spec = false;
         if (poll0 && s->fcg_spec && a.spec.fn && a.lazy_ok && r0 && c.mean_sums) {
@@ -528,16 +519,14 @@ static int cg_iterate_fused(fg_state* s, const FgCgArgs& a, CgRun& c, FgCgOutcom
         }
         if (poll0) {
             fg_htrace("cg_check_launched");
-            if (int rc = fg_poll_wait_infos(&s->poll, po, 0, B, s->info_pinned, st)) return rc;
+            const int active = fg_poll_wait_active(&s->poll, po, 0, B, s->info_pinned, st);
+            if (active < 0) return active;
             fg_htrace("cg_poll_done");
             c.info_fresh = true;
             s->fcg_first_polls += 1;
-            bool all = true, all_ok = true;
-            for (int b = 0; b < B; ++b) {
-                all = all && (s->info_pinned[b].converged || !s->info_pinned[b].is_finite);
-                all_ok = all_ok && s->info_pinned[b].converged && s->info_pinned[b].is_finite;
-            }
-            if (all) {
+            if (active == 0) {
+                bool all_ok = true;
+                for (int b = 0; b < B; ++b) all_ok = all_ok && s->info_pinned[b].converged && s->info_pinned[b].is_finite;
                 if (a.lazy_ok && r0 && all_ok && c.mean_sums) {
                     o.lazy_z = v.z; s->fcg_unstored += 1; o.spec_done = spec;
                 } else {
@@ -572,11 +561,11 @@ static int cg_iterate_fused(fg_state* s, const FgCgArgs& a, CgRun& c, FgCgOutcom
             hipLaunchKernelGGL(k_cg_check, dim3((B + CG_CHECK_WAVES - 1) / CG_CHECK_WAVES), dim3(64 * CG_CHECK_WAVES), 0, st, s->cg_acc, s->flags, s->info_dev, s->info_pinned, a.tol, it,
                                n, B, final_pass, ns, po);
             fg_htrace("cg_check_launched");
-            if (int rc = fg_poll_wait_infos(&s->poll, po, 0, B, s->info_pinned, st)) return rc;
+            const int active = fg_poll_wait_active(&s->poll, po, 0, B, s->info_pinned, st);
+            if (active < 0) return active;
             fg_htrace("cg_poll_done");
             c.info_fresh = true;
-            c.done = true;
-            for (int b = 0; b < B; ++b) c.done = c.done && (s->info_pinned[b].converged || !s->info_pinned[b].is_finite);
+            c.done = (active == 0);
             if (c.done) break;
         }
         if (it + 1 < a.max_iterations) {
@@ -661,17 +650,12 @@ static int cg_iterate_classic(fg_state* s, const FgCgArgs& a, CgRun& c, FgCgOutc
             // The poll comes BEFORE the preconditioner of the next iteration: polls are scheduled where the previous solve
             // finished, so they usually end the solve, and three kernels of M^-1 that would find every env converged
             // cost more than the idle round trip of a poll that does not.
-            if (int rc = fg_poll_wait_infos(&s->poll, po, 0, B, s->info_pinned, st)) return rc;
+            const int active = fg_poll_wait_active(&s->poll, po, 0, B, s->info_pinned, st);
+            if (active < 0) return active;
             c.info_fresh = true;
-            c.done = true;
-            active_est = 0;
-            for (int b = 0; b < B; ++b) {
-                const bool fin = s->info_pinned[b].converged || !s->info_pinned[b].is_finite;
-                c.done = c.done && fin;
-                active_est += !fin;
-            }
-            if (active_est < 1) active_est = 1;
+            c.done = (active == 0);
             if (c.done) break;
+            active_est = active;
         }
         if (a.precond && it + 1 < a.max_iterations) {
             // z = M^-1 r and r.z of the next iteration (envs that just converged are skipped via flags)
@@ -687,11 +671,7 @@ static int cg_iterate_classic(fg_state* s, const FgCgArgs& a, CgRun& c, FgCgOutc
 // finish: info read-back, best-iterate restore, predictor update, status
 static int cg_finish(fg_state* s, const FgCgArgs& a, const CgRun& c, FgCgOutcome& o, fg_solve_info* info_host, hipStream_t st) {
     const int B = s->grid.B, n = s->grid.n;
-    if (!c.info_fresh) {
-        FG_HIP_CHECK(hipMemcpyAsync(s->info_pinned, s->info_dev, sizeof(fg_solve_info) * B, hipMemcpyDeviceToHost, st));
-        FG_HIP_CHECK(hipStreamSynchronize(st));
-    }
-    if (int prc = fg_prof_collect(s, st)) return prc;
+    if (int rc = fg_solve_infos_settle(s, B, c.info_fresh, st)) return rc;
     bool failed = false;
     for (int b = 0; b < B; ++b) failed = failed || !s->info_pinned[b].converged;
     if (failed) {  // rare path: hand back the best iterate instead of the last one (results land in the pinned mirror)
@@ -699,18 +679,9 @@ static int cg_finish(fg_state* s, const FgCgArgs& a, const CgRun& c, FgCgOutcome
         hipLaunchKernelGGL(k_cg_restore_best, dim3(32, B), dim3(FG_BLOCK), 0, st, a.x, s->info_dev, s->info_pinned, s->cg_best, n);
         FG_HIP_CHECK(hipStreamSynchronize(st));
     }
-    int rc = FG_OK;
-    if (a.precond) {
-        int used_max = 0;
-        for (int b = 0; b < B; ++b) used_max = s->info_pinned[b].used_iterations > used_max ? s->info_pinned[b].used_iterations : used_max;
-        s->pred_cg[a.kind & 3] = used_max;
-    }
-    for (int b = 0; b < B; ++b) {
-        if (info_host) info_host[b] = s->info_pinned[b];
-        if (!s->info_pinned[b].is_finite) rc = FG_ERR_NOT_FINITE;
-        else if (!s->info_pinned[b].converged && rc == FG_OK) rc = FG_ERR_NOT_CONVERGED;
-    }
-    FG_HIP_CHECK(hipGetLastError());
+    int used_max = 0;
+    const int rc = fg_solve_infos_report(s, B, info_host, &used_max);
+    if (a.precond) s->pred_cg[a.kind & 3] = used_max;
     return rc;
 }
 

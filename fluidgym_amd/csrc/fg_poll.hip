@@ -86,6 +86,34 @@ int fg_poll_wait_infos(FgPoll* P, const FgPollOut& out, int first, int count, fg
     return FG_OK;
 }
 
+int fg_poll_wait_active(FgPoll* P, const FgPollOut& out, int first, int count, fg_solve_info* pinned, hipStream_t st) {
+    if (int rc = fg_poll_wait_infos(P, out, first, count, pinned, st)) return rc;
+    int active = 0;
+    for (int i = first; i < first + count; ++i) active += !(pinned[i].converged || !pinned[i].is_finite);
+    return active;
+}
+
+int fg_solve_infos_settle(fg_state* s, int count, bool fresh, hipStream_t st) {
+    if (!fresh) {
+        FG_HIP_CHECK(hipMemcpyAsync(s->info_pinned, s->info_dev, sizeof(fg_solve_info) * count, hipMemcpyDeviceToHost, st));
+        FG_HIP_CHECK(hipStreamSynchronize(st));
+    }
+    return fg_prof_collect(s, st);
+}
+
+int fg_solve_infos_report(const fg_state* s, int count, fg_solve_info* info_host, int* used_max) {
+    int rc = FG_OK;
+    *used_max = 0;
+    for (int i = 0; i < count; ++i) *used_max = s->info_pinned[i].used_iterations > *used_max ? s->info_pinned[i].used_iterations : *used_max;
+    for (int i = 0; i < count; ++i) {
+        if (info_host) info_host[i] = s->info_pinned[i];
+        if (!s->info_pinned[i].is_finite) rc = FG_ERR_NOT_FINITE;
+        else if (!s->info_pinned[i].converged && rc == FG_OK) rc = FG_ERR_NOT_CONVERGED;
+    }
+    FG_HIP_CHECK(hipGetLastError());
+    return rc;
+}
+
 // ---- FG_HTRACE=1: host-side time stamps around the polls (diagnosis of the idle time between a polled kernel and the launch that
 // follows it); the deltas between consecutive tags are summed per pair and printed when the process ends
 #include <cstdio>
