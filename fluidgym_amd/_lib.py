@@ -94,6 +94,18 @@ class FgEnvSel(Structure):
     ]
 
 
+class FgFrameSpec(Structure):
+    """Which plane of a field ``fg_frame_colorize`` draws, and how it is oriented (``fg_frame_spec``)."""
+    _fields_ = [
+        ("channel", c_int32),
+        ("axis", c_int32),
+        ("index", c_int32),
+        ("transpose", c_int32),
+        ("flip_rows", c_int32),
+        ("flip_cols", c_int32),
+    ]
+
+
 class FgStepOptions(Structure):
     _fields_ = [
         ("corrector_steps", c_int32),
@@ -251,6 +263,8 @@ SIGNATURES = {
                                     POINTER(ctypes.c_float), c_int, c_int, POINTER(c_void_p)]),
     "fg_resampler_destroy": (c_int, [c_void_p]),
     "fg_resample": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "fg_frame_colorize": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(FgFrameSpec), c_void_p, c_void_p, c_void_p,
+                                  POINTER(c_int32), c_int32, c_void_p, c_void_p]),
     "fg_envglue_jet_schedule": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "fg_envglue_channel_observe": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_void_p,
                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -344,7 +358,7 @@ _F64_STRUCTS[FgMbSimOptions] = _f64_struct(FgMbSimOptions)
 FgStepOptionsF64, FgSimOptionsF64 = _F64_STRUCTS[FgStepOptions], _F64_STRUCTS[FgSimOptions]
 FgMbStepOptionsF64, FgMbSimOptionsF64 = _F64_STRUCTS[FgMbStepOptions], _F64_STRUCTS[FgMbSimOptions]
 _F64_KEEP_FLOAT = ("fg_set_fd_preconditioner", "fg_set_fd_fast_transform", "fg_set_fd_helmholtz", "fg_coords_to_transforms", "fg_stream_triad")
-_F64_ABSENT_PREFIXES = ("fg_resampl", "fg_sparse_", "fg_envglue_")
+_F64_ABSENT_PREFIXES = ("fg_resampl", "fg_sparse_", "fg_envglue_", "fg_frame_")
 
 
 def _f64_type(tp):

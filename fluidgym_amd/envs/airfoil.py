@@ -42,6 +42,7 @@ AIRFOIL_2D_DEFAULT_CONFIG = {
 }
 JET_CENTERS = (0.2, 0.4, 0.6)   # grid.py:14-15
 JET_WIDTH = 0.08
+VORTICITY_RENDER_RANGE = {1000: (-10, 10), 3000: (-12.5, 12.5), 5000: (-15, 15)}   # airfoil_env_base.py:38-42, by Reynolds number
 
 
 def points_in_polygon(poly: np.ndarray, pts: np.ndarray) -> np.ndarray:
@@ -343,6 +344,15 @@ class AirfoilEnvBase(CylinderEnvBase):
         v = self._resampler(cells)
         v[..., torch.as_tensor(self._airfoil_mask, device=v.device)] = 0.0
         return v
+
+    def _frame_specs(self):
+        """airfoil_env_base.py:38-45, 664-702: vorticity in the range of the Reynolds number, ``icefire``, y flipped (the reference
+        flips y and x of the field, the formatting flips the columns back); no pixel is blacked out (the section's pixels hold the
+        zero the mask of ``get_vorticity`` put there)."""
+        re = int(self._reynolds_number)
+        if re not in VORTICITY_RENDER_RANGE:
+            raise ValueError(f"no vorticity colour range for Reynolds number {re}: the table has {sorted(VORTICITY_RENDER_RANGE)}")
+        return self._vortex_frame_specs(VORTICITY_RENDER_RANGE[re], True, (None, None, None))
 
 
 class AirfoilEnv2D(AirfoilEnvBase):

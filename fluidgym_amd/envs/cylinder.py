@@ -242,6 +242,41 @@ class CylinderEnvBase(FieldStatisticsMixin, FlowStatisticsMixin, FluidEnv):     
     def _diagnostic_to_view(self, cells: torch.Tensor) -> torch.Tensor:
         return self._resampler(cells)
 
+    def _get_cylinder_mask(self) -> np.ndarray:
+        """Pixels ``[ny, nx]`` (3-D: repeated along z, ``[nz, ny, nx]``) inside the cylinder on the render grid
+        (cylinder_env_base.py:518-535)."""
+        nx, ny = self.render_shape[0], self.render_shape[1]
+        radius = self.cylinder_diameter / 2 * (ny - 1) / self.H
+        center_x = round((nx - 1) / self.L * 2.0)
+        center_y = round((ny - 1) / self.H * 2.0)
+        Y, X = np.ogrid[:ny, :nx]
+        mask = np.sqrt((X - center_x) ** 2 + (Y - center_y) ** 2) <= radius
+        if self._ndims == 3:
+            mask = np.repeat(mask[None, :, :], self.render_shape[2], axis=0)
+        return mask
+
+    def _vortex_frame_specs(self, value_range, flip_y: bool, masks) -> Dict[str, tuple]:
+        """The vorticity pictures the cylinder and airfoil envs share (cylinder_env_base.py:700-739, airfoil_env_base.py:664-702): the
+        planes, with the reference's literal indices, are ``frames.vortex_frame_specs``; ``masks`` in the order of its keys."""
+        from .frames import vortex_frame_specs
+
+        w = self.get_vorticity()
+        specs = vortex_frame_specs(self._ndims, w.shape[2:], flip_y)
+        return {key: (w, spec, value_range, "icefire", mask) for (key, spec), mask in zip(specs.items(), masks)}
+
+    def _frame_specs(self):
+        """cylinder_env_base.py:700-739: vorticity in (-10, 10), ``icefire``, the cylinder black.  The mask slices are the
+        reference's: ``[y, x]``; in 3-D ``mask[0]``, ``mask[:, 0, :]`` and ``mask[:, :, 0]`` (the last two hold no solid pixel; the
+        third is ``[z, y]`` laid over the ``[y, z]`` frame, which the render grid's equal y and z extents allow there and here)."""
+        m = self.__dict__.get("_cylinder_mask")
+        if m is None:
+            m = self._cylinder_mask = self._get_cylinder_mask()
+        if self._ndims == 2:
+            masks = (self._frame_mask("xy", m),)
+        else:
+            masks = (self._frame_mask("xy", m[0]), self._frame_mask("xz", m[:, 0, :]), self._frame_mask("yz", m[:, :, 0]))
+        return self._vortex_frame_specs((-10, 10), False, masks)
+
     def _get_drag_and_lift(self):
         """[B] in 2-D; [B, NZ] per spanwise layer in 3-D (face area = edge length x D / resolution, :676-689)."""
         f = self._ring.forces(self._domain, self._nu_forces, layer_height=self.D / self._circle_resolution_angular)

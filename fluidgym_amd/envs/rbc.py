@@ -327,6 +327,15 @@ class RBCEnvBase(FlowStatisticsMixin, FluidEnv):
     def _diagnostic_to_view(self, cells: torch.Tensor) -> torch.Tensor:
         return self._resampler(cells)
 
+    def _frame_specs(self):
+        """rbc_env_base.py:541-577: the temperature between ``T_cold`` and ``T_hot + heater_limit`` in ``rainbow``; the planes and
+        their orientation are ``frames.rbc_frame_specs``."""
+        from .frames import rbc_frame_specs
+
+        T = self.get_temperature().unsqueeze(1)
+        rng = (self._T_cold, self._T_hot + self._heater_limit)
+        return {key: (T, spec, rng, "rainbow", None) for key, spec in rbc_frame_specs(self._ndims, T.shape[2:]).items()}
+
     def _get_global_obs(self):
         """rbc_env_2d.py:175-194 / rbc_env_3d.py:291-330 with a leading env axis."""
         B, d = self._num_envs, self._ndims

@@ -63,6 +63,7 @@ SMALL_TCF_3D_DEFAULT_CONFIG = {
     "enable_actions": True,
     "differentiable": False,
 }
+VELOCITY_MAX = 0.9      # upper end of the speed pictures: tcf_env.py:49-60 holds this one value for every (D, Re_wall) it lists
 LARGE_TCF_3D_DEFAULT_CONFIG = {**SMALL_TCF_3D_DEFAULT_CONFIG, "resolution_x_z": 128, "L": 2 * np.pi, "D": np.pi}
 
 
@@ -396,6 +397,30 @@ class TCF3DBottomEnv(FlowStatisticsMixin, FluidEnv):
         super().start_flow_time_correlation(lags, every=every, stride=stride, channels=channels)
         e = np.asarray(self._block.edges[1], np.float64)                              # ETT and t+ from the nominal friction velocity
         self._flow_timecorr.set_wall_units(0.5 * (e[1:] + e[:-1]), self._nu, self._u_wall)
+
+    def _frame_wall_row(self) -> int:
+        """The cell row of the wall-parallel pictures.  The reference slices its uniform render grid, y-flipped, at pixel row
+        ``y_shape_idx // 2`` with ``y_shape_idx = round((y(y+ = 150) + delta) / H * render_shape[1])`` (tcf_env.py:684-686, 736);
+        the views here are on the simulation grid, so it is the cell row whose centre is nearest that pixel row's height."""
+        ny_r = self.render_shape[1]
+        y_shape_idx = round((self._y_wall_to_y(150) + self._delta) / self._H * ny_r)
+        row = ny_r - 1 - y_shape_idx // 2                                  # the pixel row before the flip
+        height = -self._delta + (row + 0.5) * self._H / ny_r
+        e = np.asarray(self._block.edges[1], np.float64)
+        return int(np.argmin(np.abs(0.5 * (e[1:] + e[:-1]) - height)))
+
+    def _frame_specs(self):
+        """tcf_env.py:679-751: the speed in (0, ``VELOCITY_MAX``), ``viridis``, and the vorticity in a range symmetric about zero
+        over the whole three-component field, ``icefire``; the planes, with the reference's literal indices, are
+        ``frames.tcf_frame_specs``."""
+        from .frames import range_over, tcf_frame_specs
+
+        u, w = self.get_velocity(), self.get_vorticity()
+        w_range = range_over(w, symmetric=True)                          # taken once for the three pictures
+        out = {}
+        for key, spec in tcf_frame_specs(u.shape[2:], self._frame_wall_row()).items():
+            out[key] = (u, spec, (0.0, VELOCITY_MAX), "viridis", None) if key.endswith("velocity") else (w, spec, w_range, "icefire", None)
+        return out
 
     @property
     def id(self) -> str:

@@ -666,6 +666,34 @@ int fg_resampler_destroy(fg_resampler r);
 int fg_resample(fg_resampler r, const float* src, int batch, int channels, float* dst, int fill_max_steps,
                 void* stream);
 
+/* ---- RGB frames of the envs of a batch (fp32 library only; csrc/fg_frames.hip) ----------------------------------
+ * The last step of the reference's _get_render_data / _format_render_data (envs/fluid_env.py:710-747): one plane of a field, oriented,
+ * normalised, clipped, looked up in a 256-entry colour table, solid pixels blacked out, as uint8 RGB.  One launch per 64 listed envs, an
+ * env that is not listed costs nothing, nothing returns to the host, no atomics.
+ *   field  device fp32 [B][C][nz][ny][nx] (nz == 1 for a 2-D view)
+ *   spec   channel >= 0: that channel; -1: the Euclidean norm over all C channels, sqrtf(((u0 u0) + (u1 u1)) + (u2 u2))
+ *          axis -1: the 2-D field (rows y, cols x; needs nz == 1, index 0); 0: z = index, rows y, cols x; 1: y = index, rows z, cols x;
+ *          2: x = index, rows z, cols y.  Then transpose (rows <-> cols), then flip_rows, flip_cols of the transposed plane: H, W.
+ *   table  device uint8 [256][3];  mask: device uint8 [H][W] in output orientation or NULL, non-zero = solid pixel
+ *   range  device fp32 [n][2] = (lo, span) of listed env i;  envs: HOST int32 [n], each in [0, B), any order, repeats allowed
+ *   out    device uint8 [n][H][W][3]
+ * Per pixel, in fp32 with every operation rounded on its own: x = (v - lo) / span (IEEE division); x < 0 -> 0, x > 1 -> 1; NaN -> (0, 0, 0);
+ * else table[min((int)(x * 256), 255)]; a masked pixel is (0, 0, 0): byte for byte what matplotlib's
+ * cmap(clip((d - vmin) / (vmax - vmin), 0, 1), bytes=True)[..., :3] gives for a float32 array.
+ * Before any launch (and without a GPU): FG_ERR_INVALID_ARG for a null field / spec / table / range / envs / out, n < 1, an extent < 1,
+ * an env outside [0, B), channel outside [-1, C), an unknown axis, axis -1 with nz != 1, index outside the axis. */
+typedef struct fg_frame_spec {
+    int32_t channel;
+    int32_t axis;
+    int32_t index;
+    int32_t transpose;
+    int32_t flip_rows;
+    int32_t flip_cols;
+} fg_frame_spec;
+int fg_frame_colorize(const float* field, int32_t B, int32_t C, int32_t nz, int32_t ny, int32_t nx, const fg_frame_spec* spec,
+                      const uint8_t* table, const uint8_t* mask, const float* range, const int32_t* envs, int32_t n, uint8_t* out,
+                      void* stream);
+
 /* ---- env glue either side of the n sim steps of an env step (fp32 library only) ------------------------------
  * fg_envglue_jet_schedule: the action smoothing of the reference's jet envs (cylinder_env_base.py:748-753, a_k = a_{k-1} +
  * alpha (target - a_{k-1}) before every sim step) for the n sim steps of one env step at once: control[k][b] = target[b] +
