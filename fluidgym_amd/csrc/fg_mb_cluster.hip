@@ -1126,20 +1126,18 @@ bool mb_cluster_ok(const fg_mb_state* s, int pm_mode, const mb_real* diag, const
     return s->cl_cus >= CL_G;
 }
 
-// the whole CG solve of every env in one launch of clusters; same arguments and results as mb_cg.  *fell_back: a workgroup gave up
+// the whole CG solve of every env in one launch of clusters; same results as mb_cg.  *fell_back: a workgroup gave up
 // on a granule (FG_OK is returned and nothing was solved: the caller runs the one-workgroup kernels)
-int mb_cg_cluster(fg_mb_state* s, const mb_real* dt, const mb_real* rhs, mb_real* x, mb_real tol, int max_iterations, int use_x0, int pm_mode,
-                  mb_real stall_accept, int* max_it, hipStream_t st, bool* fell_back) {
+int mb_cg_cluster(fg_mb_state* s, const mb_real* dt, const mb_real* rhs, mb_real* x, const MbCgRule& R, int* max_it, hipStream_t st, bool* fell_back) {
     *fell_back = false;
 #if FG_MB_F64
-    (void)dt; (void)rhs; (void)x; (void)tol; (void)max_iterations; (void)use_x0; (void)pm_mode; (void)stall_accept; (void)max_it; (void)st;
+    (void)dt; (void)rhs; (void)x; (void)R; (void)max_it; (void)st;
     fg_set_error("the cluster CG is not part of the fp64 build");
     return FG_ERR_UNSUPPORTED;
 #else
-    const int nsys = s->B, n = s->N;
-    MbSolve q = mb_solve_ptrs(s, s->Pdiag, s->Poff, rhs, x, 1, tol);
+    const int nsys = s->B, n = s->N, pm_mode = R.pm_mode;
+    MbSolve q = mb_solve_ptrs(s, s->Pdiag, s->Poff, rhs, x, 1, R.tol);
     q.best_x = s->w[4]; q.best_it = s->best_it;
-    constexpr int CG_CHUNK = 20, CG_RESTART = 100;
     ClParams o;
     memset(&o, 0, sizeof(o));
     o.slot_cell = s->cl_slot_cell; o.nbr = s->cl_nbr; o.d4g = s->cl_d4g; o.tinfo = s->cl_tinfo; o.out_slot = s->cl_out_slot;
@@ -1154,10 +1152,10 @@ int mb_cg_cluster(fg_mb_state* s, const mb_real* dt, const mb_real* rhs, mb_real
     o.dt = dt; o.B = nsys; o.N = n; o.allow_near = s->cl_near; o.dbg_out = s->oc_dbg;
     o.n_clusters = std::max(1, std::min(nsys, s->cl_cus / CL_G));   // one workgroup per CU: every workgroup of the grid is resident
     if (s->cl_max_clusters > 0) o.n_clusters = std::min(o.n_clusters, s->cl_max_clusters);
-    o.use_x0 = use_x0; o.pm = pm_mode; o.restart_every = CG_RESTART; o.check_every = CG_CHUNK;
-    o.max_iterations = ((max_iterations + CG_CHUNK - 1) / CG_CHUNK) * CG_CHUNK;
-    o.stall_limit = s->cg_stall_limit; o.accept_window = 20;
-    o.accept_factor = stall_accept > 1.f ? stall_accept : 0.f; o.tol = tol;
+    o.use_x0 = R.use_x0; o.pm = pm_mode; o.restart_every = MB_CG_RESTART; o.check_every = MB_CG_CHUNK;
+    o.max_iterations = R.max_iterations;
+    o.stall_limit = R.stall_limit; o.accept_window = R.accept_window;
+    o.accept_factor = R.accept_factor; o.tol = R.tol;
     o.info_host = s->info_pinned; o.its_host = s->flags_pinned;
     o.poll = fg_poll_next(&s->poll);
     const bool ev = s->prof_on != 0;
@@ -1177,36 +1175,28 @@ int mb_cg_cluster(fg_mb_state* s, const mb_real* dt, const mb_real* rhs, mb_real
     else CL_LAUNCH_PM(8, 1024, 0);
 #undef CL_LAUNCH_PM
 #undef CL_LAUNCH
-    if (int rc = fg_poll_wait(&s->poll, ev ? FgPollOut{nullptr, 0} : o.poll, 0, nsys, st)) return rc;
-    for (int i = 0; i < nsys; ++i)
-        if (s->flags_pinned[i] == -77) { *fell_back = true; ++s->cl_fallbacks; return FG_OK; }
+    if (int rc = mb_whole_solve_wait(s, o.poll, nsys, st)) return rc;
+    if ((*fell_back = mb_cluster_fell_back(s, nsys))) return FG_OK;
     ++s->cl_solves;
     if (ev) {
-        fg_f32 ms = 0.f;
-        FG_HIP_CHECK(hipEventElapsedTime(&ms, s->prof_ev_oc[0], s->prof_ev_oc[1]));
-        long long its = 0;
-        for (int i = 0; i < nsys; ++i) its += s->flags_pinned[i] > 0 ? s->flags_pinned[i] : 0;
+        const long long its = mb_prof_whole_solve(s, nsys);
         // bytes the kernel streams: per solve and cell the matrix row (20 B), neighbour addresses (8), rhs, x, kept iterate (about
         // 12); per iteration the rows of the coarse operator (n8 x n8 floats per env) and the granules (16 B per halo cell)
-        s->prof_ms[2] += ms;
         s->prof_bytes[2] += (double)nsys * n * 40.0 + (double)its * ((double)o.n8 * o.ld8 * 4.0 + 16.0 * CL_G * o.n_halo_max);
-        s->prof_n[2] += 1; s->prof_launches[2] += 1;
-        s->prof_its += its;
     }
     return mb_finish(s, nsys, nullptr, max_it);
 #endif
 }
 
 // mb_jacobi's sweeps by the clusters (k_mbj_cluster): the 2-D velocity systems of the meshes the cluster CG takes.  *fell_back: a
-// workgroup gave up on a granule (nothing was solved: the caller runs the launch-per-sweep path); otherwise *done says whether every
-// system settled -- when not, the pinned mirrors hold the flags and the last two measured residuals of every system, as mb_jacobi's
-// check kernel leaves them.
+// workgroup gave up on a granule (nothing was solved: the caller runs the launch-per-sweep path); otherwise the pinned mirrors hold
+// the flags and the last two measured residuals of every system, as mb_jacobi's check kernel leaves them.
 bool mb_jacobi_cluster_ok(const fg_mb_state* s, int nc) {
     return s->cl_on && s->cl_jacobi && (s->cl_mode == 2 || s->N > 8 * 1024) && nc == 2 && s->d == 2 && s->cl_cus >= CL_G && s->cl_jbox != nullptr;
 }
 int mb_jacobi_cluster(fg_mb_state* s, const mb_real* dt, const mb_real* diag, const mb_real* off, const mb_real* rhs, mb_real* x, mb_real tol,
-                      int use_x0, hipStream_t st, bool* fell_back, bool* done) {
-    *fell_back = false; *done = false;
+                      int use_x0, hipStream_t st, bool* fell_back) {
+    *fell_back = false;
 #if FG_MB_F64
     (void)dt; (void)diag; (void)off; (void)rhs; (void)x; (void)tol; (void)use_x0; (void)st;
     fg_set_error("the cluster sweeps are not part of the fp64 build");
@@ -1231,13 +1221,8 @@ int mb_jacobi_cluster(fg_mb_state* s, const mb_real* dt, const mb_real* diag, co
     else if (s->cl_nt == 768) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mbj_cluster<768>), grid, dim3(768), 0, st, q, o);
     else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mbj_cluster<1024>), grid, dim3(1024), 0, st, q, o);
     if (int rc = fg_poll_wait(&s->poll, o.poll, 0, nsys, st)) return rc;
-    bool all = true;
-    for (int i = 0; i < nsys; ++i) {
-        if (s->flags_pinned[i] == -77) { *fell_back = true; ++s->cl_fallbacks; return FG_OK; }
-        all = all && s->flags_pinned[i] != 0;
-    }
+    if ((*fell_back = mb_cluster_fell_back(s, nsys))) return FG_OK;
     ++s->cl_jacobi_solves;
-    *done = all;
     return FG_OK;
 #endif
 }

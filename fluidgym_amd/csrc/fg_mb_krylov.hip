@@ -1142,8 +1142,7 @@ MbSolve mb_solve_ptrs(fg_mb_state* s, const mb_real* diag, const mb_real* off, c
 }
 
 
-
-// z = M in for every system still iterating (kernel form of the multilevel preconditioner; pressure systems, nc == 1)
+// the tables of the kernel form of the multilevel preconditioner (z = M in for every system still iterating; pressure systems, nc == 1)
 MlDev mb_ml_dev(const fg_mb_state* s) {
     MlDev M;
     M.a4 = s->ml_a4; M.parent4 = s->ml_parent4; M.rect4 = s->ml_rect4; M.child8 = s->ml_child8; M.rd4 = s->ml_d4g; M.aci8 = s->ml_aci8;
@@ -1152,8 +1151,6 @@ MlDev mb_ml_dev(const fg_mb_state* s) {
     M.cnt4 = s->ml_cnt4; M.g8 = s->ml_g8;
     return M;
 }
-// fused = 0: z = M in.  1 / 2: `in` is q.p / q.r and its update (k_mbb_p / k_mbb_s) happens inside the restriction
-// (k_ml_restrict_p / _s), iteration index `it`.
 // the per-env scale of the multilevel preconditioner (sum_i P_ii / geom_diag_sum) for the matrix diagonal `diag`
 void mb_ml_scale(fg_mb_state* s, const mb_real* diag, hipStream_t st) {
     hipLaunchKernelGGL(k_ml_scale, dim3(s->B), dim3(1024), 0, st, diag, s->N, s->ml_geom_diag_sum, s->ml_scale);
@@ -1186,6 +1183,8 @@ static void mb_ml_restrict_coarse(fg_mb_state* s, const MbSolve& q, const MlDev&
 #undef ML_COARSE
     }
 }
+// fused = 0: z = M in.  1 / 2: `in` is q.p / q.r and its update (k_mbb_p / k_mbb_s) happens inside the restriction
+// (k_ml_restrict_p / _s), iteration index `it`.
 void mb_ml_apply(fg_mb_state* s, const MbSolve& q, const mb_real* in, mb_real* out, hipStream_t st, int fused, int it) {
     const MlDev M = mb_ml_dev(s);
     const int nsys = q.sys_map ? q.n_map : s->B * q.nc, n = s->N;
@@ -1248,190 +1247,192 @@ void mb_ilu_apply(fg_mb_state* s, const MbSolve& q, const mb_real* in, mb_real* 
                                       (const mb_real*)s->ilu_w, (const mb_real*)s->ilu_ud, in, out););
 }
 
-int mb_bicgstab(fg_mb_state* s, const mb_real* dt, const mb_real* diag, const mb_real* off, const mb_real* rhs, mb_real* x, int nc,
-                mb_real tol, int max_iterations, int use_x0, int* max_it, hipStream_t st, int project, int refine, int multilevel,
-                int pred_slot) {
-    const int nsys = s->B * nc, n = s->N;
-    MbSolve q = mb_solve_ptrs(s, diag, off, rhs, x, nc, tol);
-    q.project = project ? 1 : 0;
-    // multilevel right preconditioning of the pressure solve: the recurrence runs on P M, the iterate advances along M p, M s
-    // multilevel == 2: right preconditioning by ILU(0) of the matrix itself (the reference's preconditioned rung; mb_ilu_*)
-    const bool ilu = multilevel == 2 && s->ilu_state > 0;
-    const bool ml = ilu || (multilevel == 1 && nc == 1 && s->ml_on && s->ml_a4 != nullptr && s->ml_mp != nullptr);
-    if (ilu) {
-        q.mp = s->ilu_mp; q.ms = s->ilu_ms;
-        mb_ilu_factor(s, dt, diag, off, st);
-    } else if (ml) {
-        q.mp = s->ml_mp; q.ms = s->ml_ms;
-        hipLaunchKernelGGL(k_ml_scale, dim3(s->B), dim3(1024), 0, st, diag, n, s->ml_geom_diag_sum, s->ml_scale);
-    }
-    const dim3 sg((nsys + 63) / 64), sb(64), grid((n + FG_BLOCK - 1) / FG_BLOCK, nsys), blk(FG_BLOCK);
-    // a refined solve that has not converged after 1500 iterations is not going to: hand over to the caller's CG fallback
-    // instead of spending the reference's 5000 (one hard env would stall the whole batch)
-    if (refine && max_iterations > 1500) max_iterations = 1500;
+// FG_MB_TRACE: the line of one poll (verify_round > 0: of a verification round of mb_bicgstab)
+static void mb_trace_poll(const fg_mb_state* s, int nsys, const char* who, int it, int verify_round) {
+    mb_real lo = 1e30f, hi = 0.f; int active = 0;
+    for (int i = 0; i < nsys; ++i) { const mb_real c = s->info_pinned[i].final_residual; lo = c < lo ? c : lo; hi = c > hi ? c : hi; active += s->flags_pinned[i] == 0; }
+    if (verify_round) fprintf(stderr, "[%s] it %4d verification round %d: %d system(s) iterate on\n", who, it, verify_round, active);
+    else fprintf(stderr, "[%s] it %4d residual min %.3e max %.3e active %d\n", who, it, lo, hi, active);
+}
+
+// BiCGStab driver.  One solve = mb_bicg_form (what runs), the recurrence laid down (mb_bicg_reopen), then per iteration
+// mb_bicg_iterate and, where a poll is due, mb_bicg_poll (+ mb_bicg_verify for the solves that are held to the true residual), and
+// mb_bicg_finish.  The order of launches and the place of every poll are part of the arithmetic: a poll that moves changes the
+// iteration a solve ends in (tests/test_gpu_mb_driver_forms.py).
+struct MbBicgRun {
+    fg_mb_state* s; hipStream_t st;
+    MbSolve q;                  // the solve bundle; q.it_base = iteration index of the last re-opening
+    int nsys, n, nc;
+    dim3 sg, grid, grid4;       // one thread per system; one / four cells per thread over all systems
+    MbBicgOpt opt;
+    bool ilu, ml, ml_fused;     // right preconditioner: ILU(0) of the matrix / multilevel (ml is set for both); p, s formed in the restriction
+    bool fused_st, fused_pv;    // k_mbb_st / k_mbb_pv instead of the separate kernels
+    bool verify;                // convergence is confirmed on the recomputed residual (k_mbb_reopen)
+    int vec_mask, restart_every;   // vec_mask: which kernel roles run four cells per thread (1 p, 2 v, 4 s, 8 t, 16 x)
+    int n_map = 0, verify_rounds = 0;   // n_map: systems of the compacted per-iteration launches (0: all systems, identity)
+};
+enum MbBicgOpen { MB_OPEN_START, MB_OPEN_RESTART, MB_OPEN_VERIFY };
+
+// the one place that decides which form of the recurrence runs
+static MbBicgRun mb_bicg_form(fg_mb_state* s, const mb_real* diag, const mb_real* off, const mb_real* rhs, mb_real* x, int nc, mb_real tol,
+                              const MbBicgOpt& opt, hipStream_t st) {
+    MbBicgRun R;
+    R.s = s; R.st = st; R.opt = opt; R.nc = nc; R.nsys = s->B * nc; R.n = s->N;
+    R.q = mb_solve_ptrs(s, diag, off, rhs, x, nc, tol);
+    R.q.project = opt.project ? 1 : 0;
+    // multilevel right preconditioning of the pressure solve: the recurrence runs on P M, the iterate advances along M p, M s;
+    // MB_PRE_ILU: right preconditioning by ILU(0) of the matrix itself (the reference's preconditioned rung; mb_ilu_*)
+    R.ilu = opt.precond == MB_PRE_ILU && s->ilu_state > 0;
+    R.ml = R.ilu || (opt.precond == MB_PRE_MULTILEVEL && nc == 1 && s->ml_on && s->ml_a4 != nullptr && s->ml_mp != nullptr);
+    if (R.ilu) { R.q.mp = s->ilu_mp; R.q.ms = s->ilu_ms; }
+    else if (R.ml) { R.q.mp = s->ml_mp; R.q.ms = s->ml_ms; }
+    R.sg = dim3((R.nsys + 63) / 64);
+    R.grid = dim3((R.n + FG_BLOCK - 1) / FG_BLOCK, R.nsys);
+    R.grid4 = dim3((R.n / 4 + FG_BLOCK - 1) / FG_BLOCK, R.nsys);
     // Four-cells-per-thread kernels (k_mbb_*<DIMS, 4>) whenever the cell count allows; FG_MB_BICG_VEC4 (read at create) is the test /
     // harness switch between the two kernel forms, not a workaround: the failures it once bisected were exact breakdowns of the
     // recurrence (mbb_p_head), deterministic per kernel form because the two forms sum in different orders.
-    const int vec_mask = (n % 4 != 0) ? 0 : (s->dbg_vec_mask & 31);
-    const dim3 grid4((n / 4 + FG_BLOCK - 1) / FG_BLOCK, nsys);
-    auto keep_best = [&](int first) {
-        hipLaunchKernelGGL(k_mbr_best_decide, sg, sb, 0, st, q, s->best_res, s->best_keep, n, nsys, first);
-        hipLaunchKernelGGL(k_mbr_best_copy, grid, blk, 0, st, n, (const int32_t*)s->best_keep, (const double*)s->x64, s->x64_best);
-    };
-    // a preconditioned or refined solve verifies convergence on the true residual (k_mbb_reopen); the plain fp32 recurrence stays
-    // the reference's (bicgstab_solver_kernel.cu declares convergence on the recurrence residual)
+    R.vec_mask = (R.n % 4 != 0) ? 0 : (s->dbg_vec_mask & 31);
     // s and t in one launch unless the recurrence is right-preconditioned (t = A M s needs all of s first); FG_MB_BICG_FUSE=0
     // (read at create) keeps the two kernels
-    const bool fused_st = !ml && s->dbg_fuse_st >= 1, fused_pv = !ml && s->dbg_fuse_st >= 2;
+    R.fused_st = !R.ml && s->dbg_fuse_st >= 1;
+    R.fused_pv = !R.ml && s->dbg_fuse_st >= 2;
     // multilevel: p and s are formed inside the restriction that follows them -- two launches fewer per iteration, which pays
     // while the launches are latency-sized (Airfoil2D x 16: 32.3-33.9 -> 34.7-34.8 env-steps/s; rocprofv3: p + restriction 10.1 -> 7.3 us, s + restriction
     // 10.4 -> 7.1 us with four threads per aggregate) and not once they carry bytes (x 64: 16.0 -> 17.4 us, 15.2 -> 14.3 us).  So: up to 32 systems.
     // FG_MB_ML_FUSE=0 never, 2 always.
-    const bool ml_fused = ml && !ilu && !FG_MB_F64 && (s->dbg_ml_fuse == 2 || (s->dbg_ml_fuse == 1 && nsys <= 32));   // (k_ml_restrict_p / _s: fp32 words)
-    if (fused_st) q.sbuf = s->w[5];
-    const bool verify = ml || refine;
-    int verify_rounds = 0;
-    if (verify) FG_HIP_CHECK(hipMemsetAsync(s->verified, 0, sizeof(int32_t) * nsys, st));
-    hipLaunchKernelGGL(k_mbs_begin, sg, sb, 0, st, dt, q, nsys);
-    if (refine) {
-        hipLaunchKernelGGL(k_mbr_fold, grid, blk, 0, st, n, q, s->x64, use_x0 ? 1 : 0);
-        MB_DISPATCH(s, hipLaunchKernelGGL(k_mbr_residual<DIMS>, grid, blk, 0, st, s->dev, q, (const double*)s->x64, project ? A_ST : -1, project ? 1 : 0););
+    R.ml_fused = R.ml && !R.ilu && !FG_MB_F64 && (s->dbg_ml_fuse == 2 || (s->dbg_ml_fuse == 1 && R.nsys <= 32));   // (k_ml_restrict_p / _s: fp32 words)
+    if (R.fused_st) R.q.sbuf = s->w[5];
+    // a preconditioned or refined solve verifies convergence on the true residual (k_mbb_reopen); the plain fp32 recurrence stays
+    // the reference's (bicgstab_solver_kernel.cu declares convergence on the recurrence residual)
+    R.verify = R.ml || opt.refine;
+    R.restart_every = opt.refine ? 100 : 200;
+    return R;
+}
+
+// Lay the recurrence down (again) from the iterate: the residual of x (refined: of the fp64 iterate, folded first), the projection's
+// sums, the kept best refinement point.  At the start from x0 or zero; at a restart and in a verification round from the current
+// iterate, with iteration index `it_base` as the new origin and p = r back in buffer 0 of the p / v pairs.
+static void mb_bicg_reopen(MbBicgRun& R, MbBicgOpen why, int it_base, int use_x0) {
+    fg_mb_state* s = R.s; hipStream_t st = R.st; MbSolve& q = R.q;
+    const dim3 sb(64), blk(FG_BLOCK);
+    const int project = R.opt.project, n = R.n;
+    if (why == MB_OPEN_VERIFY) hipLaunchKernelGGL(k_mbb_reopen, R.sg, sb, 0, st, q, s->verified, R.nsys);
+    if (why != MB_OPEN_START) { q.it_base = it_base; q.p = s->w[2]; q.v = s->w[3]; }
+    if (why == MB_OPEN_RESTART) hipLaunchKernelGGL(k_mbb_restart, R.sg, sb, 0, st, q, R.nsys);
+    if (R.opt.refine) {
+        hipLaunchKernelGGL(k_mbr_fold, R.grid, blk, 0, st, n, q, s->x64, why == MB_OPEN_START ? (use_x0 ? 1 : 0) : 2);
+        MB_DISPATCH(s, hipLaunchKernelGGL(k_mbr_residual<DIMS>, R.grid, blk, 0, st, s->dev, q, (const double*)s->x64, project ? A_ST : -1, project ? 1 : 0););
     } else {
-        MB_DISPATCH(s, hipLaunchKernelGGL(k_mbs_init<DIMS>, grid, blk, 0, st, s->dev, q, use_x0, project ? A_ST : -1, project ? 1 : 0););
+        MB_DISPATCH(s, hipLaunchKernelGGL(k_mbs_init<DIMS>, R.grid, blk, 0, st, s->dev, q, why == MB_OPEN_START ? use_x0 : 1, project ? A_ST : -1, project ? 1 : 0););
     }
-    if (project) hipLaunchKernelGGL(k_mbb_project_init, grid, blk, 0, st, n, q);
-    if (refine) keep_best(1);
-    bool done = false;
-    // first convergence poll where the previous solve of this kind finished (kernels of converged systems exit at once, so running
-    // a few launches past convergence costs ~2 us each, while every poll is a stream synchronisation: 10-20 us of idle GPU), then
-    // every 2 (every 10 beyond 20) iterations
-    int& pred = s->pred_bicg[pred_slot & 31];
-    int next_poll = (pred > 2 && s->dbg_pred) ? pred : 2;
-    const int BICG_RESTART = refine ? 100 : 200;
-    int n_map = 0;      // systems of the compacted per-iteration launches (0: all systems, identity)
-    auto update_map = [&]() -> int {     // after a poll: the systems that still iterate (flags_pinned == 0), when they are few
-        if (!s->dbg_compact || ilu) return FG_OK;
-        int act = 0;
-        for (int i = 0; i < nsys; ++i) act += s->flags_pinned[i] == 0;
-        if (act == 0 || act > 16 || 4 * act > nsys) { n_map = 0; return FG_OK; }
-        bool same = (act == n_map);
-        int k = 0;
-        for (int i = 0; i < nsys; ++i)
-            if (s->flags_pinned[i] == 0) { same = same && s->sys_map_pinned[k] == i; ++k; }
-        if (same) return FG_OK;
-        k = 0;
-        for (int i = 0; i < nsys; ++i) if (s->flags_pinned[i] == 0) s->sys_map_pinned[k++] = i;
-        // (the previous upload has executed: the poll that just returned was enqueued behind it)
-        FG_HIP_CHECK(hipMemcpyAsync(s->sys_map_dev, s->sys_map_pinned, sizeof(int32_t) * act, hipMemcpyHostToDevice, st));
-        n_map = act;
-        return FG_OK;
-    };
-    for (int it = 0; it < max_iterations && !done; ++it) {
-        if (it > 0 && it % BICG_RESTART == 0) {
-            q.it_base = it;
-            q.p = s->w[2]; q.v = s->w[3];   // the re-initialisation lays p = r down in buffer 0 of the pair (iteration index 0)
-            hipLaunchKernelGGL(k_mbb_restart, sg, sb, 0, st, q, nsys);
-            if (refine) {
-                hipLaunchKernelGGL(k_mbr_fold, grid, blk, 0, st, n, q, s->x64, 2);
-                MB_DISPATCH(s, hipLaunchKernelGGL(k_mbr_residual<DIMS>, grid, blk, 0, st, s->dev, q, (const double*)s->x64, project ? A_ST : -1, project ? 1 : 0););
-            } else {
-                MB_DISPATCH(s, hipLaunchKernelGGL(k_mbs_init<DIMS>, grid, blk, 0, st, s->dev, q, 1, project ? A_ST : -1, project ? 1 : 0););
-            }
-            if (project) hipLaunchKernelGGL(k_mbb_project_init, grid, blk, 0, st, n, q);
-            if (refine) keep_best(0);
+    if (project) hipLaunchKernelGGL(k_mbb_project_init, R.grid, blk, 0, st, n, q);
+    if (why == MB_OPEN_VERIFY) hipLaunchKernelGGL(k_mbb_verify, R.sg, sb, 0, st, q, s->verified, n, R.nsys, (int)(R.verify_rounds == 3));
+    if (R.opt.refine) {
+        hipLaunchKernelGGL(k_mbr_best_decide, R.sg, sb, 0, st, q, s->best_res, s->best_keep, n, R.nsys, why == MB_OPEN_START ? 1 : 0);
+        hipLaunchKernelGGL(k_mbr_best_copy, R.grid, blk, 0, st, n, (const int32_t*)s->best_keep, (const double*)s->x64, s->x64_best);
+    }
+}
+
+// the launches of iteration `it`
+static void mb_bicg_iterate(MbBicgRun& R, int it) {
+    fg_mb_state* s = R.s; hipStream_t st = R.st; MbSolve& q = R.q;
+    const dim3 blk(FG_BLOCK);
+    const int li = it - q.it_base;
+    if (R.fused_pv) {   // p and v of iteration li live in buffer li & 1 of their pair
+        q.p = (li & 1) ? s->w[6] : s->w[2]; q.p_prev = (li & 1) ? s->w[2] : s->w[6];
+        q.v = (li & 1) ? s->w[7] : s->w[3]; q.v_prev = (li & 1) ? s->w[3] : s->w[7];
+    }
+    // Compacted launches: while only a few systems of the batch still iterate (envs differ: the slowest of 64 pressure systems
+    // needs 2-3x the mean), the kernels of an iteration are launched over those systems only -- grid.y = n_map, system =
+    // sys_map[blockIdx.y] -- instead of over all of them with most workgroups leaving at once (Airfoil2D x 64 with random actions:
+    // 47 % of all launched iterations ran for 1-3 systems, ~5.5 us per launch against ~2.5)
+    MbSolve qi = q;
+    dim3 gi = R.grid, gi4 = R.grid4;
+    if (R.n_map > 0) { qi.sys_map = s->sys_map_dev; qi.n_map = R.n_map; gi.y = gi4.y = (unsigned)R.n_map; }
+    // one kernel role: in its four-cell form over gi4 when vec_mask has all of `bits` (1 p, 2 v, 4 s, 8 t, 16 x; a fused kernel
+    // needs both of its halves), else in its one-cell form over gi
+#define MBB_LAUNCH(K, bits)                                                                                    \
+    do {                                                                                                       \
+        if ((R.vec_mask & (bits)) == (bits)) hipLaunchKernelGGL((K<DIMS, 4>), gi4, blk, 0, st, s->dev, qi, li);  \
+        else hipLaunchKernelGGL((K<DIMS, 1>), gi, blk, 0, st, s->dev, qi, li);                                 \
+    } while (0)
+    MB_DISPATCH(s, {
+        if (R.fused_pv) MBB_LAUNCH(k_mbb_pv, 3);
+        else {
+            if (!R.ml_fused) MBB_LAUNCH(k_mbb_p, 1);   // (ml_fused: p is formed inside the restriction, mb_ml_apply below)
+            if (R.ilu) mb_ilu_apply(s, qi, qi.p, s->ilu_mp, st);
+            else if (R.ml) mb_ml_apply(s, qi, qi.p, s->ml_mp, st, R.ml_fused ? 1 : 0, li);
+            MBB_LAUNCH(k_mbb_v, 2);
         }
-        const int li = it - q.it_base;
-        if (fused_pv) {   // p and v of iteration li live in buffer li & 1 of their pair
-            q.p = (li & 1) ? s->w[6] : s->w[2]; q.p_prev = (li & 1) ? s->w[2] : s->w[6];
-            q.v = (li & 1) ? s->w[7] : s->w[3]; q.v_prev = (li & 1) ? s->w[3] : s->w[7];
+        if (R.fused_st) MBB_LAUNCH(k_mbb_st, 12);
+        else {
+            if (!R.ml_fused) MBB_LAUNCH(k_mbb_s, 4);   // (ml_fused: s is formed inside the restriction)
+            if (R.ilu) mb_ilu_apply(s, qi, qi.r, s->ilu_ms, st);
+            else if (R.ml) mb_ml_apply(s, qi, qi.r, s->ml_ms, st, R.ml_fused ? 2 : 0, li);
+            MBB_LAUNCH(k_mbb_t, 8);
         }
-        // Compacted launches: while only a few systems of the batch still iterate (envs differ: the slowest of 64 pressure systems
-        // needs 2-3x the mean), the kernels of an iteration are launched over those systems only -- grid.y = n_map, system =
-        // sys_map[blockIdx.y] -- instead of over all of them with most workgroups leaving at once (Airfoil2D x 64 with random actions:
-        // 47 % of all launched iterations ran for 1-3 systems, ~5.5 us per launch against ~2.5)
-        MbSolve qi = q;
-        dim3 gi = grid, gi4 = grid4;
-        if (n_map > 0) { qi.sys_map = s->sys_map_dev; qi.n_map = n_map; gi.y = gi4.y = (unsigned)n_map; }
-        // one kernel role: in its four-cell form over gi4 when vec_mask has all of `bits` (1 p, 2 v, 4 s, 8 t, 16 x; a fused kernel
-        // needs both of its halves), else in its one-cell form over gi
-#define MBB_LAUNCH(K, bits)                                                                                        \
-        do {                                                                                                       \
-            if ((vec_mask & (bits)) == (bits)) hipLaunchKernelGGL((K<DIMS, 4>), gi4, blk, 0, st, s->dev, qi, li);  \
-            else hipLaunchKernelGGL((K<DIMS, 1>), gi, blk, 0, st, s->dev, qi, li);                                 \
-        } while (0)
-        MB_DISPATCH(s, {
-            if (fused_pv) MBB_LAUNCH(k_mbb_pv, 3);
-            else {
-                if (!ml_fused) MBB_LAUNCH(k_mbb_p, 1);   // (ml_fused: p is formed inside the restriction, mb_ml_apply below)
-                if (ilu) mb_ilu_apply(s, qi, qi.p, s->ilu_mp, st);
-                else if (ml) mb_ml_apply(s, qi, qi.p, s->ml_mp, st, ml_fused ? 1 : 0, li);
-                MBB_LAUNCH(k_mbb_v, 2);
-            }
-            if (fused_st) MBB_LAUNCH(k_mbb_st, 12);
-            else {
-                if (!ml_fused) MBB_LAUNCH(k_mbb_s, 4);   // (ml_fused: s is formed inside the restriction)
-                if (ilu) mb_ilu_apply(s, qi, qi.r, s->ilu_ms, st);
-                else if (ml) mb_ml_apply(s, qi, qi.r, s->ml_ms, st, ml_fused ? 2 : 0, li);
-                MBB_LAUNCH(k_mbb_t, 8);
-            }
-            MBB_LAUNCH(k_mbb_x, 16);
-        });
+        MBB_LAUNCH(k_mbb_x, 16);
+    });
 #undef MBB_LAUNCH
-        if (it + 1 >= next_poll || it + 1 == max_iterations) {
-            next_poll = it + 1 + (it < 20 ? 2 : 10);   // long (pressure) solves: fewer host round trips
-            FgPollOut po = fg_poll_next(&s->poll);
-            hipLaunchKernelGGL(k_mbs_check, sg, sb, 0, st, q, s->info_pinned, s->flags_pinned, A_RR, it, n, nsys, (int)(it + 1 == max_iterations), -1, po);
-            if (int rc = mb_poll(s, nsys, st, done, po, true)) return rc;
-            if (int rc = update_map()) return rc;
-            if (nc == 1 && s->dbg_trace) {
-                mb_real lo = 1e30f, hi = 0.f; int active = 0;
-                for (int i = 0; i < nsys; ++i) { const mb_real c = s->info_pinned[i].final_residual; lo = c < lo ? c : lo; hi = c > hi ? c : hi; active += s->flags_pinned[i] == 0; }
-                fprintf(stderr, "[mb_bicg] it %4d residual min %.3e max %.3e active %d\n", it + 1, lo, hi, active);
-            }
-            if (done && verify && verify_rounds < 3 && it + 1 < max_iterations) {   // see k_mbb_reopen
-                bool any = false;
-                for (int i = 0; i < nsys; ++i) any = any || (s->flags_pinned[i] == 1 && s->info_pinned[i].converged && s->info_pinned[i].is_finite);
-                if (any) {
-                    ++verify_rounds;
-                    hipLaunchKernelGGL(k_mbb_reopen, sg, sb, 0, st, q, s->verified, nsys);
-                    q.it_base = it + 1;
-                    q.p = s->w[2]; q.v = s->w[3];
-                    if (refine) {
-                        hipLaunchKernelGGL(k_mbr_fold, grid, blk, 0, st, n, q, s->x64, 2);
-                        MB_DISPATCH(s, hipLaunchKernelGGL(k_mbr_residual<DIMS>, grid, blk, 0, st, s->dev, q, (const double*)s->x64, project ? A_ST : -1, project ? 1 : 0););
-                    } else {
-                        MB_DISPATCH(s, hipLaunchKernelGGL(k_mbs_init<DIMS>, grid, blk, 0, st, s->dev, q, 1, project ? A_ST : -1, project ? 1 : 0););
-                    }
-                    if (project) hipLaunchKernelGGL(k_mbb_project_init, grid, blk, 0, st, n, q);
-                    hipLaunchKernelGGL(k_mbb_verify, sg, sb, 0, st, q, s->verified, n, nsys, (int)(verify_rounds == 3));
-                    if (refine) keep_best(0);
-                    po = fg_poll_next(&s->poll);
-                    hipLaunchKernelGGL(k_mbs_check, sg, sb, 0, st, q, s->info_pinned, s->flags_pinned, A_RR, it, n, nsys, 0, -1, po);
-                    if (int rc = mb_poll(s, nsys, st, done, po, true)) return rc;
-                    if (int rc = update_map()) return rc;
-                    next_poll = it + 1 + 2;
-                    if (nc == 1 && s->dbg_trace) {
-                        int open = 0;
-                        for (int i = 0; i < nsys; ++i) open += s->flags_pinned[i] == 0;
-                        fprintf(stderr, "[mb_bicg] it %4d verification round %d: %d system(s) iterate on\n", it + 1, verify_rounds, open);
-                    }
-                }
-            }
-        }
-    }
-    if (refine) {
-        hipLaunchKernelGGL(k_mbr_best_restore, grid, blk, 0, st, n, q, s->x64, (const double*)s->x64_best, (const mb_real*)s->best_res);
-        hipLaunchKernelGGL(k_mbr_fold, grid, blk, 0, st, n, q, s->x64, 3);
+}
+
+// one poll round behind iteration `it`: verdicts (final: the cap is reached, every system ends here), the host's wait, the map of
+// the compacted launches, the trace line (verify_round > 0: the round's own line)
+static int mb_bicg_poll(MbBicgRun& R, int it, int final, int verify_round, bool& done) {
+    fg_mb_state* s = R.s;
+    const int nsys = R.nsys;
+    const FgPollOut po = fg_poll_next(&s->poll);
+    hipLaunchKernelGGL(k_mbs_check, R.sg, dim3(64), 0, R.st, R.q, s->info_pinned, s->flags_pinned, A_RR, it, R.n, nsys, final, -1, po);
+    if (int rc = mb_poll(s, nsys, R.st, done, po, true)) return rc;
+    if (R.nc == 1 && s->dbg_trace) mb_trace_poll(s, nsys, "mb_bicg", it + 1, verify_round);
+    // the systems that still iterate (flags_pinned == 0) become the map of the compacted launches, when they are few
+    if (!s->dbg_compact || R.ilu) return FG_OK;
+    int act = 0, k = 0;
+    for (int i = 0; i < nsys; ++i) act += s->flags_pinned[i] == 0;
+    if (act == 0 || act > 16 || 4 * act > nsys) { R.n_map = 0; return FG_OK; }
+    bool same = (act == R.n_map);
+    for (int i = 0; i < nsys; ++i)
+        if (s->flags_pinned[i] == 0) { same = same && s->sys_map_pinned[k] == i; ++k; }
+    if (same) return FG_OK;
+    k = 0;
+    for (int i = 0; i < nsys; ++i) if (s->flags_pinned[i] == 0) s->sys_map_pinned[k++] = i;
+    // (the previous upload has executed: the poll that just returned was enqueued behind it)
+    FG_HIP_CHECK(hipMemcpyAsync(s->sys_map_dev, s->sys_map_pinned, sizeof(int32_t) * act, hipMemcpyHostToDevice, R.st));
+    R.n_map = act;
+    return FG_OK;
+}
+
+// every system has reported: those that report convergence are held to the recomputed residual (see k_mbb_reopen); the ones that
+// miss it iterate on, and `done` says whether any does
+static int mb_bicg_verify(MbBicgRun& R, int it, bool& done) {
+    const fg_mb_state* s = R.s;
+    bool any = false;
+    for (int i = 0; i < R.nsys; ++i) any = any || (s->flags_pinned[i] == 1 && s->info_pinned[i].converged && s->info_pinned[i].is_finite);
+    if (!any) return FG_OK;
+    ++R.verify_rounds;
+    mb_bicg_reopen(R, MB_OPEN_VERIFY, it + 1, 1);
+    return mb_bicg_poll(R, it, 0, R.verify_rounds, done);
+}
+
+// the end of a solve: the refined solve's best refinement point, the verdict, the predictor of the next solve of this place, and
+// the FG_MB_TRACE_FAIL dumps
+static int mb_bicg_finish(MbBicgRun& R, int* max_it) {
+    fg_mb_state* s = R.s; hipStream_t st = R.st;
+    const int nsys = R.nsys;
+    if (R.opt.refine) {
+        hipLaunchKernelGGL(k_mbr_best_restore, R.grid, dim3(FG_BLOCK), 0, st, R.n, R.q, s->x64, (const double*)s->x64_best, (const mb_real*)s->best_res);
+        hipLaunchKernelGGL(k_mbr_fold, R.grid, dim3(FG_BLOCK), 0, st, R.n, R.q, s->x64, 3);
         FG_HIP_CHECK(hipMemcpyAsync(s->info_pinned, s->info_dev, sizeof(fg_solve_info) * nsys, hipMemcpyDeviceToHost, st));
         FG_HIP_CHECK(hipStreamSynchronize(st));
     }
     const int frc = mb_finish(s, nsys, nullptr, max_it);
-    if (max_it && frc == FG_OK) pred = *max_it < 200 ? *max_it : 200;
+    if (max_it && frc == FG_OK) s->pred_bicg[R.opt.pred_slot & 31] = *max_it < 200 ? *max_it : 200;
     if (frc == FG_ERR_NOT_CONVERGED && s->dbg_fail)      // FG_MB_TRACE_FAIL: how far from the tolerance a capped solve ended
         for (int i = 0; i < nsys; ++i)
             if (!s->info_pinned[i].converged)
-                fprintf(stderr, "[mb_bicg] capped system %d (nc %d, ilu %d, project %d, refine %d): it %d residual %g tol %g\n", i, nc, ilu, project, refine,
-                        (int)s->info_pinned[i].used_iterations, (double)s->info_pinned[i].final_residual, (double)tol);
+                fprintf(stderr, "[mb_bicg] capped system %d (nc %d, ilu %d, project %d, refine %d): it %d residual %g tol %g\n", i, R.nc, R.ilu, R.opt.project, R.opt.refine,
+                        (int)s->info_pinned[i].used_iterations, (double)s->info_pinned[i].final_residual, (double)R.q.tol);
     if (frc == FG_ERR_NOT_FINITE && s->dbg_fail) {   // rare path, FG_MB_TRACE_FAIL only: the recurrence scalars of the systems that broke down
         std::vector<FgDacc> acc_raw((size_t)nsys * MB_ACC);
         std::vector<double> acc((size_t)nsys * MB_ACC);
@@ -1442,12 +1443,44 @@ int mb_bicgstab(fg_mb_state* s, const mb_real* dt, const mb_real* diag, const mb
         for (int i = 0; i < nsys; ++i) {
             if (s->info_pinned[i].is_finite) continue;
             fprintf(stderr, "[mb_bicg] non-finite system %d (nc %d, vec_mask %d, project %d, refine %d): it %d residual %g alpha %g omega %g acc",
-                    i, nc, vec_mask, project, refine, (int)s->info_pinned[i].used_iterations, s->info_pinned[i].final_residual, sc[2 * i], sc[2 * i + 1]);
+                    i, R.nc, R.vec_mask, R.opt.project, R.opt.refine, (int)s->info_pinned[i].used_iterations, s->info_pinned[i].final_residual, sc[2 * i], sc[2 * i + 1]);
             for (int k = 0; k < MB_ACC; ++k) fprintf(stderr, " %g", acc[(size_t)i * MB_ACC + k]);
             fprintf(stderr, "\n");
         }
     }
     return frc;
+}
+
+int mb_bicgstab(fg_mb_state* s, const mb_real* dt, const mb_real* diag, const mb_real* off, const mb_real* rhs, mb_real* x, int nc,
+                mb_real tol, int max_iterations, int use_x0, int* max_it, hipStream_t st, const MbBicgOpt& opt) {
+    MbBicgRun R = mb_bicg_form(s, diag, off, rhs, x, nc, tol, opt, st);
+    if (R.ilu) mb_ilu_factor(s, dt, diag, off, st);
+    else if (R.ml) mb_ml_scale(s, diag, st);
+    // a refined solve that has not converged after 1500 iterations is not going to: hand over to the caller's CG fallback
+    // instead of spending the reference's 5000 (one hard env would stall the whole batch)
+    if (opt.refine && max_iterations > 1500) max_iterations = 1500;
+    if (R.verify) FG_HIP_CHECK(hipMemsetAsync(s->verified, 0, sizeof(int32_t) * R.nsys, st));
+    hipLaunchKernelGGL(k_mbs_begin, R.sg, dim3(64), 0, st, dt, R.q, R.nsys);
+    mb_bicg_reopen(R, MB_OPEN_START, 0, use_x0);
+    bool done = false;
+    // first convergence poll where the previous solve of this kind finished (kernels of converged systems exit at once, so running
+    // a few launches past convergence costs ~2 us each, while every poll is a stream synchronisation: 10-20 us of idle GPU), then
+    // every 2 (every 10 beyond 20) iterations
+    const int pred = s->pred_bicg[opt.pred_slot & 31];
+    int next_poll = (pred > 2 && s->dbg_pred) ? pred : 2;
+    for (int it = 0; it < max_iterations && !done; ++it) {
+        if (it > 0 && it % R.restart_every == 0) mb_bicg_reopen(R, MB_OPEN_RESTART, it, 1);
+        mb_bicg_iterate(R, it);
+        if (it + 1 < next_poll && it + 1 != max_iterations) continue;
+        next_poll = it + 1 + (it < 20 ? 2 : 10);   // long (pressure) solves: fewer host round trips
+        if (int rc = mb_bicg_poll(R, it, (int)(it + 1 == max_iterations), 0, done)) return rc;
+        if (done && R.verify && R.verify_rounds < 3 && it + 1 < max_iterations) {
+            const int rounds = R.verify_rounds;
+            if (int rc = mb_bicg_verify(R, it, done)) return rc;
+            if (R.verify_rounds != rounds) next_poll = it + 1 + 2;
+        }
+    }
+    return mb_bicg_finish(R, max_it);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -1566,11 +1599,31 @@ __global__ void k_mbj_check(MbSolve q, fg_solve_info* __restrict__ mirror, int32
 }
 }  // namespace
 
+// after a round of sweeps, launched or by the clusters: did no system break down (pinned mirrors)
+static bool mb_sweeps_finite(const fg_mb_state* s, int nsys) {
+    for (int i = 0; i < nsys; ++i) if (!s->info_pinned[i].is_finite) return false;
+    return true;
+}
+
+// sweeps that are handed over: 3 = BiCGStab may start from the sweeps' iterate, 2 = it starts from zero.  From the iterate only when
+// every system still iterating is finite and well above the tolerance: sweeps that stall just above it sit at fp32's attainable
+// accuracy, the residual of such an iterate is rounding noise, and a BiCGStab recurrence started on noise has been seen to
+// report convergence on a wrong iterate (Airfoil2D, resolution_div 2: one env's drag -5.0 for 0.34).
+static int mb_sweeps_hand_over(const fg_mb_state* s, int nsys, mb_real tol) {
+    bool from_iterate = true;
+    for (int i = 0; i < nsys; ++i) {
+        const double r1 = (double)s->jac_res_pinned[2 * i];
+        from_iterate = from_iterate && s->info_pinned[i].is_finite && std::isfinite(r1);
+        if (s->flags_pinned[i] == 0 && !(r1 > 8.0 * (double)tol)) from_iterate = false;
+    }
+    return from_iterate ? 3 : 2;
+}
+
 int mb_jacobi(fg_mb_state* s, const mb_real* dt, const mb_real* diag, const mb_real* off, const mb_real* rhs, mb_real* x, int nc, mb_real tol,
               int use_x0, int* max_it, hipStream_t st, int pred_slot, int* outcome) {
     *outcome = 0;
-    const int ps = pred_slot & 3;
-    if (s->jac_skip[ps] > 0) { --s->jac_skip[ps]; return FG_OK; }
+    FgJacHist& H = s->jac_hist[pred_slot & 3];
+    if (!fg_sweeps_enter(H)) return FG_OK;
     *outcome = 2;
     // Check points at FIXED sweep counts -- 12, 14, ... 32 (beyond that BiCGStab is the cheaper iteration: the airfoil meshes need
     // 40-55 sweeps) -- each with a verdict on the device: a system stops at the first check point where its residual is below the
@@ -1608,30 +1661,26 @@ int mb_jacobi(fg_mb_state* s, const mb_real* dt, const mb_real* diag, const mb_r
     static_assert((FIRST + STEP * (CHECKS - 1) - 1 - (FIRST - 3)) / 2 < MB_ACC, "one accumulator per measuring sweep");
     // first poll at the check point the previous solve of this pass ended at
     int upto = 1;
-    if (s->jac_sweeps[ps] > FIRST) upto = 1 + (s->jac_sweeps[ps] - FIRST + STEP - 1) / STEP;
+    if (H.sweeps > FIRST) upto = 1 + (H.sweeps - FIRST + STEP - 1) / STEP;
     if (upto > CHECKS) upto = CHECKS;
     bool ok = false, by_cluster = false;
     // the sweeps of an env by a cluster of workgroups, one launch per solve (k_mbj_cluster, fg_mb_cluster.hip): the same sweeps, check
     // points and verdicts; its give-up rule is this loop's, applied per env
     if (mb_jacobi_cluster_ok(s, nc)) {
-        bool fell_back = false, done = false;
-        if (int rc = mb_jacobi_cluster(s, dt, diag, off, rhs, x, tol, use_x0, st, &fell_back, &done)) return rc;
-        if (!fell_back) {
-            by_cluster = true;
-            bool bad = false;
-            for (int i = 0; i < nsys; ++i) bad = bad || !s->info_pinned[i].is_finite;
-            ok = done && !bad;
-        }
+        bool fell_back = false;
+        if (int rc = mb_jacobi_cluster(s, dt, diag, off, rhs, x, tol, use_x0, st, &fell_back)) return rc;
+        by_cluster = !fell_back;
+        ok = by_cluster && mb_sweeps_finite(s, nsys);
+        for (int i = 0; i < nsys; ++i) ok = ok && s->flags_pinned[i] != 0;
     }
     while (!by_cluster) {
         const FgPollOut po = fg_poll_next(&s->poll);
         run_to_check(upto, po);
         bool done = false;
         if (int rc = mb_poll(s, nsys, st, done, po, false)) return rc;
-        bool bad = false;
+        bool bad = !mb_sweeps_finite(s, nsys);
         double need = 0.0;
         for (int i = 0; i < nsys; ++i) {
-            if (!s->info_pinned[i].is_finite) bad = true;
             if (s->flags_pinned[i] != 0) continue;
             const double r1 = s->jac_res_pinned[2 * i], r0 = s->jac_res_pinned[2 * i + 1];
             if (r0 > 0.0 && r1 > 0.0) {
@@ -1649,27 +1698,14 @@ int mb_jacobi(fg_mb_state* s, const mb_real* dt, const mb_real* diag, const mb_r
         upto = checks + (more < 1 ? 1 : more);
     }
     if (!ok) {
-        // handed over: 3 = BiCGStab may start from the sweeps' iterate, 2 = it starts from zero.  From the iterate only when every
-        // system still iterating is finite and well above the tolerance: sweeps that stall just above it sit at fp32's attainable
-        // accuracy, the residual of such an iterate is rounding noise, and a BiCGStab recurrence started on noise has been seen to
-        // report convergence on a wrong iterate (Airfoil2D, resolution_div 2: one env's drag -5.0 for 0.34).
-        bool from_iterate = true;
-        for (int i = 0; i < nsys; ++i) {
-            const double r1 = (double)s->jac_res_pinned[2 * i];
-            from_iterate = from_iterate && s->info_pinned[i].is_finite && std::isfinite(r1);
-            if (s->flags_pinned[i] == 0 && !(r1 > 8.0 * (double)tol)) from_iterate = false;
-        }
-        *outcome = from_iterate ? 3 : 2;
-        s->jac_fails[ps] += 1;
-        s->jac_skip[ps] = s->jac_fails[ps] > 6 ? 512 : (4 << s->jac_fails[ps]);
-        s->jac_sweeps[ps] = 0;
+        *outcome = mb_sweeps_hand_over(s, nsys, tol);
+        fg_sweeps_gave_up(H);
         return FG_OK;
     }
-    s->jac_fails[ps] = 0;
     const int frc = mb_finish(s, nsys, nullptr, max_it);
     int used = 0;
     for (int i = 0; i < nsys; ++i) used = std::max(used, (int)s->info_pinned[i].used_iterations);
-    s->jac_sweeps[ps] = used > 0 ? used : FIRST;
+    fg_sweeps_solved(H, used > 0 ? used : FIRST);
     *outcome = 1;
     return frc;
 }
@@ -1682,12 +1718,14 @@ int mb_jacobi(fg_mb_state* s, const mb_real* dt, const mb_real* diag, const mb_r
 // with every failure (4 ... 256) and halves with every success.
 int mb_pressure_bicgstab(fg_mb_state* s, const mb_real* dt, mb_real tol, int max_iterations, int use_x0, int* max_it, hipStream_t st, int project,
                          int refine, int pred_slot) {
+    const MbBicgOpt plain = {project, refine, MB_PRE_NONE, pred_slot};
     const bool have_ml = s->ml_on && s->ml_a4 != nullptr && s->ml_mp != nullptr && s->d == 2;
     if (have_ml && s->ml_bicg_skip > 0) --s->ml_bicg_skip;
     else if (have_ml) {
         ++s->ml_bicg_attempts;
         const int cap = max_iterations < s->dbg_ml_cap ? max_iterations : s->dbg_ml_cap;
-        const int rc = mb_bicgstab(s, dt, s->Pdiag, s->Poff, s->div, s->pres, 1, tol, cap, use_x0, max_it, st, project, refine, 1, (pred_slot + 16) & 31);
+        const MbBicgOpt trial = {project, refine, MB_PRE_MULTILEVEL, (pred_slot + 16) & 31};
+        const int rc = mb_bicgstab(s, dt, s->Pdiag, s->Poff, s->div, s->pres, 1, tol, cap, use_x0, max_it, st, trial);
         if (rc == FG_OK) { s->ml_bicg_backoff = s->ml_bicg_backoff > 4 ? s->ml_bicg_backoff / 2 : 4; return rc; }
         if (rc != FG_ERR_NOT_CONVERGED && rc != FG_ERR_NOT_FINITE) return rc;
         ++s->ml_bicg_failures;
@@ -1695,65 +1733,88 @@ int mb_pressure_bicgstab(fg_mb_state* s, const mb_real* dt, mb_real tol, int max
         s->ml_bicg_backoff = s->ml_bicg_backoff < 256 ? s->ml_bicg_backoff * 2 : 256;
         use_x0 = (rc == FG_ERR_NOT_CONVERGED && refine) ? 1 : 0;   // the refined solver handed back its best refinement point
     }
-    return mb_bicgstab(s, dt, s->Pdiag, s->Poff, s->div, s->pres, 1, tol, max_iterations, use_x0, max_it, st, project, refine, 0, pred_slot);
+    return mb_bicgstab(s, dt, s->Pdiag, s->Poff, s->div, s->pres, 1, tol, max_iterations, use_x0, max_it, st, plain);
 }
 
-// project_mean: every residual is used with its mean removed.  For a symmetric matrix with the constant null space (an
-// orthogonal mesh) that changes nothing; with cross-metric terms 1^T P != 0, the plain recurrence accumulates a constant
-// residual component that no search direction can reduce (the solve stalls just above the envs' tolerance and cannot be
-// warm-started), and removing it is what makes the singular system consistent.
-int mb_cg(fg_mb_state* s, const mb_real* dt, const mb_real* diag, const mb_real* off, const mb_real* rhs, mb_real* x, mb_real tol,
-          int max_iterations, int use_x0, int project_mean, mb_real stall_accept, int* max_it, hipStream_t st) {
-    const int nsys = s->B, n = s->N;
-    // the multilevel preconditioner in kernel form (k_ml_prolong_cg / k_mbc_ap<.., MBC_PRE> / k_mbc_update<.., true>): what the fp64 build runs once
-    // the tables are installed, and in the fp32 build the debug form FG_MB_PCG_KERNEL=1 of the on-chip / cluster kernels' recurrence.
-    // Pressure systems of 2-D meshes; the residual projected onto the complement of the constant, or not at all
-    const bool pre = (FG_MB_F64 || s->dbg_pcg_kernel) && s->ml_on && s->ml_a4 != nullptr && s->ml_mp != nullptr && s->d == 2 &&
-                     diag == s->Pdiag && (!project_mean || s->yproj_const);
-    if (!pre) {
-        const int pm = project_mean ? (s->yproj_const ? 1 : 2) : 0;
-        if (mb_cluster_ok(s, pm, diag, off)) {
-            bool fell_back = false;
-            const int rc = mb_cg_cluster(s, dt, rhs, x, tol, max_iterations, use_x0, pm, stall_accept, max_it, st, &fell_back);
-            if (!fell_back) return rc;
+// Pressure CG.  What all of its forms are held to (MbCgRule), what the two whole-solve drivers share (fg_mb_onchip.hip,
+// fg_mb_cluster.hip), the choice of the form, and the kernel-pair form itself.
+MbCgRule mb_cg_rule(const fg_mb_state* s, mb_real tol, int max_iterations, int use_x0, int project_mean, mb_real stall_accept) {
+    return {((max_iterations + MB_CG_CHUNK - 1) / MB_CG_CHUNK) * MB_CG_CHUNK, s->cg_stall_limit, stall_accept > 1.f ? stall_accept : 0.f, 20,
+            tol, use_x0, project_mean ? (s->yproj_const ? 1 : 2) : 0};
+}
+
+int mb_whole_solve_wait(fg_mb_state* s, const FgPollOut& po, int nsys, hipStream_t st) {
+    return fg_poll_wait(&s->poll, s->prof_on ? FgPollOut{nullptr, 0} : po, 0, nsys, st);
+}
+
+long long mb_prof_whole_solve(fg_mb_state* s, int nsys) {
+    fg_f32 ms = 0.f;
+    (void)hipEventElapsedTime(&ms, s->prof_ev_oc[0], s->prof_ev_oc[1]);   // (the stream was synchronised: both events have completed)
+    long long its = 0;
+    for (int i = 0; i < nsys; ++i) its += s->flags_pinned[i] > 0 ? s->flags_pinned[i] : 0;
+    s->prof_ms[2] += ms;
+    s->prof_n[2] += 1; s->prof_launches[2] += 1;
+    s->prof_its += its;
+    return its;
+}
+
+bool mb_cluster_fell_back(fg_mb_state* s, int nsys) {
+    for (int i = 0; i < nsys; ++i)
+        if (s->flags_pinned[i] == -77) { ++s->cl_fallbacks; return true; }
+    return false;
+}
+
+// the samples of the chunks' first iterations (event pairs around the kernel pair), read after the poll that follows them
+static int mb_prof_collect_chunks(fg_mb_state* s) {
+    for (int k = 0; k < s->prof_used; ++k) {
+        fg_f32 ms = 0.f;
+        FG_HIP_CHECK(hipEventElapsedTime(&ms, s->prof_ev[2 * k], s->prof_ev[2 * k + 1]));
+        const int kind = s->prof_kind[k];
+        if (s->prof_active[k] > 0) {
+            // algorithmic bytes per cell: stencil kernel r, p_old, diag, 2d off, p_new, v (+ the neighbour table, shared
+            // by the env batch); update kernel x (r/w), p, v, r (r/w)
+            const double per_cell = kind == 0 ? 4.0 * (5 + 2 * s->d) + 4.0 * 2 * s->d / (double)s->B : 24.0;
+            s->prof_ms[kind] += ms;
+            s->prof_bytes[kind] += per_cell * (double)s->N * s->prof_active[k];
+            s->prof_n[kind] += 1;
         }
-        if (mb_onchip_ok(s, pm)) return mb_cg_onchip(s, dt, diag, off, rhs, x, tol, max_iterations, use_x0, pm, stall_accept, max_it, st);
     }
-    MbSolve q = mb_solve_ptrs(s, diag, off, rhs, x, 1, tol);
+    s->prof_used = 0;
+    return FG_OK;
+}
+
+// Which form solves: the clusters, one workgroup per env, or the kernel pair -- plain, or with the multilevel preconditioner in
+// kernel form (k_ml_prolong_cg / k_mbc_ap<.., MBC_PRE> / k_mbc_update<.., true>): what the fp64 build runs once the tables are
+// installed, and in the fp32 build the debug form FG_MB_PCG_KERNEL=1 of the on-chip / cluster kernels' recurrence.  Pressure systems
+// of 2-D meshes; the residual projected onto the complement of the constant, or not at all
+enum MbCgForm { MB_CG_ONCHIP, MB_CG_KERNELS, MB_CG_KERNELS_PRE };
+static MbCgForm mb_cg_form(const fg_mb_state* s, const mb_real* diag, const mb_real* off, int pm_mode, bool* clusters_first) {
+    *clusters_first = false;
+    if ((FG_MB_F64 || s->dbg_pcg_kernel) && s->ml_on && s->ml_a4 != nullptr && s->ml_mp != nullptr && s->d == 2 && diag == s->Pdiag && pm_mode != 2)
+        return MB_CG_KERNELS_PRE;
+    *clusters_first = mb_cluster_ok(s, pm_mode, diag, off);   // (a cluster that gives up on a granule hands the solve to the form returned)
+    return mb_onchip_ok(s, pm_mode) ? MB_CG_ONCHIP : MB_CG_KERNELS;
+}
+
+// the kernel-pair form: MB_CG_CHUNK iterations are enqueued between two convergence checks (one poll of the host per chunk); every
+// launch gets its iteration index, and the iteration the recurrence last started at, as arguments
+static int mb_cg_kernels(fg_mb_state* s, const mb_real* dt, const mb_real* diag, const mb_real* off, const mb_real* rhs, mb_real* x,
+                         const MbCgRule& R, bool pre, int* max_it, hipStream_t st) {
+    const int nsys = s->B, n = s->N, pm_mode = R.pm_mode, project_mean = pm_mode != 0;
+    MbSolve q = mb_solve_ptrs(s, diag, off, rhs, x, 1, R.tol);
     q.rw = nullptr;
-    q.best_x = s->w[4]; q.best_it = s->best_it; q.stall_limit = s->cg_stall_limit;
-    q.accept_factor = stall_accept > 1.f ? stall_accept : 0.f; q.accept_window = 20;
+    q.best_x = s->w[4]; q.best_it = s->best_it; q.stall_limit = R.stall_limit;
+    q.accept_factor = R.accept_factor; q.accept_window = R.accept_window;
     const dim3 sg((nsys + 63) / 64), sb(64), grid((n + FG_BLOCK - 1) / FG_BLOCK, nsys), blk(FG_BLOCK);
     const bool vec4 = (n % 4 == 0) && !s->dbg_scalar_cg;   // FG_MB_SCALAR_CG=1 forces the one-cell-per-thread kernels
     const dim3 grid4((n / 4 + FG_BLOCK - 1) / FG_BLOCK, nsys);
     hipLaunchKernelGGL(k_mbs_begin, sg, sb, 0, st, dt, q, nsys);
-    MB_DISPATCH(s, hipLaunchKernelGGL(k_mbs_init<DIMS>, grid, blk, 0, st, s->dev, q, use_x0, project_mean ? C_SUM : -1, 0););
+    MB_DISPATCH(s, hipLaunchKernelGGL(k_mbs_init<DIMS>, grid, blk, 0, st, s->dev, q, R.use_x0, project_mean ? C_SUM : -1, 0););
     const MlDev ML = mb_ml_dev(s);
     if (pre) { mb_ml_scale(s, diag, st); s->ml_cg_solves += 1; }
+    q.max_iterations = R.max_iterations;      // (set behind the opening launches, as ever: they are handed 0)
     bool done = false;
-    // CG_CHUNK iterations are enqueued between two convergence checks (one poll of the host per chunk); every launch gets its
-    // iteration index, and the iteration the recurrence last started at, as arguments
-    constexpr int CG_CHUNK = 20, CG_RESTART = 100;
-    q.max_iterations = ((max_iterations + CG_CHUNK - 1) / CG_CHUNK) * CG_CHUNK;
     int active_now = 0;  // systems still iterating, from the poll before this chunk (all active ones at chunk 0)
-    auto prof_collect = [&]() -> int {
-        for (int k = 0; k < s->prof_used; ++k) {
-            fg_f32 ms = 0.f;
-            FG_HIP_CHECK(hipEventElapsedTime(&ms, s->prof_ev[2 * k], s->prof_ev[2 * k + 1]));
-            const int kind = s->prof_kind[k];
-            if (s->prof_active[k] > 0) {
-                // algorithmic bytes per cell: stencil kernel r, p_old, diag, 2d off, p_new, v (+ the neighbour table, shared
-                // by the env batch); update kernel x (r/w), p, v, r (r/w)
-                const double per_cell = kind == 0 ? 4.0 * (5 + 2 * s->d) + 4.0 * 2 * s->d / (double)s->B : 24.0;
-                s->prof_ms[kind] += ms;
-                s->prof_bytes[kind] += per_cell * (double)n * s->prof_active[k];
-                s->prof_n[kind] += 1;
-            }
-        }
-        s->prof_used = 0;
-        return FG_OK;
-    };
-    const int pm_mode = project_mean ? (s->yproj_const ? 1 : 2) : 0;
     int it_fresh = 0;   // iteration the recurrence started at: 0, then that of the last restart
     // one launch of a recurrence kernel, between the pair `e` of the live profiler's events when the iteration is sampled
 #define MBC_LAUNCH(K, g, e, ...)                                                                                                  \
@@ -1766,7 +1827,7 @@ int mb_cg(fg_mb_state* s, const mb_real* dt, const mb_real* diag, const mb_real*
         const mb_real* pB = s->w[2];
         const mb_real* z = pre ? s->ml_mp : nullptr;   // z = M (r - mean r) of the preconditioned recurrence
         MB_DISPATCH_PM(s, pm_mode, {
-            for (int k = 0; k < CG_CHUNK; ++k) {
+            for (int k = 0; k < MB_CG_CHUNK; ++k) {
                 const int li = it0 + k;
                 const bool ev = !pre && sample && k == 0 && s->prof_used + 2 <= 32;   // (the live profiler samples the plain recurrence)
                 const int e0 = s->prof_used;
@@ -1792,44 +1853,38 @@ int mb_cg(fg_mb_state* s, const mb_real* dt, const mb_real* diag, const mb_real*
                 }
             }
         });
-        const int last = it0 + CG_CHUNK - 1;   // the check reads what the update kernel of the chunk's last iteration summed
+        const int last = it0 + MB_CG_CHUNK - 1;   // the check reads what the update kernel of the chunk's last iteration summed
         hipLaunchKernelGGL(k_mbs_check, sg, sb, 0, st, q, s->info_pinned, s->flags_pinned, C_RHO + (last + 1) % 3, last, n, nsys,
                            (int)(last + 1 >= q.max_iterations), project_mean ? C_SUM + (last + 1) % 3 : -1, po);
     };
 #undef MBC_LAUNCH
-    const bool trace = s->dbg_trace != 0;
     int recoveries = 0;
-    bool need_restart = false;
-    for (int it = 0; it < q.max_iterations && !done; it += CG_CHUNK) {
-        if (it > 0 && (it % CG_RESTART == 0 || need_restart)) {
+    bool need_restart = false, failed = false;
+    for (int it = 0; it < q.max_iterations && !done; it += MB_CG_CHUNK) {
+        if (it > 0 && (it % MB_CG_RESTART == 0 || need_restart)) {
             need_restart = false;
             it_fresh = it;
             hipLaunchKernelGGL(k_mbc_clear, sg, sb, 0, st, q, nsys, it);
             MB_DISPATCH(s, hipLaunchKernelGGL(k_mbc_restart<DIMS>, grid, blk, 0, st, s->dev, q, it, project_mean););
         }
-        if (it == 0) { active_now = 0; for (int i = 0; i < nsys; ++i) active_now += 1; }  // inactive envs exit in k_mbs_begin's flags; counted below after the first poll
+        if (it == 0) active_now = nsys;  // inactive envs exit in k_mbs_begin's flags; counted below after the first poll
         const FgPollOut po = fg_poll_next(&s->poll);
         enqueue_chunk(it, s->prof_on && (s->prof_chunk++ % 4 == 0), po);
         if (int rc = mb_poll(s, nsys, st, done, po, true)) return rc;
         active_now = 0;
         for (int i = 0; i < nsys; ++i) active_now += s->flags_pinned[i] == 0;
-        if (s->prof_used) if (int rc = prof_collect()) return rc;
+        if (s->prof_used) if (int rc = mb_prof_collect_chunks(s)) return rc;
         bool broke = false;
         for (int i = 0; i < nsys; ++i) broke = broke || s->flags_pinned[i] == 2;
-        if (broke && recoveries < 3 && it + CG_CHUNK < q.max_iterations) {
+        if (broke && recoveries < 3 && it + MB_CG_CHUNK < q.max_iterations) {
             hipLaunchKernelGGL(k_mbs_recover, grid, blk, 0, st, n, q);
             hipLaunchKernelGGL(k_mbs_recover_flags, sg, sb, 0, st, q, nsys);
             ++recoveries;
             need_restart = true;
             done = false;
         }
-        if (trace) {
-            mb_real lo = 1e30f, hi = 0.f; int active = 0;
-            for (int i = 0; i < nsys; ++i) { const mb_real c = s->info_pinned[i].final_residual; lo = c < lo ? c : lo; hi = c > hi ? c : hi; active += s->flags_pinned[i] == 0; }
-            fprintf(stderr, "[mb_cg] it %4d residual min %.3e max %.3e active %d\n", it + CG_CHUNK, lo, hi, active);
-        }
+        if (s->dbg_trace) mb_trace_poll(s, nsys, "mb_cg", it + MB_CG_CHUNK, 0);
     }
-    bool failed = false;
     for (int i = 0; i < nsys; ++i) failed = failed || !s->info_pinned[i].converged || s->flags_pinned[i] == 5;
     if (failed) {
         hipLaunchKernelGGL(k_mbs_restore_best, grid, blk, 0, st, n, q);
@@ -1837,4 +1892,21 @@ int mb_cg(fg_mb_state* s, const mb_real* dt, const mb_real* diag, const mb_real*
         FG_HIP_CHECK(hipStreamSynchronize(st));
     }
     return mb_finish(s, nsys, nullptr, max_it);
+}
+
+// project_mean: every residual is used with its mean removed.  For a symmetric matrix with the constant null space (an
+// orthogonal mesh) that changes nothing; with cross-metric terms 1^T P != 0, the plain recurrence accumulates a constant
+// residual component that no search direction can reduce (the solve stalls just above the envs' tolerance and cannot be
+// warm-started), and removing it is what makes the singular system consistent.
+int mb_cg(fg_mb_state* s, const mb_real* dt, const mb_real* diag, const mb_real* off, const mb_real* rhs, mb_real* x, mb_real tol,
+          int max_iterations, int use_x0, int project_mean, mb_real stall_accept, int* max_it, hipStream_t st) {
+    const MbCgRule R = mb_cg_rule(s, tol, max_iterations, use_x0, project_mean, stall_accept);
+    bool clusters_first = false, fell_back = false;
+    const MbCgForm form = mb_cg_form(s, diag, off, R.pm_mode, &clusters_first);
+    if (clusters_first) {
+        const int rc = mb_cg_cluster(s, dt, rhs, x, R, max_it, st, &fell_back);
+        if (!fell_back) return rc;
+    }
+    if (form == MB_CG_ONCHIP) return mb_cg_onchip(s, dt, diag, off, rhs, x, R, max_it, st);
+    return mb_cg_kernels(s, dt, diag, off, rhs, x, R, form == MB_CG_KERNELS_PRE, max_it, st);
 }

@@ -941,28 +941,27 @@ bool mb_onchip_ok(const fg_mb_state* s, int pm_mode) {
     return s->onchip_mode && s->d == 2 && s->nbr16 != nullptr && s->N <= OC_MAX_CELLS && pm_mode != 2;
 }
 
-// the whole CG solve of every env in one launch (k_mbc_onchip); same arguments and results as mb_cg
-int mb_cg_onchip(fg_mb_state* s, const mb_real* dt, const mb_real* diag, const mb_real* off, const mb_real* rhs, mb_real* x, mb_real tol,
-                 int max_iterations, int use_x0, int pm_mode, mb_real stall_accept, int* max_it, hipStream_t st) {
+// the whole CG solve of every env in one launch (k_mbc_onchip); same results as mb_cg
+int mb_cg_onchip(fg_mb_state* s, const mb_real* dt, const mb_real* diag, const mb_real* off, const mb_real* rhs, mb_real* x, const MbCgRule& R,
+                 int* max_it, hipStream_t st) {
 #if FG_MB_F64
-    (void)dt; (void)diag; (void)off; (void)rhs; (void)x; (void)tol; (void)max_iterations; (void)use_x0; (void)pm_mode; (void)stall_accept; (void)max_it; (void)st;
+    (void)dt; (void)diag; (void)off; (void)rhs; (void)x; (void)R; (void)max_it; (void)st;
     fg_set_error("the on-chip CG is not part of the fp64 build");   // (never reached: fg_mb_create switches it off there)
     return FG_ERR_UNSUPPORTED;
 #else
-    const int nsys = s->B, n = s->N;
-    MbSolve q = mb_solve_ptrs(s, diag, off, rhs, x, 1, tol);
+    const int nsys = s->B, n = s->N, pm_mode = R.pm_mode;
+    MbSolve q = mb_solve_ptrs(s, diag, off, rhs, x, 1, R.tol);
     q.best_x = s->w[4]; q.best_it = s->best_it;
-    constexpr int CG_CHUNK = 20, CG_RESTART = 100;
     OcParams o;
     o.nbr16 = s->nbr16; o.dt = dt; o.yp = s->dev.yproj;
     o.off4 = (off == s->Poff && !(s->oc_variant & 2)) ? s->Poff4 : nullptr;
     o.fence = (s->oc_variant & 1) ? 0 : 1;
     o.dbg = s->oc_variant >> 8;
     o.dbg_out = s->oc_dbg;
-    o.use_x0 = use_x0; o.project_mean = pm_mode; o.restart_every = CG_RESTART; o.check_every = CG_CHUNK;
-    o.max_iterations = ((max_iterations + CG_CHUNK - 1) / CG_CHUNK) * CG_CHUNK;
-    o.stall_limit = s->cg_stall_limit; o.accept_window = 20;
-    o.accept_factor = stall_accept > 1.f ? stall_accept : 0.f; o.tol = tol;
+    o.use_x0 = R.use_x0; o.project_mean = pm_mode; o.restart_every = MB_CG_RESTART; o.check_every = MB_CG_CHUNK;
+    o.max_iterations = R.max_iterations;
+    o.stall_limit = R.stall_limit; o.accept_window = R.accept_window;
+    o.accept_factor = R.accept_factor; o.tol = R.tol;
     o.info_host = s->info_pinned; o.its_host = s->flags_pinned;
     o.poll = fg_poll_next(&s->poll);
     const bool ev = s->prof_on != 0;
@@ -1008,19 +1007,13 @@ int mb_cg_onchip(fg_mb_state* s, const mb_real* dt, const mb_real* diag, const m
     else if (n <= 24 * 1024) OC_LAUNCH_PM(24, false, 1024, false, false, false);
     else OC_LAUNCH_PM(28, false, 1024, false, false, false);
 #undef OC_LAUNCH_PRE
-    // info_pinned / flags_pinned (iterations run) were written by the kernel; with profiling events the stream is synchronised
-    if (int rc = fg_poll_wait(&s->poll, ev ? FgPollOut{nullptr, 0} : o.poll, 0, nsys, st)) return rc;
+    // info_pinned / flags_pinned (iterations run) were written by the kernel
+    if (int rc = mb_whole_solve_wait(s, o.poll, nsys, st)) return rc;
     if (ev) {
-        fg_f32 ms = 0.f;
-        FG_HIP_CHECK(hipEventElapsedTime(&ms, s->prof_ev_oc[0], s->prof_ev_oc[1]));
-        long long its = 0;
-        for (int i = 0; i < nsys; ++i) its += s->flags_pinned[i] > 0 ? s->flags_pinned[i] : 0;
+        const long long its = mb_prof_whole_solve(s, nsys);
         // bytes the kernel streams: per iteration and cell the off-diagonals (4 F) and the packed neighbour table (2 F);
         // per solve and cell rhs, x0 / x, diagonal, kept iterate (about 20 B)
-        s->prof_ms[2] += ms;
         s->prof_bytes[2] += (double)its * n * (6.0 * s->F) + (double)nsys * n * 20.0;
-        s->prof_n[2] += 1; s->prof_launches[2] += 1;
-        s->prof_its += its;
     }
     return mb_finish(s, nsys, nullptr, max_it);
 #endif

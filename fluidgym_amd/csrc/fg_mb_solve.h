@@ -1,6 +1,7 @@
-// Shared by the translation units of the multi-block Krylov solvers (fg_mb_step.hip: assembly kernels, BiCGStab / chunked CG kernels,
-// multilevel preconditioner, step driver and C ABI; fg_mb_onchip.hip: the whole-solve-on-chip CG): accumulator names, the solver's
-// pointer bundle, verdict bookkeeping, and the host entry points that cross the two files.
+// Shared by the translation units of the multi-block solvers (fg_mb_step.hip: assembly kernels, step driver with its retry ladders
+// and C ABI; fg_mb_krylov.hip: BiCGStab / chunked CG / sweep kernels, multilevel and ILU preconditioners and their host drivers;
+// fg_mb_onchip.hip: the whole-solve-on-chip CG; fg_mb_cluster.hip: the same solve and the sweeps by a cluster of workgroups per env):
+// accumulator names, the solver's pointer bundle, verdict bookkeeping, and the host entry points that cross the files.
 #pragma once
 #include "fg_mb.h"
 
@@ -134,28 +135,41 @@ int mb_alloc(fg_mb_state* s, T** p, size_t count) {
 // host side (fg_mb_krylov.hip unless noted)
 MbSolve mb_solve_ptrs(fg_mb_state* s, const mb_real* diag, const mb_real* off, const mb_real* rhs, mb_real* x, int nc, mb_real tol);
 int mb_finish(fg_mb_state* s, int nsys, fg_solve_info* info_host, int* max_it);
-// fg_mb_onchip.hip: the whole CG solve of every env in one launch (k_mbc_onchip); same arguments and results as mb_cg
+// the pressure CG in all its forms: iterations between two checks / two restarts from the true residual, and what a solve is held to
+constexpr int MB_CG_CHUNK = 20, MB_CG_RESTART = 100;
+struct MbCgRule {   // max_iterations: rounded up to whole chunks; pm_mode: residual projection 0 none, 1 constant, 2 installed vector (yproj)
+    int max_iterations, stall_limit; mb_real accept_factor; int accept_window; mb_real tol; int use_x0, pm_mode;
+};
+MbCgRule mb_cg_rule(const fg_mb_state* s, mb_real tol, int max_iterations, int use_x0, int project_mean, mb_real stall_accept);
+// wait for a whole-solve kernel's own results: by sequence words, or a stream synchronisation when the live profiler has events around it
+int mb_whole_solve_wait(fg_mb_state* s, const FgPollOut& po, int nsys, hipStream_t st);
+// the live profiler's sample of such a launch (kernel class 2); returns the iterations its systems ran, for the caller's byte count
+long long mb_prof_whole_solve(fg_mb_state* s, int nsys);
+// a cluster kernel gave up on a granule (-77 in the pinned flags): counted; the caller repeats the solve with the one-workgroup kernels
+bool mb_cluster_fell_back(fg_mb_state* s, int nsys);
+// fg_mb_onchip.hip: the whole CG solve of every env in one launch (k_mbc_onchip); same results as mb_cg
 bool mb_onchip_ok(const fg_mb_state* s, int pm_mode);
-int mb_cg_onchip(fg_mb_state* s, const mb_real* dt, const mb_real* diag, const mb_real* off, const mb_real* rhs, mb_real* x, mb_real tol,
-                 int max_iterations, int use_x0, int pm_mode, mb_real stall_accept, int* max_it, hipStream_t st);
+int mb_cg_onchip(fg_mb_state* s, const mb_real* dt, const mb_real* diag, const mb_real* off, const mb_real* rhs, mb_real* x, const MbCgRule& R,
+                 int* max_it, hipStream_t st);
 // fg_mb_cluster.hip: the same solve by a cluster of workgroups per env (k_mbc_cluster); tables built behind fg_mb_set_multilevel
 int mb_cluster_build(fg_mb_state* s, int n4, int n8, const int32_t* rect4_host, const uint16_t* parent4, const uint2* child8, const mb_real* rd4,
                      const mb_real* aci8_padded);
 bool mb_cluster_ok(const fg_mb_state* s, int pm_mode, const mb_real* diag, const mb_real* off);
-int mb_cg_cluster(fg_mb_state* s, const mb_real* dt, const mb_real* rhs, mb_real* x, mb_real tol, int max_iterations, int use_x0, int pm_mode,
-                  mb_real stall_accept, int* max_it, hipStream_t st, bool* fell_back);
+int mb_cg_cluster(fg_mb_state* s, const mb_real* dt, const mb_real* rhs, mb_real* x, const MbCgRule& R, int* max_it, hipStream_t st, bool* fell_back);
 bool mb_jacobi_cluster_ok(const fg_mb_state* s, int nc);
 int mb_jacobi_cluster(fg_mb_state* s, const mb_real* dt, const mb_real* diag, const mb_real* off, const mb_real* rhs, mb_real* x, mb_real tol,
-                      int use_x0, hipStream_t st, bool* fell_back, bool* done);
+                      int use_x0, hipStream_t st, bool* fell_back);
 constexpr int ML_N8_MAX = 2048, ML_ROWS = 16, ML_CG = 64;   // multilevel coarse solve: rows per workgroup, column groups
 void mb_ml_scale(fg_mb_state* s, const mb_real* diag, hipStream_t st);
 bool mb_ilu_prepare(fg_mb_state* s);
 void mb_ilu_factor(fg_mb_state* s, const mb_real* dt, const mb_real* diag, const mb_real* off, hipStream_t st);
 void mb_ilu_apply(fg_mb_state* s, const MbSolve& q, const mb_real* in, mb_real* out, hipStream_t st);
 void mb_ml_apply(fg_mb_state* s, const MbSolve& q, const mb_real* in, mb_real* out, hipStream_t st, int fused = 0, int it = 0);
+// a BiCGStab solve beyond its system: project (iterate on Q P), refine (fp64 iterate and residual), right preconditioner, predictor slot
+enum MbPrecond { MB_PRE_NONE = 0, MB_PRE_MULTILEVEL = 1, MB_PRE_ILU = 2 };
+struct MbBicgOpt { int project = 0; int refine = 0; MbPrecond precond = MB_PRE_NONE; int pred_slot = 31; };
 int mb_bicgstab(fg_mb_state* s, const mb_real* dt, const mb_real* diag, const mb_real* off, const mb_real* rhs, mb_real* x, int nc,
-                mb_real tol, int max_iterations, int use_x0, int* max_it, hipStream_t st, int project = 0, int refine = 0, int multilevel = 0,
-                int pred_slot = 31);
+                mb_real tol, int max_iterations, int use_x0, int* max_it, hipStream_t st, const MbBicgOpt& opt = MbBicgOpt());
 // point-Jacobi sweeps for the velocity systems where their rows are diagonally dominant (the cylinder meshes: 12 sweeps); *outcome: 0 not
 // tried (backing off), 1 solved, 2 / 3 given up -- then the caller runs BiCGStab, from a cleared start vector (2) or from the sweeps' last
 // iterate, which sits in x (3)

@@ -758,28 +758,22 @@ __global__ __launch_bounds__(FG_BLOCK) void k_mb_wall_forces(int d, int N, int N
     }
 }
 
-extern "C" int fg_mb_wall_forces(fg_mb_handle s, const int32_t* cell_index, const int32_t* slot_index, const mb_real* geom, int32_t n,
-                                 int32_t layers, mb_real area_scale, mb_real viscosity, mb_real* out, void* stream) {
-    FG_REQUIRE(s && s->finalized && s->velocity && s->pressure && s->bvel, FG_ERR_NOT_BOUND, "fg_mb_wall_forces: fields not bound");
-    FG_REQUIRE(cell_index && slot_index && geom && out && n > 0 && layers > 0, FG_ERR_INVALID_ARG, "fg_mb_wall_forces: bad argument");
-    hipLaunchKernelGGL(k_mb_wall_forces, dim3(layers, s->B), dim3(FG_BLOCK), 0, (hipStream_t)stream, s->d, s->N, s->NB, n, layers,
-                       (const mb_real*)s->velocity, (const mb_real*)s->bvel, (const mb_real*)s->pressure, cell_index, slot_index, geom, area_scale,
-                       MbNu{viscosity, nullptr}, out);
-    FG_HIP_CHECK(hipGetLastError());
-    return FG_OK;
-}
-// the same sums with env b's own viscosity: viscosity_B [B] on the device (read at launch, like the handle's own array), nullptr =
+// the sums with env b's own viscosity: viscosity_B [B] on the device (read at launch, like the handle's own array), nullptr =
 // the scalar for every env
 extern "C" int fg_mb_wall_forces_batch(fg_mb_handle s, const int32_t* cell_index, const int32_t* slot_index, const mb_real* geom, int32_t n,
                                        int32_t layers, mb_real area_scale, mb_real viscosity, const mb_real* viscosity_B, mb_real* out,
                                        void* stream) {
-    FG_REQUIRE(s && s->finalized && s->velocity && s->pressure && s->bvel, FG_ERR_NOT_BOUND, "fg_mb_wall_forces_batch: fields not bound");
-    FG_REQUIRE(cell_index && slot_index && geom && out && n > 0 && layers > 0, FG_ERR_INVALID_ARG, "fg_mb_wall_forces_batch: bad argument");
+    FG_REQUIRE(s && s->finalized && s->velocity && s->pressure && s->bvel, FG_ERR_NOT_BOUND, "fg_mb_wall_forces: fields not bound");
+    FG_REQUIRE(cell_index && slot_index && geom && out && n > 0 && layers > 0, FG_ERR_INVALID_ARG, "fg_mb_wall_forces: bad argument");
     hipLaunchKernelGGL(k_mb_wall_forces, dim3(layers, s->B), dim3(FG_BLOCK), 0, (hipStream_t)stream, s->d, s->N, s->NB, n, layers,
                        (const mb_real*)s->velocity, (const mb_real*)s->bvel, (const mb_real*)s->pressure, cell_index, slot_index, geom, area_scale,
                        MbNu{viscosity, viscosity_B}, out);
     FG_HIP_CHECK(hipGetLastError());
     return FG_OK;
+}
+extern "C" int fg_mb_wall_forces(fg_mb_handle s, const int32_t* cell_index, const int32_t* slot_index, const mb_real* geom, int32_t n,
+                                 int32_t layers, mb_real area_scale, mb_real viscosity, mb_real* out, void* stream) {
+    return fg_mb_wall_forces_batch(s, cell_index, slot_index, geom, n, layers, area_scale, viscosity, nullptr, out, stream);
 }
 
 extern "C" int fg_mb_set_viscosity(fg_mb_handle s, mb_real nu) {
@@ -798,6 +792,80 @@ extern "C" int fg_mb_set_viscosity_batch(fg_mb_handle s, const mb_real* nu_B) {
     }
     s->nu_B = nu_B;
     return FG_OK;
+}
+
+// One velocity solve of non-orthogonal pass `no` (the systems are assembled): the sweeps where the policy asks for them, BiCGStab,
+// and the reference's retry ladder.  *m: iterations of the attempt that counts.
+static int mb_velocity_solve(fg_mb_state* s, const fg_mb_step_options* opt, int no, int* m, const mb_real* dt_B, hipStream_t st) {
+    const int B = s->B, N = s->N, d = s->d;
+    // initial guess: zero on the first non-orthogonal pass, the previous pass's result after that (x = None if no_step == 0
+    // or not advect_non_ortho_reuse_result, PISOtorch_simulation.py:1735-1742; tests/golden/reference_split_step.json);
+    // fg_mb_set_advection_start(1): the current velocity on the first pass (opt-in)
+    int vrc = FG_OK, jac = 0;
+    const int start_x0 = (no > 0 || s->adv_from_result) ? 1 : 0;
+    // policy advection_jacobi: the sweeps first (mb_jacobi); what they do not settle goes to BiCGStab from a cleared start vector
+    if (s->adv_jacobi && s->jac_res_pinned) {
+        vrc = mb_jacobi(s, dt_B, s->Cdiag, s->Coff, s->rhs, s->ures, d, opt->advection_tol, start_x0, m, st, no & 3, &jac);
+        if (jac == 1) s->jac_solves += 1;
+        else if (jac >= 2) s->jac_fallbacks += 1;
+    }
+    if (jac != 1)      // (after sweeps that gave up: from their last iterate when it is finite -- closer than either start vector)
+        vrc = mb_bicgstab(s, dt_B, s->Cdiag, s->Coff, s->rhs, s->ures, d, opt->advection_tol,
+                          opt->max_iterations, jac == 2 ? 0 : (jac == 3 ? 1 : start_x0), m, st, {0, 0, MB_PRE_NONE, no & 3});
+    // ---- the reference's retry ladder (_linear_solve, PISOtorch_diff.py:410-476).  The advection solve runs without
+    // returnBestResult, so "not solved" = any system unconverged (or non-finite); every rung starts from zero
+    // ("do not start with a possibly corrupted result tensor", :429-431)
+    auto v_failed = [](int rc) { return rc == FG_ERR_NOT_FINITE || rc == FG_ERR_NOT_CONVERGED; };
+    if ((s->ladder_force & 1) && vrc == FG_OK) vrc = FG_ERR_NOT_CONVERGED;
+    if (v_failed(vrc) && opt->solver_double_fallback) {   // fp64 rung: fp64 iterate, residual b - C x recomputed in fp64
+        ++s->ladder[0];
+        vrc = mb_bicgstab(s, dt_B, s->Cdiag, s->Coff, s->rhs, s->ures, d, opt->advection_tol, opt->max_iterations, 0, m, st, {0, 1});
+        if ((s->ladder_force & 4) && vrc == FG_OK) vrc = FG_ERR_NOT_CONVERGED;
+    }
+    if (v_failed(vrc) && opt->bicg_precondition_fallback) {
+        ++s->ladder[1];
+        if (s->dbg_rung_ilu && !FG_MB_F64 && mb_ilu_prepare(s)) {
+            // preconditioned rung as in the reference: BiCGStab right-preconditioned by ILU(0) of the matrix
+            vrc = mb_bicgstab(s, dt_B, s->Cdiag, s->Coff, s->rhs, s->ures, d, opt->advection_tol, opt->max_iterations, 0, m, st, {0, 0, MB_PRE_ILU});
+        } else {   // meshes the schedule does not cover, the fp64 build: right diagonal scaling, (C D^-1) y = b, x = D^-1 y
+            const dim3 blk(FG_BLOCK), gn((N + FG_BLOCK - 1) / FG_BLOCK, B);
+            MB_DISPATCH(s, hipLaunchKernelGGL(k_mb_scale_cols<DIMS>, gn, blk, 0, st, s->dev, dt_B, s->Cdiag, s->Coff, s->Sdiag, s->Soff););
+            vrc = mb_bicgstab(s, dt_B, s->Sdiag, s->Soff, s->rhs, s->ures, d, opt->advection_tol, opt->max_iterations, 0, m, st);
+            hipLaunchKernelGGL(k_mb_unscale, dim3((N + FG_BLOCK - 1) / FG_BLOCK, B * d), blk, 0, st, N, d, dt_B, (const mb_real*)s->Cdiag, s->ures);
+        }
+    }
+    return vrc;
+}
+
+// One pressure solve (non-orthogonal pass `ps` of corrector `c`; matrix and right-hand side are assembled, the start vector sits in
+// s->pres when `warm`): CG or BiCGStab as the options say, the cold repeat of a warm start, and the retry ladder.
+static int mb_pressure_solve(fg_mb_state* s, const fg_mb_step_options* opt, int c, int ps, int warm, int* m, const mb_real* dt_B, hipStream_t st) {
+    auto solve = [&](int use_x0, int force_cg = 0) {
+        return (opt->pressure_use_bicgstab && !force_cg)
+                   ? mb_pressure_bicgstab(s, dt_B, opt->pressure_tol, opt->max_iterations, use_x0, m, st, opt->pressure_project_mean,
+                                          opt->pressure_use_bicgstab == 2, 4 + 4 * (c & 1) + (ps & 3))
+                   : mb_cg(s, dt_B, s->Pdiag, s->Poff, s->div, s->pres, opt->pressure_tol, opt->max_iterations, use_x0,
+                           opt->pressure_project_mean, opt->pressure_stall_accept, m, st);
+    };
+    int prc = solve(warm);
+    if ((s->ladder_force & 2) && prc == FG_OK) prc = FG_ERR_NOT_FINITE;
+    // a warm-started solve that ends unconverged falls back to the reference's start from zero
+    if (prc == FG_ERR_NOT_CONVERGED && ps == 0 && warm) prc = solve(0);
+    // ---- retry ladder (PISOtorch_diff.py:410-476): pressure solves run with returnBestResult, so only a NON-FINITE
+    // residual counts as "not solved".  fp64 rung: the refined BiCGStab (fp64 iterate and residual) from zero -- the
+    // reference repeats CG in fp64, which on the non-symmetric matrix stalls exactly like fp32 CG
+    if (prc == FG_ERR_NOT_FINITE && opt->solver_double_fallback && opt->pressure_use_bicgstab != 2) {
+        ++s->ladder[2];
+        prc = mb_bicgstab(s, dt_B, s->Pdiag, s->Poff, s->div, s->pres, 1, opt->pressure_tol, opt->max_iterations, 0, m, st,
+                          {opt->pressure_project_mean, 1});
+    }
+    // BiCGStab keeps no best iterate: a solve of it that broke down or ran out of iterations is repeated with CG,
+    // which hands back its best iterate (last resort; the refined solver hands back its best refinement point itself)
+    if (opt->pressure_use_bicgstab && (prc == FG_ERR_NOT_FINITE || (prc == FG_ERR_NOT_CONVERGED && opt->pressure_use_bicgstab != 2))) {
+        ++s->ladder[3];
+        prc = solve(0, 1);
+    }
+    return prc;
 }
 
 extern "C" int fg_mb_piso_step(fg_mb_handle s, const mb_real* dt_B, const fg_mb_step_options* opt, int32_t* stats_host, void* stream) {
@@ -840,41 +908,7 @@ extern "C" int fg_mb_piso_step(fg_mb_handle s, const mb_real* dt_B, const fg_mb_
             FgRange range_vel("mb_velocity_solve");
             hipLaunchKernelGGL(k_mb_vrhs<DIMS>, gv, blk, 0, st, D, dt_B, nu, s->velocity, s->ures, s->bvel, s->fb, s->source, s->rhs);
             int m = 0;
-            // initial guess: zero on the first non-orthogonal pass, the previous pass's result after that (x = None if no_step == 0
-            // or not advect_non_ortho_reuse_result, PISOtorch_simulation.py:1735-1742; tests/golden/reference_split_step.json);
-            // fg_mb_set_advection_start(1): the current velocity on the first pass (opt-in)
-            int vrc = FG_OK, jac = 0;
-            const int start_x0 = (no > 0 || s->adv_from_result) ? 1 : 0;
-            // policy advection_jacobi: the sweeps first (mb_jacobi); what they do not settle goes to BiCGStab from a cleared start vector
-            if (s->adv_jacobi && s->jac_res_pinned) {
-                vrc = mb_jacobi(s, dt_B, s->Cdiag, s->Coff, s->rhs, s->ures, d, opt->advection_tol, start_x0, &m, st, no & 3, &jac);
-                if (jac == 1) s->jac_solves += 1;
-                else if (jac >= 2) s->jac_fallbacks += 1;
-            }
-            if (jac != 1)      // (after sweeps that gave up: from their last iterate when it is finite -- closer than either start vector)
-                vrc = mb_bicgstab(s, dt_B, s->Cdiag, s->Coff, s->rhs, s->ures, d, opt->advection_tol,
-                                  opt->max_iterations, jac == 2 ? 0 : (jac == 3 ? 1 : start_x0), &m, st, 0, 0, 0, no & 3);
-            // ---- the reference's retry ladder (_linear_solve, PISOtorch_diff.py:410-476).  The advection solve runs without
-            // returnBestResult, so "not solved" = any system unconverged (or non-finite); every rung starts from zero
-            // ("do not start with a possibly corrupted result tensor", :429-431)
-            auto v_failed = [](int rc) { return rc == FG_ERR_NOT_FINITE || rc == FG_ERR_NOT_CONVERGED; };
-            if ((s->ladder_force & 1) && vrc == FG_OK) vrc = FG_ERR_NOT_CONVERGED;
-            if (v_failed(vrc) && opt->solver_double_fallback) {   // fp64 rung: fp64 iterate, residual b - C x recomputed in fp64
-                ++s->ladder[0];
-                vrc = mb_bicgstab(s, dt_B, s->Cdiag, s->Coff, s->rhs, s->ures, d, opt->advection_tol, opt->max_iterations, 0, &m, st, 0, 1);
-                if ((s->ladder_force & 4) && vrc == FG_OK) vrc = FG_ERR_NOT_CONVERGED;
-            }
-            if (v_failed(vrc) && opt->bicg_precondition_fallback) {
-                ++s->ladder[1];
-                if (s->dbg_rung_ilu && !FG_MB_F64 && mb_ilu_prepare(s)) {
-                    // preconditioned rung as in the reference: BiCGStab right-preconditioned by ILU(0) of the matrix
-                    vrc = mb_bicgstab(s, dt_B, s->Cdiag, s->Coff, s->rhs, s->ures, d, opt->advection_tol, opt->max_iterations, 0, &m, st, 0, 0, 2);
-                } else {   // meshes the schedule does not cover, the fp64 build: right diagonal scaling, (C D^-1) y = b, x = D^-1 y
-                    hipLaunchKernelGGL(k_mb_scale_cols<DIMS>, gn, blk, 0, st, D, dt_B, s->Cdiag, s->Coff, s->Sdiag, s->Soff);
-                    vrc = mb_bicgstab(s, dt_B, s->Sdiag, s->Soff, s->rhs, s->ures, d, opt->advection_tol, opt->max_iterations, 0, &m, st);
-                    hipLaunchKernelGGL(k_mb_unscale, dim3((N + FG_BLOCK - 1) / FG_BLOCK, B * d), blk, 0, st, N, d, dt_B, (const mb_real*)s->Cdiag, s->ures);
-                }
-            }
+            const int vrc = mb_velocity_solve(s, opt, no, &m, dt_B, st);
             if (vrc == FG_ERR_NOT_FINITE) {
                 fg_set_error("fg_mb_piso_step: the velocity (BiCGStab) solve produced a non-finite residual");
                 mask_failed(d);   // solve_ok = False before CopyVelocityResultToBlocks (PISOtorch_simulation.py:1752-1757): state intact
@@ -900,31 +934,7 @@ extern "C" int fg_mb_piso_step(fg_mb_handle s, const mb_real* dt_B, const fg_mb_
                 const int warm = (ps > 0 || opt->pressure_warm_start) ? 1 : 0;
                 if (ps == 0 && warm)  // start from the pressure field (the previous solve's result, or a restored state)
                     hipLaunchKernelGGL(k_mb_copy, dim3((N + FG_BLOCK - 1) / FG_BLOCK, B), blk, 0, st, (size_t)N, dt_B, s->pressure, s->pres);
-                auto solve = [&](int use_x0, int force_cg = 0) {
-                    return (opt->pressure_use_bicgstab && !force_cg)
-                               ? mb_pressure_bicgstab(s, dt_B, opt->pressure_tol, opt->max_iterations, use_x0, &m, st, opt->pressure_project_mean,
-                                                      opt->pressure_use_bicgstab == 2, 4 + 4 * (c & 1) + (ps & 3))
-                               : mb_cg(s, dt_B, s->Pdiag, s->Poff, s->div, s->pres, opt->pressure_tol, opt->max_iterations, use_x0,
-                                       opt->pressure_project_mean, opt->pressure_stall_accept, &m, st);
-                };
-                int prc = solve(warm);
-                if ((s->ladder_force & 2) && prc == FG_OK) prc = FG_ERR_NOT_FINITE;
-                // a warm-started solve that ends unconverged falls back to the reference's start from zero
-                if (prc == FG_ERR_NOT_CONVERGED && ps == 0 && warm) prc = solve(0);
-                // ---- retry ladder (PISOtorch_diff.py:410-476): pressure solves run with returnBestResult, so only a NON-FINITE
-                // residual counts as "not solved".  fp64 rung: the refined BiCGStab (fp64 iterate and residual) from zero -- the
-                // reference repeats CG in fp64, which on the non-symmetric matrix stalls exactly like fp32 CG
-                if (prc == FG_ERR_NOT_FINITE && opt->solver_double_fallback && opt->pressure_use_bicgstab != 2) {
-                    ++s->ladder[2];
-                    prc = mb_bicgstab(s, dt_B, s->Pdiag, s->Poff, s->div, s->pres, 1, opt->pressure_tol, opt->max_iterations, 0, &m, st,
-                                      opt->pressure_project_mean, 1);
-                }
-                // BiCGStab keeps no best iterate: a solve of it that broke down or ran out of iterations is repeated with CG,
-                // which hands back its best iterate (last resort; the refined solver hands back its best refinement point itself)
-                if (opt->pressure_use_bicgstab && (prc == FG_ERR_NOT_FINITE || (prc == FG_ERR_NOT_CONVERGED && opt->pressure_use_bicgstab != 2))) {
-                    ++s->ladder[3];
-                    prc = solve(0, 1);
-                }
+                const int prc = mb_pressure_solve(s, opt, c, ps, warm, &m, dt_B, st);
                 if (prc == FG_ERR_NOT_FINITE) {
                     fg_set_error("fg_mb_piso_step: the pressure solve produced a non-finite residual");
                     mask_failed(1);
@@ -1239,8 +1249,9 @@ extern "C" int fg_mb_solver_hints(fg_mb_handle s, int32_t* hints48, int32_t set)
     for (int k = 0; k < 4; ++k) { if (set) *trial[k] = hints48[32 + k]; else hints48[32 + k] = *trial[k]; }
     // the velocity sweeps' back-off (mb_jacobi): whether a solve goes through the sweeps or straight to BiCGStab
     for (int k = 0; k < 4; ++k) {
-        if (set) { s->jac_skip[k] = hints48[36 + k]; s->jac_fails[k] = hints48[40 + k]; s->jac_sweeps[k] = hints48[44 + k]; }
-        else { hints48[36 + k] = s->jac_skip[k]; hints48[40 + k] = s->jac_fails[k]; hints48[44 + k] = s->jac_sweeps[k]; }
+        FgJacHist& H = s->jac_hist[k];
+        if (set) { H.skip = hints48[36 + k]; H.fails = hints48[40 + k]; H.sweeps = hints48[44 + k]; }
+        else { hints48[36 + k] = H.skip; hints48[40 + k] = H.fails; hints48[44 + k] = H.sweeps; }
     }
     return FG_OK;
 }
@@ -1496,7 +1507,7 @@ extern "C" int fg_mb_set_stall_limit(fg_mb_handle s, int32_t iterations) {
 extern "C" int fg_mb_set_advection_jacobi(fg_mb_handle s, int on) {
     FG_REQUIRE(s != nullptr, FG_ERR_INVALID_ARG, "fg_mb_set_advection_jacobi: null handle");
     if (!s->adv_jacobi_env) s->adv_jacobi = on ? 1 : 0;      // (FG_ADV_JACOBI in the environment wins: A/B runs of whole envs)
-    for (int k = 0; k < 4; ++k) { s->jac_sweeps[k] = 0; s->jac_skip[k] = 0; s->jac_fails[k] = 0; }
+    for (int k = 0; k < 4; ++k) s->jac_hist[k] = FgJacHist{0, 0, 0};
     return FG_OK;
 }
 extern "C" int fg_mb_advection_jacobi_counts(fg_mb_handle s, int64_t* out2) {
