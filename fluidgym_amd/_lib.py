@@ -251,6 +251,8 @@ SIGNATURES = {
     "fg_mb_cell_moments_widths": (c_int, [c_void_p, c_void_p, c_int64, POINTER(c_int64), c_int32, c_void_p, c_void_p, POINTER(c_int32)]),
     "fg_plane_spectra": (c_int, [POINTER(c_void_p), POINTER(c_int64), c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_int32), c_int32,
                                  c_void_p, c_void_p, c_void_p]),
+    "fg_plane_histogram": (c_int, [POINTER(c_void_p), POINTER(c_int64), c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_int32), c_int32,
+                                   c_void_p, c_void_p, c_int32, POINTER(c_int32), c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "fg_coherence_litmus": (c_int, [c_int32, c_int32, c_int32, c_int32, POINTER(c_int64), POINTER(ctypes.c_double), c_void_p]),
     "fg_profile_enable": (c_int, [c_void_p, c_int]),
     "fg_profile_kinds": (c_int, []),

@@ -7,7 +7,9 @@ planes (``simulation/plane_spectra.PlaneSpectra``; the reference's ``PSD_planes`
 (``simulation/plane_budgets.PlaneBudgets``; the reference's ``TurbulentEnergyBudgetsOnlineParallel_Torch``,
 ``TCF_tools.py:438-443, 1512-1516``), and ``start_flow_time_correlation`` / ``stop_flow_time_correlation`` for the temporal two-point
 correlations of the planes (``simulation/plane_timecorr.PlaneTimeCorrelation``; the reference's
-``TemporalTwoPointCorrelation_Online_torch``, ``TCF_tools.py:431-436, 1508-1511``).
+``TemporalTwoPointCorrelation_Online_torch``, ``TCF_tools.py:431-436, 1508-1511``), and ``start_flow_histograms`` /
+``stop_flow_histograms`` for the PDFs and joint PDFs of chosen rows (``simulation/plane_hist.PlaneHistograms``; the reference records
+no distributions).
 
 The multi-block envs (cylinder, airfoil) have no homogeneous plane; ``FieldStatisticsMixin`` gives them ``start_field_statistics`` /
 ``stop_field_statistics``: the time-averaged fields per cell, in 3-D averaged over the span as well
@@ -21,6 +23,7 @@ import numpy as np
 
 from ..simulation.cell_moments import CellMoments
 from ..simulation.plane_budgets import PlaneBudgets
+from ..simulation.plane_hist import CHANNEL_ORDER, PlaneHistograms
 from ..simulation.plane_spectra import PlaneSpectra, check_extents
 from ..simulation.plane_stats import CHANNEL_SETS, PlaneMoments
 from ..simulation.plane_timecorr import PlaneTimeCorrelation
@@ -60,6 +63,9 @@ class FlowStatisticsMixin:
     _flow_timecorr: Optional[PlaneTimeCorrelation] = None   # None (the default): the step path does nothing for the correlations
     _flow_timecorr_every: int = 1
     _flow_timecorr_tick: int = 0
+    _flow_hist: Optional[PlaneHistograms] = None    # None (the default): the step path does nothing for the histograms
+    _flow_hist_every: int = 1
+    _flow_hist_tick: int = 0
 
     def start_flow_statistics(self, order: int = 2, every: int = 1) -> None:
         """Start a fresh record of moments up to ``order``; a sample is taken after every ``every``-th sim step of ``step()``."""
@@ -172,6 +178,52 @@ class FlowStatisticsMixin:
         corr = self._flow_timecorr
         corr.update(blk.velocity, blk.pressure if "p" in corr.channels else None,
                     blk.passiveScalar if "T" in corr.channels else None, time=self._sim.total_time)
+
+    def start_flow_histograms(self, ranges=None, bins: int = 128, joint: Sequence = (), joint_bins: int = 32,
+                              rows: Optional[Sequence[int]] = None, channels: Optional[Sequence[str]] = None, every: int = 1) -> None:
+        """Start a fresh record of the histograms of ``channels`` (default: those of the moments; any of ``u, v, w, p, T`` in that
+        order) over the rows ``rows`` (default: all) and of the joint histograms of the channel pairs ``joint``; a sample is taken
+        after every ``every``-th sim step of ``step()``.  ``ranges`` maps a channel to ``(lo, hi)`` or to ``[n_rows, 2]``; None takes,
+        per listed row and channel, the minimum and maximum over the batch of the current state, widened by half the span on each
+        side (by 1 where the span is zero)."""
+        _check_start(self, "start_flow_histograms", every, "flow histograms")
+        channels = self._flow_channels() if channels is None else tuple(channels)
+        blk = self._domain.getBlock(0)
+        if any(c not in CHANNEL_ORDER for c in channels) or ("w" in channels and self._ndims != 3):
+            raise ValueError(f"channels must be names from {CHANNEL_ORDER} that fit the {self._ndims}-D domain, got {channels}")
+        if "T" in channels and not blk.hasPassiveScalar():
+            raise ValueError("start_flow_histograms: channel T needs a domain with a passive scalar")
+        ny = int(blk.velocity.shape[-2])
+        if rows is not None and (len(rows) < 1 or min(rows) < 0 or max(rows) >= ny):
+            raise ValueError(f"rows must lie in [0, {ny}), got {list(rows)}")
+        if ranges is None:
+            src = {"u": (blk.velocity, 0), "v": (blk.velocity, 1), "w": (blk.velocity, 2), "p": (blk.pressure, 0),
+                   "T": (blk.passiveScalar, 0)}
+            listed = list(range(ny)) if rows is None else [int(r) for r in rows]
+            ranges = {}
+            for c in channels:
+                t, comp = src[c]
+                f = t[:, comp].double().movedim(-2, 0)[listed].flatten(1)               # [R, B * nz * nx]
+                lo, hi = f.amin(dim=1).cpu().numpy(), f.amax(dim=1).cpu().numpy()
+                pad = np.where(hi > lo, 0.5 * (hi - lo), 1.0)
+                ranges[c] = np.stack([lo - pad, hi + pad], axis=1)
+        self._flow_hist = PlaneHistograms(channels, ranges, bins, joint, joint_bins, rows)
+        self._flow_hist_every, self._flow_hist_tick = int(every), 0
+
+    def stop_flow_histograms(self) -> PlaneHistograms:
+        """Stop recording and hand out the record (on the GPU; its accessors, ``pooled()`` and ``save`` read it back)."""
+        if self._flow_hist is None:
+            raise RuntimeError("stop_flow_histograms: no histograms are being recorded")
+        hist, self._flow_hist = self._flow_hist, None
+        return hist
+
+    def _record_histogram_sample(self) -> None:
+        """Called after a sim step while histograms are active."""
+        if not _due(self, "_flow_hist"):
+            return
+        blk = self._domain.getBlock(0)
+        hist = self._flow_hist
+        hist.update(blk.velocity, blk.pressure if "p" in hist.channels else None, blk.passiveScalar if "T" in hist.channels else None)
 
 
 class FieldStatisticsMixin:

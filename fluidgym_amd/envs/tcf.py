@@ -376,6 +376,8 @@ class TCF3DBottomEnv(FlowStatisticsMixin, FluidEnv):
                 self._record_budgets_sample()
             if self._flow_timecorr is not None:
                 self._record_time_correlation_sample()
+            if self._flow_hist is not None:
+                self._record_histogram_sample()
             tb.append(b)
             tt.append(t)
         tau_bottom, tau_top = torch.stack(tb).mean(dim=0), torch.stack(tt).mean(dim=0)

@@ -634,6 +634,40 @@ int fg_plane_budgets(const fg_real* const* fields, const int64_t* batch_stride, 
  * outside [0, ny), a non-positive extent, a batch stride below nz * ny * nx, batch * K * n_planes above 2^31 - 1. */
 int fg_plane_spectra(const fg_real* const* channels, const int64_t* batch_stride, int32_t K, int32_t batch, int32_t nz, int32_t ny,
                      int32_t nx, const int32_t* planes, int32_t n_planes, double* amp, double* power, void* stream);
+/* ---- online PDFs and joint PDFs of wall-parallel planes (csrc/fg_planehist.hip; both libraries, handle-free) ---------------------
+ * One sample of PlaneHistograms (simulation/plane_hist.py; the reference records no distributions): for every listed row
+ * (env, rows[r]) the histogram over (z, x) of each of K channels and the joint histogram of each listed channel pair, ADDED to
+ * running 64-bit counters, in one launch per 256 listed rows.
+ *   channels, batch_stride, K   as for fg_plane_moments (HOST tables, copied into the kernel arguments), K = 1..5
+ *   rows             HOST table of n_rows = 1..ny row indices in [0, ny), ascending and unique, copied into the kernel arguments
+ *   lo, scale        DEVICE arrays [n_rows][K] of fg_real: the lower edge of row r, channel k and bins / (hi - lo)
+ *   bins             2..256.  The slot of a value v, evaluated in fg_real with two separately rounded operations (the file is compiled
+ *                    with -ffp-contract=off):  t = (v - lo[r][k]) * scale[r][k];  slot = bins + 2 if v is NaN, 0 if !(t >= 0) (below
+ *                    the range, -inf), bins + 1 if t >= bins (at or above the upper edge, +inf), 1 + (int)t otherwise.  t is compared
+ *                    as a real before the conversion.
+ *   pairs            HOST table [n_pairs][2] of channel indices in [0, K), n_pairs = 0..6; (k, k) is allowed
+ *   joint_bins       2..64, a divisor of bins.  A cell whose slots a, b of a pair are both in 1..bins adds one to element
+ *                    ja * joint_bins + jb of the pair's slab, j = (slot - 1) / (bins / joint_bins); any other cell adds one to the
+ *                    slab's last element ("outside").  The joint table is consistent with the marginals by construction.
+ *   counts           DEVICE [batch][n_rows][K][bins + 3]: slot 0 below, 1..bins the bins, bins + 1 above, bins + 2 NaN
+ *   joint            DEVICE [batch][n_rows][n_pairs][joint_bins^2 + 1]; NULL exactly when n_pairs == 0
+ * The caller zeroes both arrays before the first sample and counts the samples itself, so that merging two records is an addition.
+ * Ownership and loads are those of fg_plane_moments (one workgroup, or one wave for planes of up to 1024 cells, per listed row; 16-byte
+ * loads under the same conditions).  The sample's histograms are 32-bit counters in LDS, filled with LDS integer atomics; every
+ * non-zero one is then added to its global counter by a plain load and store of the row's single owner: every update is an integer
+ * addition, no global atomic exists, a row's result depends only on its cells and the tables and repeats bit for bit.  A non-finite
+ * cell goes to its slot and harms nothing else; rows and envs that are not listed are not written.  Asynchronous on `stream`; nothing
+ * returns to the host.
+ * FG_ERR_UNSUPPORTED (before any launch): the counters of a row, K (bins + 3) + n_pairs (joint_bins^2 + 1) words of 4 bytes, do not
+ * fit in 160 KB of LDS -- four rows share a workgroup's LDS when the plane has up to 1024 cells, so there 16 bytes per word count.
+ * K = 5, bins = 256, n_pairs = 3 fits with joint_bins = 64 for larger planes and with joint_bins = 32 for those.
+ * FG_ERR_INVALID_ARG (before any launch): a null pointer or joint != NULL disagreeing with n_pairs, K outside 1..5, bins outside 2..256,
+ * joint_bins outside 2..64 or not a divisor of bins, n_pairs outside 0..6, a pair index outside [0, K), n_rows outside 1..ny, rows not
+ * ascending and unique or outside [0, ny), a non-positive extent, a batch stride below nz * ny * nx, nz * nx above 2^30 or
+ * batch * n_rows above 2^31 - 1. */
+int fg_plane_histogram(const fg_real* const* channels, const int64_t* batch_stride, int32_t K, int32_t batch, int32_t nz, int32_t ny,
+                       int32_t nx, const int32_t* rows, int32_t n_rows, const fg_real* lo, const fg_real* scale, int32_t bins,
+                       const int32_t* pairs, int32_t n_pairs, int32_t joint_bins, uint64_t* counts, uint64_t* joint, void* stream);
 int fg_profile_enable(fg_handle h, int on);
 int fg_profile_kinds(void);
 const char* fg_profile_kind_name(int kind);
