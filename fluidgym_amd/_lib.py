@@ -106,6 +106,26 @@ class FgFrameSpec(Structure):
     ]
 
 
+class FgRenderCamera(Structure):
+    """The affine ray generator of ``fg_render_isosurface`` / ``fg_render_volume`` in index space (``fg_render_camera``): pixel
+    ``(i, j)`` has the origin ``o0 + (j + 1/2) ou + (i + 1/2) ov`` and the direction ``d0 + (j + 1/2) du + (i + 1/2) dv``."""
+    _fields_ = [(name, ctypes.c_float * 3) for name in ("o0", "ou", "ov", "d0", "du", "dv")]
+
+
+class FgRenderOptions(Structure):
+    """Step, headlight, clip box and the two fixed colours of the ray marcher (``fg_render_options``)."""
+    _fields_ = [
+        ("step", ctypes.c_float),
+        ("ambient", ctypes.c_float),
+        ("diffuse", ctypes.c_float),
+        ("has_clip", c_int32),
+        ("clip_lo", ctypes.c_float * 3),
+        ("clip_hi", ctypes.c_float * 3),
+        ("body_color", ctypes.c_uint8 * 4),
+        ("background", ctypes.c_uint8 * 4),
+    ]
+
+
 class FgStepOptions(Structure):
     _fields_ = [
         ("corrector_steps", c_int32),
@@ -267,6 +287,12 @@ SIGNATURES = {
     "fg_resample": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
     "fg_frame_colorize": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(FgFrameSpec), c_void_p, c_void_p, c_void_p,
                                   POINTER(c_int32), c_int32, c_void_p, c_void_p]),
+    "fg_render_isosurface": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32,
+                                     c_void_p, c_void_p, c_void_p, POINTER(FgRenderCamera), POINTER(FgRenderOptions), c_int32, c_int32,
+                                     POINTER(c_int32), c_int32, c_void_p, c_void_p, c_void_p]),
+    "fg_render_volume": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                 POINTER(FgRenderCamera), POINTER(FgRenderOptions), c_int32, c_int32, POINTER(c_int32), c_int32, c_void_p,
+                                 c_void_p]),
     "fg_envglue_jet_schedule": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "fg_envglue_channel_observe": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_void_p,
                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -360,7 +386,7 @@ _F64_STRUCTS[FgMbSimOptions] = _f64_struct(FgMbSimOptions)
 FgStepOptionsF64, FgSimOptionsF64 = _F64_STRUCTS[FgStepOptions], _F64_STRUCTS[FgSimOptions]
 FgMbStepOptionsF64, FgMbSimOptionsF64 = _F64_STRUCTS[FgMbStepOptions], _F64_STRUCTS[FgMbSimOptions]
 _F64_KEEP_FLOAT = ("fg_set_fd_preconditioner", "fg_set_fd_fast_transform", "fg_set_fd_helmholtz", "fg_coords_to_transforms", "fg_stream_triad")
-_F64_ABSENT_PREFIXES = ("fg_resampl", "fg_sparse_", "fg_envglue_", "fg_frame_")
+_F64_ABSENT_PREFIXES = ("fg_resampl", "fg_sparse_", "fg_envglue_", "fg_frame_", "fg_render_")
 
 
 def _f64_type(tp):

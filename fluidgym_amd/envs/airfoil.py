@@ -42,6 +42,7 @@ AIRFOIL_2D_DEFAULT_CONFIG = {
 }
 JET_CENTERS = (0.2, 0.4, 0.6)   # grid.py:14-15
 JET_WIDTH = 0.08
+VORTICITY_RENDER_LEVELS = {1000: 2.0, 3000: 3.5, 5000: 4.5}   # airfoil_env_3d.py:21-25: level of the 3-D picture, by Reynolds number
 VORTICITY_RENDER_RANGE = {1000: (-10, 10), 3000: (-12.5, 12.5), 5000: (-15, 15)}   # airfoil_env_base.py:38-42, by Reynolds number
 
 
@@ -353,6 +354,13 @@ class AirfoilEnvBase(CylinderEnvBase):
         if re not in VORTICITY_RENDER_RANGE:
             raise ValueError(f"no vorticity colour range for Reynolds number {re}: the table has {sorted(VORTICITY_RENDER_RANGE)}")
         return self._vortex_frame_specs(VORTICITY_RENDER_RANGE[re], True, (None, None, None))
+
+    def _frame_specs_3d(self):
+        """airfoil_env_3d.py:489-520; the section's mask, repeated along the span, is the solid body."""
+        solid = self.__dict__.get("_frame_masks", {}).get("xyz")
+        if solid is None:             # built once: the repeated mask is as large as a channel of the render grid
+            solid = self._frame_mask("xyz", np.repeat(np.asarray(self._airfoil_mask)[None, :, :], self.render_shape[2], axis=0))
+        return self._vortex_frame_specs_3d(VORTICITY_RENDER_LEVELS, 0, solid, (self.L + 1.5, self.H, self.D))
 
 
 class AirfoilEnv2D(AirfoilEnvBase):

@@ -42,6 +42,8 @@ CYLINDER_ROT_2D_DEFAULT_CONFIG = dict(CYLINDER_JET_2D_DEFAULT_CONFIG)
 
 ONCHIP_PCG_MAX_CELLS = 24 * 1024   # the multilevel-preconditioned on-chip CG (2-D): fg_mb_onchip.hip OC_L2_CELLS
 
+VORTICITY_RENDER_LEVELS = {100: 1.5, 250: 2.5, 500: 3.5}   # jet_cylinder_env_3d.py:15-19: level of the 3-D picture, by Reynolds number
+
 
 class CylinderEnvBase(FieldStatisticsMixin, FlowStatisticsMixin, FluidEnv):      # (multi-block: the plane statistics refuse with
                                                                                  # NotImplementedError, the per-cell ones record)
@@ -276,6 +278,26 @@ class CylinderEnvBase(FieldStatisticsMixin, FlowStatisticsMixin, FluidEnv):     
         else:
             masks = (self._frame_mask("xy", m[0]), self._frame_mask("xz", m[:, 0, :]), self._frame_mask("yz", m[:, :, 0]))
         return self._vortex_frame_specs((-10, 10), False, masks)
+
+    def _vortex_frame_specs_3d(self, levels: dict, clip_x: int, solid, extent) -> Dict[str, dict]:
+        """The 3-D picture the cylinder and airfoil envs share (jet_cylinder_env_3d.py:511-546, airfoil_env_3d.py:489-520): the
+        surface of the vorticity magnitude at the level of the Reynolds number, coloured by the speed, ``rainbow``, the body as a
+        solid, elev 10, azim 60.  The reference zeroes the vorticity in front of ``clip_x`` and in the 15 outermost rows of y: the
+        clip box here."""
+        re = int(self._reynolds_number)
+        if re not in levels:
+            raise ValueError(f"no vorticity level for Reynolds number {re}: the table has {sorted(levels)}")
+        w, u = self.get_vorticity(), self.get_velocity()
+        nz, ny, nx = (int(v) for v in w.shape[2:])
+        return {"3d_vorticity": dict(mode="iso", view=w, channel=-1, level=levels[re], color_view=u, color_channel=-1,
+                                     color_range=self._speed_range_3d(u), cmap="rainbow",
+                                     clip=((clip_x, 15, 0), (nx - 1, ny - 16, nz - 1)), solid=solid, extent=extent, elev=10, azim=60)}
+
+    def _frame_specs_3d(self):
+        m = self.__dict__.get("_cylinder_mask")
+        if m is None:
+            m = self._cylinder_mask = self._get_cylinder_mask()
+        return self._vortex_frame_specs_3d(VORTICITY_RENDER_LEVELS, 20, self._frame_mask("xyz", m), (self.L, self.H, self.H))
 
     def _get_drag_and_lift(self):
         """[B] in 2-D; [B, NZ] per spanwise layer in 3-D (face area = edge length x D / resolution, :676-689)."""

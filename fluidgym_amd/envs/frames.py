@@ -347,8 +347,10 @@ class FrameRecorder:
     """The device-to-host side of a recording: every sample is copied into pinned memory asynchronously, behind the kernel on the
     stream that drew it; ``finish`` waits once and stacks."""
 
-    def __init__(self, envs: Sequence[int], every: int, fps: int):
+    def __init__(self, envs: Sequence[int], every: int, fps: int, size_3d: Optional[Tuple[int, int]] = None):
+        """``size_3d``: ``(H, W)`` of the 3-D keys a recording with ``render_3d=True`` adds to every sample, or None."""
         self.envs = [int(e) for e in envs]
+        self.size_3d = None if size_3d is None else (int(size_3d[0]), int(size_3d[1]))
         self.every, self.tick, self.fps = int(every), 0, int(fps)
         self.steps: list = []
         self.samples: Dict[str, list] = {}

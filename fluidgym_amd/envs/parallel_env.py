@@ -352,6 +352,33 @@ class ParallelFluidEnv:
     def render(self, save: bool = False, render_3d: bool = False, filename: Optional[str] = None, output_path: Any = None):
         raise NotImplementedError("Rendering is not implemented for ParallelFluidEnv.")      # parallel_env.py:289-319
 
+    # ---- frames (envs/frames.py, envs/render3d.py): drawn by the lane that owns the env, handed back as its tensors
+    def _lane_frames(self, method: str, envs, **kw) -> Dict[str, torch.Tensor]:
+        lanes = self.lane_envs
+        n_lane = self._n_local // len(lanes)
+        chosen = list(range(self._n_local)) if envs is None else [int(e) for e in np.asarray(envs).reshape(-1)]
+        if not chosen or min(chosen) < 0 or max(chosen) >= self._n_local:
+            raise ValueError(f"envs must name at least one env of this rank's batch [0, {self._n_local}), got {chosen}")
+        parts, order = [], []
+        for l, env in enumerate(lanes):
+            at = [k for k, e in enumerate(chosen) if e // n_lane == l]
+            if at:
+                parts.append(getattr(env, method)(envs=[chosen[k] - l * n_lane for k in at], **kw))
+                order += at
+        from .frames import env_index_tensor
+
+        back = env_index_tensor(np.argsort(np.asarray(order)), self._device)       # uploaded once per distinct list and kept
+        return {key: torch.cat([p[key] for p in parts], dim=0).index_select(0, back) for key in parts[0]}
+
+    def render_frames(self, envs=None, cmap=None) -> Dict[str, torch.Tensor]:
+        """``FluidEnv.render_frames`` for the envs ``envs`` of this rank's batch (indices into it; default: all, in order): every
+        lane draws the envs it owns, the frames come back in the order asked for, on this rank's device."""
+        return self._lane_frames("render_frames", envs, cmap=cmap)
+
+    def render_frames_3d(self, envs=None, size=(480, 640), view=None, cmap=None, projection: str = "persp") -> Dict[str, torch.Tensor]:
+        """``FluidEnv.render_frames_3d`` for the envs ``envs`` of this rank's batch, as ``render_frames``."""
+        return self._lane_frames("render_frames_3d", envs, size=size, view=view, cmap=cmap, projection=projection)
+
     @property
     def num_envs(self) -> int:
         return self._n_total

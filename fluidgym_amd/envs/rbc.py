@@ -336,6 +336,17 @@ class RBCEnvBase(FlowStatisticsMixin, FluidEnv):
         rng = (self._T_cold, self._T_hot + self._heater_limit)
         return {key: (T, spec, rng, "rainbow", None) for key, spec in rbc_frame_specs(self._ndims, T.shape[2:]).items()}
 
+    def _frame_specs_3d(self):
+        """rbc_env_3d.py:511-527: the temperature as a volume between ``T_cold`` and ``T_hot + heater_limit``, ``rainbow``, the
+        opacity of a sample the reference's ``log1p`` of the normalised value (``render3d.log_opacity_table``), elev 15, azim 45; the
+        box has the proportions of the render grid, as ``set_box_aspect(field.shape)`` gives it there."""
+        from .render3d import log_opacity_table
+
+        T = self.get_temperature().unsqueeze(1)
+        return {"3d_temperature": dict(mode="volume", view=T, channel=0, range=(self._T_cold, self._T_hot + self._heater_limit),
+                                       cmap="rainbow", opacity=log_opacity_table(), extent=tuple(float(v) for v in self.render_shape),
+                                       elev=15, azim=45)}
+
     def _get_global_obs(self):
         """rbc_env_2d.py:175-194 / rbc_env_3d.py:291-330 with a leading env axis."""
         B, d = self._num_envs, self._ndims

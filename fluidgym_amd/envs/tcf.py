@@ -64,6 +64,7 @@ SMALL_TCF_3D_DEFAULT_CONFIG = {
     "differentiable": False,
 }
 VELOCITY_MAX = 0.9      # upper end of the speed pictures: tcf_env.py:49-60 holds this one value for every (D, Re_wall) it lists
+Q_CRITERION_ISO = 0.05   # level of the 3-D picture: tcf_env.py:36-47 holds this one value for every (D, Re_wall) it lists
 LARGE_TCF_3D_DEFAULT_CONFIG = {**SMALL_TCF_3D_DEFAULT_CONFIG, "resolution_x_z": 128, "L": 2 * np.pi, "D": np.pi}
 
 
@@ -423,6 +424,26 @@ class TCF3DBottomEnv(FlowStatisticsMixin, FluidEnv):
         for key, spec in tcf_frame_specs(u.shape[2:], self._frame_wall_row()).items():
             out[key] = (u, spec, (0.0, VELOCITY_MAX), "viridis", None) if key.endswith("velocity") else (w, spec, w_range, "icefire", None)
         return out
+
+    def _frame_specs_3d(self):
+        """tcf_env.py:753-778: the surface ``|Q| = Q_CRITERION_ISO`` between the bottom wall and y+ = 150, coloured by the speed in
+        (0, ``VELOCITY_MAX``), ``rainbow``, seen from elev 15, azim 60.  The views of this env are on the wall-refined simulation
+        grid, which would stretch the picture: Q and the velocity are resampled onto ``render_shape`` for this path only (the
+        resampler is created on first use).  The reference crops its arrays at ``y_shape_idx``; here that is the clip box, inside
+        the box of the whole channel.  (The reference colours with the x- and y-flipped speed of its slices; the speed is taken
+        unflipped here, at the cell of the hit.)"""
+        rs = self.__dict__.get("_render3d_resampler")
+        if rs is None:
+            from ..simulation.resample import UniformResampler
+
+            rs = self._render3d_resampler = UniformResampler(self._block.edges, self.render_shape, fill_max_steps=16, device=self._cuda_device)
+        q, u = rs(self.get_q_criterion()), rs(self.get_velocity())
+        nz, ny, nx = (int(v) for v in q.shape[2:])
+        y_shape_idx = round((self._y_wall_to_y(150) + self._delta) / self._H * self.render_shape[1])
+        top = min(max(y_shape_idx - 1, 1), ny - 1)
+        return {"3d_q_criterion": dict(mode="iso", view=q, channel=0, level=Q_CRITERION_ISO, color_view=u, color_channel=-1,
+                                       color_range=(0.0, VELOCITY_MAX), cmap="rainbow", clip=((0, 0, 0), (nx - 1, top, nz - 1)),
+                                       solid=None, extent=(self._L, self._H, self._D), elev=15, azim=60)}
 
     @property
     def id(self) -> str:

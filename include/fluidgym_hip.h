@@ -728,6 +728,53 @@ int fg_frame_colorize(const float* field, int32_t B, int32_t C, int32_t nz, int3
                       const uint8_t* table, const uint8_t* mask, const float* range, const int32_t* envs, int32_t n, uint8_t* out,
                       void* stream);
 
+/* ---- 3-D frames of the envs of a batch: ray-cast iso-surfaces and volumes (fp32 library only; csrc/fg_render3d.hip) ----------
+ * The reference's render(render_3d=True) (envs/util/visualization.py:211-475: marching cubes + Poly3DCollection, ax.voxels) as one ray
+ * marcher: one thread per pixel, 16 x 16 pixel tiles, one launch per 64 listed envs, nothing returns to the host, no atomics.
+ *   volume   device fp32 [B][C][nz][ny][nx], samples at the integer points of index space, the box [0, nx-1] x [0, ny-1] x [0, nz-1]
+ *   channel  >= 0: that channel; -1: the Euclidean norm over all C channels, formed as fg_frame_colorize forms it
+ *   camera   an affine ray generator in index space, (x, y, z) per vector: pixel (i, j) (row, column) has the origin
+ *            o0 + (j + 1/2) ou + (i + 1/2) ov and the direction d0 + (j + 1/2) du + (i + 1/2) dv (orthographic: du = dv = 0;
+ *            perspective: ou = ov = 0); the direction is not normalised, t counts in its units
+ *   options  step (in t; samples at t0 + s step), ambient and diffuse of the headlight ambient + diffuse |n.d| / (|n| |d|), the clip box
+ *            [clip_lo, clip_hi] of index space for the surface (has_clip != 0), body and background colour
+ *   table    device uint8 [256][3];  range: device fp32 [n][2] = (lo, span) of listed env i;  envs: HOST int32 [n], each in [0, B)
+ *   out      device uint8 [n][H][W][3]
+ * fg_render_isosurface: the first pair of consecutive samples, both inside the clip box, between which |f| - level changes sign, one
+ *   secant step, the analytic gradient of the trilinear interpolant as the normal, the colour of color_volume [B][color_C][nz][ny][nx]
+ *   at the cell the hit truncates to, normalised by range and looked up as fg_frame_colorize does; level: device fp32 [n]; solid:
+ *   device uint8 [nz][ny][nx] or NULL, a second level set at 1/2 along the whole ray, drawn in the body colour, the nearer hit wins;
+ *   depth: device fp32 [n][H][W] or NULL, t of the hit or +inf.
+ * fg_render_volume: front-to-back emission-absorption over the same samples: bin k of the normalised value, C += (1 - A) opacity[k]
+ *   table[k], A += (1 - A) opacity[k], stops once A > 0.99, the rest is the background; opacity: device fp32 [256], per step.
+ * The order of the float32 operations is written once at the top of csrc/fg_render3d.hip; the result is defined by it, bit for bit.
+ * Limits: a ray takes at most 65536 samples (s = 0 .. 65535): with a step below (path through the box) / 65535 the march ends before
+ *   the far side of the box, without an error.  The camera entries are checked one by one; a camera whose sums o0 + (j + 1/2) ou +
+ *   (i + 1/2) ov overflow float32 gives positions that are not numbers: such a sample reads cell 0, its value is NaN and crosses nothing.
+ * Before any launch (and without a GPU): FG_ERR_INVALID_ARG for a null argument, n < 1, an extent < 2, an env outside [0, B), a channel
+ * outside [-1, C), H or W < 1, a frame of 2^31 bytes or more, step <= 0, an empty clip box, a non-finite camera entry, d0 = 0. */
+typedef struct fg_render_camera {
+    float o0[3], ou[3], ov[3];
+    float d0[3], du[3], dv[3];
+} fg_render_camera;
+typedef struct fg_render_options {
+    float step;
+    float ambient;
+    float diffuse;
+    int32_t has_clip;
+    float clip_lo[3];
+    float clip_hi[3];
+    uint8_t body_color[4];      /* r, g, b, unused */
+    uint8_t background[4];      /* r, g, b, unused */
+} fg_render_options;
+int fg_render_isosurface(const float* volume, int32_t B, int32_t C, int32_t nz, int32_t ny, int32_t nx, int32_t channel,
+                         const float* level, const float* color_volume, int32_t color_C, int32_t color_channel, const float* range,
+                         const uint8_t* table, const uint8_t* solid, const fg_render_camera* camera, const fg_render_options* options,
+                         int32_t H, int32_t W, const int32_t* envs, int32_t n, uint8_t* out, float* depth, void* stream);
+int fg_render_volume(const float* volume, int32_t B, int32_t C, int32_t nz, int32_t ny, int32_t nx, int32_t channel, const float* range,
+                     const uint8_t* table, const float* opacity, const fg_render_camera* camera, const fg_render_options* options,
+                     int32_t H, int32_t W, const int32_t* envs, int32_t n, uint8_t* out, void* stream);
+
 /* ---- env glue either side of the n sim steps of an env step (fp32 library only) ------------------------------
  * fg_envglue_jet_schedule: the action smoothing of the reference's jet envs (cylinder_env_base.py:748-753, a_k = a_{k-1} +
  * alpha (target - a_{k-1}) before every sim step) for the n sim steps of one env step at once: control[k][b] = target[b] +
