@@ -126,6 +126,19 @@ class FgRenderOptions(Structure):
     ]
 
 
+class FgNoiseSegment(Structure):
+    """One tensor of a ``fg_obs_noise_add`` launch (``fg_noise_segment``): ``dst[r][i] = src[r][i] + sigma z``, strides in elements."""
+    _fields_ = [
+        ("src", c_void_p),
+        ("dst", c_void_p),
+        ("src_stride", c_int64),
+        ("dst_stride", c_int64),
+        ("n", c_int32),
+        ("tag", ctypes.c_uint32),
+        ("sigma", ctypes.c_double),
+    ]
+
+
 class FgStepOptions(Structure):
     _fields_ = [
         ("corrector_steps", c_int32),
@@ -293,6 +306,7 @@ SIGNATURES = {
     "fg_render_volume": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                                  POINTER(FgRenderCamera), POINTER(FgRenderOptions), c_int32, c_int32, POINTER(c_int32), c_int32, c_void_p,
                                  c_void_p]),
+    "fg_obs_noise_add": (c_int, [POINTER(FgNoiseSegment), c_int32, c_int32, c_int32, ctypes.c_uint64, c_void_p, c_void_p, c_void_p]),
     "fg_envglue_jet_schedule": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "fg_envglue_channel_observe": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_void_p,
                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -386,7 +400,7 @@ _F64_STRUCTS[FgMbSimOptions] = _f64_struct(FgMbSimOptions)
 FgStepOptionsF64, FgSimOptionsF64 = _F64_STRUCTS[FgStepOptions], _F64_STRUCTS[FgSimOptions]
 FgMbStepOptionsF64, FgMbSimOptionsF64 = _F64_STRUCTS[FgMbStepOptions], _F64_STRUCTS[FgMbSimOptions]
 _F64_KEEP_FLOAT = ("fg_set_fd_preconditioner", "fg_set_fd_fast_transform", "fg_set_fd_helmholtz", "fg_coords_to_transforms", "fg_stream_triad")
-_F64_ABSENT_PREFIXES = ("fg_resampl", "fg_sparse_", "fg_envglue_", "fg_frame_", "fg_render_")
+_F64_ABSENT_PREFIXES = ("fg_resampl", "fg_sparse_", "fg_envglue_", "fg_frame_", "fg_render_", "fg_obs_")
 
 
 def _f64_type(tp):

@@ -775,6 +775,33 @@ int fg_render_volume(const float* volume, int32_t B, int32_t C, int32_t nz, int3
                      const uint8_t* table, const float* opacity, const fg_render_camera* camera, const fg_render_options* options,
                      int32_t H, int32_t W, const int32_t* envs, int32_t n, uint8_t* out, void* stream);
 
+/* ---- counter-based Gaussian noise on observations / actions of a batch (fp32 library only; csrc/fg_obsnoise.hip) ----------
+ * dst[r][i] = src[r][i] + sigma z for every segment (one tensor of an observation dict each), row r < rows and element i < n, in ONE
+ * launch; z is normal number i % 4 of the Philox4x32-10 block with
+ *   key      (seed & 0xffffffff, seed >> 32)
+ *   counter  ((tag << 24) | (i / 4), row_id(r), counters[r][0], counters[r][1])
+ * so a row's noise is a pure function of (seed, row id, its episode and step words, tag, element): it does not depend on the batch around
+ * it, and the only state is the caller's counters.  The fp32 arithmetic that turns the words into z is written once at the top of
+ * csrc/fg_obsnoise.hip and defines the result bit for bit (tests/obs_noise_ref.py restates it in NumPy).
+ *   seg       HOST array of n_seg segments (copied into the kernel arguments): src, dst device pointers of `dtype`; src_stride, dst_stride
+ *             in elements between rows; n contiguous elements per row; tag < 256; sigma.  dst == src is allowed, any other overlap is not
+ *   dtype     0: float, dst = src + (float)sigma * z in fp32;  1: double, dst = src + sigma * (double)z in fp64 (an fp64 env's tensors go
+ *             through this entry of the fp32 library); z itself is always formed in fp32
+ *   counters  device uint32 [rows][2] = (episode, step);  row_ids: device int32 [rows], or NULL: row r is r
+ * Asynchronous on `stream`, no LDS, no atomics, nothing returns to the host.
+ * Before any launch (and without a GPU): FG_ERR_INVALID_ARG for a null seg / counters / src / dst, n_seg outside [1, 8], rows outside
+ * [1, 65535], an unknown dtype, n outside [1, 2^26], tag >= 256, a stride smaller than n. */
+typedef struct fg_noise_segment {
+    const void* src;
+    void* dst;
+    int64_t src_stride, dst_stride;
+    int32_t n;
+    uint32_t tag;
+    double sigma;
+} fg_noise_segment;
+int fg_obs_noise_add(const fg_noise_segment* seg, int32_t n_seg, int32_t rows, int32_t dtype, uint64_t seed,
+                     const uint32_t* counters, const int32_t* row_ids, void* stream);
+
 /* ---- env glue either side of the n sim steps of an env step (fp32 library only) ------------------------------
  * fg_envglue_jet_schedule: the action smoothing of the reference's jet envs (cylinder_env_base.py:748-753, a_k = a_{k-1} +
  * alpha (target - a_{k-1}) before every sim step) for the n sim steps of one env step at once: control[k][b] = target[b] +
