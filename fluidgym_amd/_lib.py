@@ -307,6 +307,10 @@ SIGNATURES = {
                                  POINTER(FgRenderCamera), POINTER(FgRenderOptions), c_int32, c_int32, POINTER(c_int32), c_int32, c_void_p,
                                  c_void_p]),
     "fg_obs_noise_add": (c_int, [POINTER(FgNoiseSegment), c_int32, c_int32, c_int32, ctypes.c_uint64, c_void_p, c_void_p, c_void_p]),
+    "fg_baseline_opposition": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, POINTER(c_int32), POINTER(ctypes.c_double), c_int32,
+                                       c_int32, c_void_p, c_void_p]),
+    "fg_baseline_pd": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, ctypes.c_double, ctypes.c_double,
+                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fg_envglue_jet_schedule": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "fg_envglue_channel_observe": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_void_p,
                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

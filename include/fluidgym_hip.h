@@ -802,6 +802,33 @@ typedef struct fg_noise_segment {
 int fg_obs_noise_add(const fg_noise_segment* seg, int32_t n_seg, int32_t rows, int32_t dtype, uint64_t seed,
                      const uint32_t* counters, const int32_t* row_ids, void* stream);
 
+/* ---- baseline controllers of the TCF and RBC envs (csrc/fg_baselines.hip; both libraries, handle-free) -------------------------
+ * One action of the whole batch in ONE launch each (fluidgym_amd/baselines.py).  Fields are read in place:
+ * cell (env, z, y, x) is v[env * batch_stride + (z * ny + y) * nx + x] (batch_stride in reals, >= nz * ny * nx; 2-D: nz = 1).
+ * fg_baseline_opposition: v = the wall-normal velocity.  For env b, wall w (n_walls = 1 or 2) and row r = rows[w] (HOST table, like
+ *   gain; both copied into the kernel arguments): m = mean of v over the plane (z, x) at y = r, P[i][j] = mean of v over the patch
+ *   x in [i actor, (i + 1) actor), z in [j actor, (j + 1) actor) of that plane (one z row per patch where nz = 1), and
+ *   action[b][w][i][j] = gain[w] (P[i][j] - m), action [batch][n_walls][nx / actor][nz / actor] on the device.
+ * fg_baseline_pd: v = the vertical velocity, wy [ny] DEVICE weights that sum to 1.  E[b][hz][hx] = sum_y wy[y] * mean of v over
+ *   x in [hx seg, (hx + 1) seg), z in [hz seg, (hz + 1) seg) (z = 0 alone where nz = 1), and action[b][hz][hx] =
+ *   -(kp E + kd_over_dt (E - e_state[b][hz][hx])), the second term 0 for an env with first[b] != 0; then e_state := E and first[b] := 0.
+ *   e_state (fp64) and action are [batch][nz / seg][nx / seg] on the device (nz / seg = 1 where nz = 1), first [batch] int32 on the
+ *   device.  tickets [batch]: 64-bit device counters, zeroed once by the caller, that order the one write of first[env] after the
+ *   reads of it by the env's heaters (an integer atomic, as in fg_plane_moments).
+ * Sums are fp64 in a fixed tree -- every lane its cells in ascending order, the xor butterfly of the wave, the waves in ascending
+ * order; opposition control sums the plane as the sum of its patch sums -- and the result is rounded once to fg_real: no
+ * floating-point atomic, so an env's action depends neither on the launch order nor on the rest of the batch and repeats bit for
+ * bit.  One workgroup per (env, wall); one workgroup, or one wave for heater columns of up to 1024 cells, per (env, heater).  16-byte
+ * loads where the extents, the pointer and the batch stride allow, single reals otherwise, with the same arithmetic.  Asynchronous
+ * on `stream`; nothing returns to the host.  Before any launch (and without a GPU) FG_ERR_INVALID_ARG: a null pointer, batch < 1, a
+ * non-positive extent, actor / seg < 1 or not dividing nx (and nz where nz > 1), n_walls not 1 or 2, a row outside [0, ny), a batch
+ * stride below nz * ny * nx, a plane or heater column of more than 2^30 cells, more than 2^31 - 1 workgroups. */
+int fg_baseline_opposition(const fg_real* v, int64_t batch_stride, int32_t batch, int32_t nz, int32_t ny, int32_t nx,
+                           const int32_t* rows, const double* gain, int32_t n_walls, int32_t actor, fg_real* action, void* stream);
+int fg_baseline_pd(const fg_real* v, int64_t batch_stride, int32_t batch, int32_t nz, int32_t ny, int32_t nx, int32_t seg,
+                   const double* wy, double kp, double kd_over_dt, double* e_state, int32_t* first, uint64_t* tickets,
+                   fg_real* action, void* stream);
+
 /* ---- env glue either side of the n sim steps of an env step (fp32 library only) ------------------------------
  * fg_envglue_jet_schedule: the action smoothing of the reference's jet envs (cylinder_env_base.py:748-753, a_k = a_{k-1} +
  * alpha (target - a_{k-1}) before every sim step) for the n sim steps of one env step at once: control[k][b] = target[b] +
