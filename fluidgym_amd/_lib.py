@@ -320,6 +320,7 @@ SIGNATURES = {
     "fg_mb_destroy": (c_int, [c_void_p]),
     "fg_config_dump": (c_int, [c_void_p, ctypes.c_char_p, c_int]),
     "fg_mb_config_dump": (c_int, [c_void_p, ctypes.c_char_p, c_int]),
+    "fg_switch_values": (c_int, [c_int32, ctypes.c_char_p, c_int32]),
     "fg_mb_add_block": (c_int, [c_void_p, POINTER(c_float), c_int32, c_int32, c_int32, POINTER(c_int32)]),
     "fg_mb_connect": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),
     "fg_mb_make_periodic": (c_int, [c_void_p, c_int32, c_int32]),
@@ -474,6 +475,18 @@ def load_f64() -> ctypes.CDLL:
         raise NativeLibraryError("libfluidgym_hip_f64.so ABI version mismatch")
     _lib_f64 = lib
     return lib
+
+
+def read_json(fn, first, lib=None) -> dict:
+    """The JSON object of ``fg_config_dump`` / ``fg_mb_config_dump`` / ``fg_switch_values`` (``first``: the handle or the family):
+    a call that finds its buffer too small answers with the length it needs."""
+    import json
+
+    need = 1024
+    while need > 0:
+        buf = ctypes.create_string_buffer(need)
+        need = check(fn(first, buf, need), allow=range(need + 1, 1 << 24), lib=lib)
+    return json.loads(buf.value.decode())
 
 
 def check(rc: int, allow=(), lib=None):

@@ -58,6 +58,7 @@ extern "C" int fg_create(const fg_config* cfg, const fg_real* hx, const fg_real*
 
     fg_state* s = new fg_state();
     memset(s, 0, sizeof(*s));
+    fg_switches_read(s);      // (the environment is read here and nowhere else: fg_switches.h)
     s->cfg = *cfg;
     FgGrid& g = s->grid;
     g.dims = cfg->dims; g.nx = cfg->nx; g.ny = cfg->ny; g.nz = cfg->nz;
@@ -120,30 +121,7 @@ extern "C" int fg_create(const fg_config* cfg, const fg_real* hx, const fg_real*
     for (int k = 0; k < 4; ++k) { s->pred_bicg[k] = 2; s->pred_cg[k] = 1; }
     s->wall_forcing_axis = -1;
     s->ref64_inner = 1e-4f;
-    s->cg_wgs_per_slot = 256;      // (FG_CG_WGS_PER_SLOT until round 5: never changed by a test or a bench leg -- a constant since round 6)
-    // FG_BICG3: z-marching two-kernel BiCGStab in 3-D (fg_bicgstab3d.hip): 0 never | > 0 always, with that z-chunk length (tests on
-    // small grids) | unset: when the grid fits the tiles and fills the chip.  FG_BICG3_BXL: 16 / 32 float4 lanes along x (tile shape)
-    { const char* ev = getenv("FG_BICG3"); s->bicg3_force = ev ? atoi(ev) : -1; }
-    { const char* ev = getenv("FG_BICG3_BXL"); s->bicg3_bxl = ev ? atoi(ev) : 0; }
-    { const char* ev = getenv("FG_BICG_SUB"); s->bicg_sub = ev ? atoi(ev) : -1; }
-    { const char* ev = getenv("FG_REDUCE_WGS"); s->reduce_wgs = ev ? atoi(ev) : 0; }
-    { const char* ev = getenv("FG_BICG3_MIX"); s->bicg3_mix = ev ? atoi(ev) : 3; }   // bit 0: kernel a, bit 1: kernel b as z-march (debugging)
-    { const char* ev = getenv("FG_BICG_FUSED"); s->bicg_fused = ev ? atoi(ev) : 1; }   // 0 five kernels | 1 two kernels in 2-D (default) | 2 two kernels in 3-D as well   // read once, never on the step path
-    s->tridiag_cb = 64;            // (FG_TRIDIAG_CB until round 5; 32 = half-width column blocks in k_tridiag_y_lds: measured, no gain)
-    s->helm_cb_pref = 32;          // (FG_HELM_CB until round 5; 64-column workgroups of k_helm_apply_y: 8.1 against 7.0 us)
-    { const char* ev = getenv("FG_HELM_ROWFORM"); s->helm_rowform_off = (ev && atoi(ev) == 0) ? 1 : 0; }   // 0: k_helm_coeffs + the array-form line kernels
-    { const char* ev = getenv("FG_FD_FACFUSE"); s->fd_facfuse = ev ? atoi(ev) : 1; }
-    { const char* ev = getenv("FG_DEV_DT"); s->dev_dt = ev ? atoi(ev) : 1; }
-    // (default OFF: built for VERDICT r5 item 6 and measured on the RBC leg -- at the bench state's sub-step (0.02, not the 0.0125 the
-    //  round-5 experiment costed) the velocity systems take 16-17 sweeps and the scalar systems do not contract by 0.7: 775 against 793 env-steps/s)
-    { const char* ev = getenv("FG_ADV_LINESWEEP"); s->adv_linesweep = ev ? atoi(ev) : 0; }
-    { const char* ev = getenv("FG_FD_ROWMEAN"); s->fd_rowmean = ev ? atoi(ev) : 1; }     // 0: the fused CG keeps the grid's A = 1 factors
     s->fd_row_epoch = -1; s->rA_epoch = 0; s->fd_row_part_epoch = -1;
-    { const char* ev = getenv("FG_CG_FUSED"); s->cg_fused = ev ? atoi(ev) : 1; }       // 0: five-kernel preconditioned CG iteration (fg_poisson.hip)
-    { const char* ev = getenv("FG_BICG_PFUSED"); s->bicg_pfused = ev ? atoi(ev) : 1; } // 0: eleven-launch Helmholtz-preconditioned BiCGStab iteration
-    // FG_ADV_JACOBI: 1 = the velocity systems of uniform 2-D grids go to the Jacobi sweeps first (fg_jacobi.hip) | 0 = never | unset: off
-    // until fg_set_advection_jacobi turns it on (the Python Simulation does, policy advection_jacobi)
-    { const char* ev = getenv("FG_ADV_JACOBI"); s->adv_jacobi = ev ? atoi(ev) : 0; s->adv_jacobi_env = ev ? 1 : 0; }
     for (int k = 0; k < 4; ++k) s->jac_hist[k] = FgJacHist{0, 0, 0};
     s->jac_solves = s->jac_fallbacks = 0;
     FG_HIP_CHECK(hipHostMalloc(&s->jac_prev, sizeof(float) * 4 * nsys));   // (on-chip form: [nsys] previous residual | [nsys][2] residuals of passes 0 and 1; streaming form: [nsys][2])
@@ -154,11 +132,6 @@ extern "C" int fg_create(const fg_config* cfg, const fg_real* hx, const fg_real*
     FG_HIP_CHECK(hipMemset(s->fcg_xsum, 0, sizeof(FgDacc) * 2 * (size_t)g.B));
     FG_HIP_CHECK(hipMalloc(&s->fcg_lazy, sizeof(int32_t) * (size_t)g.B));
     FG_HIP_CHECK(hipMemset(s->fcg_lazy, 0, sizeof(int32_t) * (size_t)g.B));
-    { const char* e = getenv("FG_FCG_FIRST"); s->fcg_first = (e && atoi(e) == 0) ? 0 : 1; }
-    { const char* e = getenv("FG_JAC_SPEC"); s->jac_spec = (e && atoi(e) == 0) ? 0 : 1; }
-    { const char* e = getenv("FG_FCG_SPEC"); s->fcg_spec = (e && atoi(e) == 0) ? 0 : 1; }
-    { const char* e = getenv("FG_JAC_PREFACTOR"); s->jac_prefactor = (e && atoi(e) == 0) ? 0 : 1; }
-    { const char* e = getenv("FG_JAC_WARM"); s->jac_warm = e ? (atoi(e) != 0 ? 1 : 0) : -1; }      // (-1: where it pays, jac_warm_start)
     s->cg_return_best = 1;
     s->cg_reset_steps = 100;
     s->adv_from_result = 1;
@@ -842,20 +815,15 @@ extern "C" int fg_piso_step(fg_handle s, const fg_real* dt_B, const fg_step_opti
 
 extern "C" int fg_config_dump(fg_handle s, char* buf, int n) {
     FG_REQUIRE(s && buf && n > 0, FG_ERR_INVALID_ARG, "fg_config_dump: bad argument");
-    char tmp[3072];
-    const int len = snprintf(tmp, sizeof(tmp),
-        "{\"build\": \"%s\", \"FG_CG_FUSED\": %d, \"FG_BICG_PFUSED\": %d, \"FG_BICG_FUSED\": %d, \"FG_BICG_SUB\": %d, \"FG_BICG3\": %d, "
-        "\"FG_BICG3_BXL\": %d, \"FG_BICG3_MIX\": %d, \"FG_REDUCE_WGS\": %d, \"FG_CG_WGS_PER_SLOT\": %d, \"FG_TRIDIAG_CB\": %d, \"FG_HELM_CB\": %d, "
-        "\"FG_HELM_ROWFORM\": %d, \"FG_FD_ROWMEAN\": %d, \"FG_POLL_SPIN\": %d, \"FG_PROF_PERIOD\": %d, \"fast_transform_x\": %d, \"fd_preconditioner\": %d, "
-        "\"helmholtz\": %d, \"advection_preconditioner\": %d, \"advection_from_result\": %d, \"return_best\": %d, \"cg_reset_steps\": %d, "
-        "\"double_fallback\": %d, \"wall_forcing_axis\": %d, \"FG_ADV_JACOBI\": %d, \"FG_FCG_FIRST\": %d, \"FG_JAC_WARM\": %d, \"first_iterate_polls\": %ld, \"unstored_pressure_solves\": %ld, \"FG_JAC_SPEC\": %d, \"FG_FCG_SPEC\": %d, \"jacobi_speculation_misses\": %ld, \"jacobi_floor_released\": %ld, \"pressure_refinement_corrections\": %ld}",
-        FG_F64 ? "f64" : "f32", s->cg_fused, s->bicg_pfused, s->bicg_fused, s->bicg_sub, s->bicg3_force, s->bicg3_bxl, s->bicg3_mix, s->reduce_wgs,
-        s->cg_wgs_per_slot, s->tridiag_cb, s->helm_cb_pref, s->helm_rowform_off ? 0 : 1, s->fd_rowmean, s->poll.spin, s->prof.period, s->fd_dct_x, s->fd_Qx ? 1 : 0,
-        s->fd_lam ? 1 : 0, s->adv_precond, s->adv_from_result, s->cg_return_best, s->cg_reset_steps, s->double_fallback, s->wall_forcing_axis, s->adv_jacobi, s->fcg_first, s->jac_warm,
-        s->fcg_first_polls, s->fcg_unstored, s->jac_spec, s->fcg_spec, s->jac_spec_missed, s->jac_floor_released, s->ref64_corrections);
-    if (len >= n) return len + 1;
-    memcpy(buf, tmp, (size_t)len + 1);
-    return FG_OK;
+    std::string out = std::string("{\"build\": \"") + (FG_F64 ? "f64" : "f32") + "\"";
+    fg_switches_json(s, out);
+    const std::pair<const char*, long long> state[] = {
+        {"fast_transform_x", s->fd_dct_x}, {"fd_preconditioner", s->fd_Qx ? 1 : 0}, {"helmholtz", s->fd_lam ? 1 : 0}, {"advection_preconditioner", s->adv_precond},
+        {"advection_from_result", s->adv_from_result}, {"return_best", s->cg_return_best}, {"cg_reset_steps", s->cg_reset_steps}, {"double_fallback", s->double_fallback},
+        {"wall_forcing_axis", s->wall_forcing_axis}, {"first_iterate_polls", s->fcg_first_polls}, {"unstored_pressure_solves", s->fcg_unstored},
+        {"jacobi_speculation_misses", s->jac_spec_missed}, {"jacobi_floor_released", s->jac_floor_released}, {"pressure_refinement_corrections", s->ref64_corrections}};
+    for (const auto& kv : state) fg_json_put(out, kv.first, kv.second);
+    return fg_json_out(out + "}", buf, n);
 }
 
 extern "C" int fg_solver_unconverged(fg_handle s, int64_t* out4) {

@@ -10,6 +10,7 @@
 #include <type_traits>
 
 #include "../../include/fluidgym_hip.h"
+#include "fg_switches.h"
 
 // fg_real (include/fluidgym_hip.h): float in libfluidgym_hip.so, double in libfluidgym_hip_f64.so (-DFG_REAL_DOUBLE).  The fp32 build is
 // the product the benchmarks run; the fp64 build exists for FluidEnv(dtype=torch.float64) and compiles the core translation units only
@@ -546,7 +547,7 @@ enum FgProfKind {
 #define FG_PROF_POOL 256
 struct FgProfMeta { int kind; int nsys; double bytes_per_sys; double flops_per_sys; };
 struct FgProf {
-    int on, used, period;
+    int on, used;
     int prefetched;           // slots whose counts a poll already copied to the host (fg_prof_prefetch)
     hipEvent_t ev[2 * FG_PROF_POOL];
     FgProfMeta meta[FG_PROF_POOL];
@@ -635,7 +636,7 @@ __device__ __forceinline__ void fg_poll_publish(const FgPollOut& p, int i) {
 #endif
 struct FgPoll {
     int32_t* seq;      // pinned [n]
-    int n; int32_t epoch; int spin;    // spin == 0 (FG_POLL_SPIN=0): hipStreamSynchronize, as before
+    int n; int32_t epoch; int spin, words;    // switches (fg_switches.h, set before fg_poll_create): spin == 0: hipStreamSynchronize; words == 0: no result words
     unsigned long long* gran; int n_gran;      // pinned result words {payload, sequence number} (FgPollOut::gran): 8 per sequence word
 };
 int fg_poll_create(FgPoll* P, int n);
@@ -787,24 +788,16 @@ struct fg_state {
     // reference's first rung), 1 every solve (its preconditionBiCG), 2 only to repeat a solve that failed (its
     // BiCG_precondition_fallback); line_retries counts the repeats.  Factors [B][N], allocated on first use
     int adv_precond; long long line_retries;
-    int cg_wgs_per_slot;          // workgroups sharing one CG accumulator slot (256; FG_CG_WGS_PER_SLOT at fg_create: tuning)
     int wall_forcing_axis; fg_real wall_forcing_coef[2]; fg_real* force_uniform;   // fg_set_wall_stress_forcing: [B, dims] uniform body force (device)
-    int reduce_wgs;               // FG_REDUCE_WGS: workgroups per env of the reduction kernels (0 = the rule of fg_reduce_wgs)
-    int bicg_sub;                 // FG_BICG_SUB: envs per sub-batch of the 2-D two-kernel BiCGStab (-1 = by the working set, 0 = never)
-    int bicg3_force, bicg3_bxl, bicg3_mix;   // FG_BICG3 / FG_BICG3_BXL at fg_create (fg_bicgstab3d.hip)
-    int bicg_fused;               // 1 (default): two-kernel BiCGStab iteration (fg_bicgstab.hip); FG_BICG_FUSED=0 at fg_create: five kernels
-    // fused row kernels (fg_fftcg.hip / fg_fftbicg.hip): cg_fused 1 (default) = three-launch preconditioned pressure CG on 2-D grids
-    // with a fast x transform, FG_CG_FUSED=0 at fg_create keeps the five kernels; alpha_k per env and parity; sum(x_k) per env and parity
-    int cg_fused, bicg_pfused; double* fcg_alpha; FgDacc* fcg_xsum;
+    FG_SB_SWITCHES(FG_SW_MEMBER)      // every switch member of this handle family: declared, defaulted and described in fg_switches.h
+    // fused row kernels (fg_fftcg.hip / fg_fftbicg.hip): alpha_k per env and parity; sum(x_k) per env and parity
+    double* fcg_alpha; FgDacc* fcg_xsum;
     // First iterate of the fused CG left unmaterialised (fg_fftcg.hip, k_fcg_check0): fcg_lazy[b] = 1 for an env whose FIRST iterate
     // from zero met the tolerance -- its result is x = alpha_0 z_0 (FgCgOutcome says whether the marks belong to a solve and whether
-    // any x was stored).  fcg_first: 0 switches the whole scheme off (FG_FCG_FIRST=0).
-    int32_t* fcg_lazy; int fcg_first;
-    int fcg_spec;      // FG_FCG_SPEC (default 1): the corrector launched behind k_fcg_check0 (FgCgSpec)
-    int jac_spec; long jac_spec_missed;      // FG_JAC_SPEC (default 1): k_h and the divergence kernel launched behind the sweeps' check kernel (FgSpecHook) | solves that went round again without them
+    // any x was stored).  fcg_first: 0 switches the whole scheme off.
+    int32_t* fcg_lazy;
+    long jac_spec_missed;      // solves that went round again without the kernels launched behind the sweeps' check kernel (jac_spec, FgSpecHook)
     long jac_floor_released = 0;   // systems the streaming sweeps ended on the fp32-floor rule (measured residual above the tolerance): fg_config_dump
-    int jac_prefactor;      // FG_JAC_PREFACTOR (default 1): fg_fd_rowmean_prefactor behind the sweeps' check kernel
-    int jac_warm;      // the Jacobi sweeps of the velocity systems start from the block velocity: 1 always, 0 never (the BiCGStab start vector), -1 (default) on the grids where that saves a pass (fg_jacobi.hip: jac_warm_start)
     long fcg_unstored, fcg_first_polls;      // solves that stored no x | solves whose first iterate was polled (fg_config_dump)
     fg_real* line_inv; fg_real* line_cp;
     fg_real* ilu_d;               // [B,N] modified diagonal of the ILU(0) preconditioner (fg_ilu0.hip), built per solve
@@ -822,19 +815,16 @@ struct fg_state {
     // transform axes, per-solve coefficient arrays [B][N] and a [B][d][N] temporary of the basis changes
     float* fd_lam; float* helm_diag; float* helm_lower; float* helm_upper; float* helm_tmp;
     // row form of the 2-D Helmholtz factors (fg_linepre.hip k_helm_factor_y / k_helm_apply_y): lower_j per env and row, 1 / (hx hz),
-    // columns per workgroup the last fg_helm_factor chose (0 = the array form), FG_HELM_ROWFORM=0 at fg_create
-    float* helm_lower_row; float helm_rs; int helm_cb, helm_rowform_off, helm_cb_pref;
+    // columns per workgroup the last fg_helm_factor chose (0 = the array form)
+    float* helm_lower_row; float helm_rs; int helm_cb;
     // second factor set + the record of a factorisation made ahead of the solves (fg_helm_factor_pair): which sets are valid, for which
     // dt array / diffusivity / wall conditions; helm_set = the set the last fg_helm_factor selected for fg_helm_apply
     float* line_inv2; float* line_cp2; float* helm_lower_row2; int helm_pre_mask; const fg_real* helm_pre_dt; FgNu helm_pre_nu[2]; int helm_pre_walls[2][2]; int helm_set;
-    int tridiag_cb;               // FG_TRIDIAG_CB at fg_create: 64 keeps 64-column workgroups in k_tridiag_y_lds (default: 32 where they divide)
     // x axis marked as a cosine-transform axis (uniform width, FIXED ends): fg_fdfft.hip replaces the two x GEMMs
     int fd_dct_x; float2* fd_dct_tw; float2* fd_dct_rot; float fd_dct_fwd[2]; float fd_dct_inv[2];
     // row-mean preconditioner of the fused pressure CG (fg_fdprecond.hip k_fd_rowmean_factor): eigenvalues of the x basis [nx], per-env
-    // factors [B][N] / [B][ny], FG_FD_ROWMEAN at fg_create (1), epoch of the 1/A field the factors were made from (rA_epoch: bumped by
-    // everything that rewrites s->rA)
-    float* fd_lam_x; float* fd_row_inv; float* fd_row_cp; float* fd_row_lower; int fd_rowmean; long fd_row_epoch; mutable long rA_epoch;
-    int fd_facfuse;               // FG_FD_FACFUSE (default 1): the first tridiagonal solve after 1/A changed makes the row-mean factors itself (0: k_fd_rowmean_factor, a launch of its own)
+    // factors [B][N] / [B][ny], epoch of the 1/A field the factors were made from (rA_epoch: bumped by everything that rewrites s->rA)
+    float* fd_lam_x; float* fd_row_inv; float* fd_row_cp; float* fd_row_lower; long fd_row_epoch; mutable long rA_epoch;
     float* fd_row_part; long fd_row_part_epoch;   // per-tile row sums of 1/A written by k_adv_build, and the rA epoch they belong to
     // test entries only (fg_debug_apply_*): host array of FG_FORM_SLOTS the preconditioner dispatchers fill with the forms they launch
     // (FG_FORM_* codes of include/fluidgym_hip.h); nullptr on every step path
@@ -845,16 +835,14 @@ struct fg_state {
     fg_real* dt_pinned;      // [B] host-pinned per-env substep sizes of fg_single_step
     fg_real* dt_dev;         // [B]
     double* t_rem_dev;       // [B] FgDtRule::t_rem (fp32 build)
-    int dev_dt;              // FG_DEV_DT (default 1): the adaptive sub-step is taken on the device behind the CFL kernel
     // iterations the last solve of each KIND needed (the first convergence poll of the next one is scheduled there): advection kinds
     // 0 scalar, 1 velocity; pressure kinds 0 first corrector, 1 later correctors, 2 stand-alone calls.  Until round 5 one predictor per
     // solver served all kinds: the RBC env's second corrector (0-1 iterations) then launched the first corrector's three iterations
     // before its first poll, and the first corrector polled twice
     int pred_bicg[4], pred_cg[4];
-    // Jacobi sweeps for the velocity systems of the uniform 2-D grids (fg_jacobi.hip): switch (FG_ADV_JACOBI / fg_set_advection_jacobi),
-    // per-kind history (sweeps the last solve needed; solves still to skip after a failure), pinned residuals of the pass before the last
+    // Jacobi sweeps for the velocity systems of the uniform 2-D grids (fg_jacobi.hip): switch (fg_switches.h / fg_set_advection_jacobi)
+    // and whether the environment set it, per-kind history (sweeps the last solve needed; solves still to skip after a failure), pinned residuals of the pass before the last
     int adv_jacobi, adv_jacobi_env; FgJacHist jac_hist[4]; float* jac_prev;
-    int adv_linesweep;            // FG_ADV_LINESWEEP (default 1): line sweeps instead of the Helmholtz-preconditioned BiCGStab where they contract (fg_linepre.hip)
     long long jac_solves, jac_fallbacks;
     long jac_rA_epoch;      // rA_epoch at which rA = 1 / A was written for the velocity system in s->A (the streaming sweeps read it)
     FgCounters ctr;         // iterations per solve kind since the last reset (fg_solver_counters)

@@ -523,12 +523,11 @@ struct JacPlan { bool ok, xt; int q, span, sweeps, tiles; double cost; };
 // 7 100-7 170 env-steps/s against 6 400-6 780 with two passes of 6 over full rows); 8 on 32-column bands (512 x 256: 1 834 against
 // 1 466 with full rows of 16)
 int jac_sweeps_for(int span, bool xt) { return xt ? (span <= 32 ? 8 : 12) : (span <= 16 ? 4 : (span <= 32 ? 6 : 8)); }
-JacPlan jac_plan(const FgGrid& G) {
+JacPlan jac_plan(const fg_state* s) {
+    const FgGrid& G = s->grid;
     JacPlan best = {false, false, 0, 0, 0, 0, 1e30};
     if (G.dims != 2 || !(G.fixed[2] && G.fixed[3])) return best;
-    // FG_JAC_SHAPE (A/B runs): 1 = full rows only, 2 = bands only; FG_JAC_SWEEPS = sweeps per pass (clamped to what the region allows)
-    static const int force_shape = [] { const char* e = getenv("FG_JAC_SHAPE"); return e ? atoi(e) : 0; }();
-    static const int force_sweeps = [] { const char* e = getenv("FG_JAC_SWEEPS"); return e ? atoi(e) : 0; }();
+    const int force_shape = s->jac_shape, force_sweeps = s->jac_sweeps;      // (A/B runs: fg_switches.h)
     auto sweeps_of = [&](int span, bool xt) { int S = force_sweeps > 0 ? force_sweeps : jac_sweeps_for(span, xt); const int cap = (span - 4) / 2; return S > cap ? cap : (S < 1 ? 1 : S); };
     if (force_shape != 2 && (G.nx == 64 || G.nx == 128 || G.nx == 256 || G.nx == 512)) {
         const int rows = JAC_CELLS / G.nx;
@@ -560,7 +559,7 @@ int launch_pass(const fg_state* s, int slot, const JacPlan& P, const JacArgs& a,
 
 }  // namespace
 
-static bool jac_onchip_ok(const fg_state* s, const FgBicgArgs& a) { return a.nc == 2 && jac_plan(s->grid).ok && jac_lds_ready(); }
+static bool jac_onchip_ok(const fg_state* s, const FgBicgArgs& a) { return a.nc == 2 && jac_plan(s).ok && jac_lds_ready(); }
 // the streaming form takes the velocity systems of everything else (3-D; 2-D grids no region shape fits), where rA = 1 / diag is at hand
 static bool jac_stream_ok(const fg_state* s, const FgBicgArgs& a) { return a.nc == s->grid.dims && a.diag == s->A && s->rA != nullptr && s->rA_epoch == s->jac_rA_epoch; }
 
@@ -593,7 +592,7 @@ int fg_jacobi_solve(fg_state* s, const FgBicgArgs& a, fg_solve_info* info_host, 
     // Region shape and sweeps per pass: fixed by the grid, NOT by the history of the handle -- an env stops at the first pass boundary
     // where the verdict holds, so its iterate (its bits) does not depend on how many passes were enqueued ahead, and a replayed step
     // (get_state -> set_state -> step) repeats exactly (jac_sweeps_for).
-    const JacPlan plan = jac_plan(G);
+    const JacPlan plan = jac_plan(s);
     const int S = plan.sweeps;
     // passes to enqueue before the first check: what the previous solve of this kind needed (the history only decides how much is
     // enqueued ahead of the poll)
@@ -601,7 +600,7 @@ int fg_jacobi_solve(fg_state* s, const FgBicgArgs& a, fg_solve_info* info_host, 
     JacArgs q = {};
     q.diag = a.diag; q.off = a.off; q.rhs = a.rhs; q.acc = s->acc; q.flags = s->flags; q.info = s->info_dev; q.tol = a.tol;
     q.sweeps = S; q.nx = G.nx; q.ny = G.ny; q.n = n; q.tiles = plan.tiles;
-    { static const int xr = [] { const char* e = getenv("FG_JAC_XCD"); return e ? atoi(e) : 1; }(); q.xcd_remap = xr; }
+    q.xcd_remap = s->jac_xcd;
     float* work = s->w[0];
     const double bytes_sys = 0.5 * 4.0 * n * 11.0, flops_sys = 0.5 * n * 2.0 * 9.0 * S;
     int passes = 0;

@@ -690,9 +690,9 @@ int fg_helm_alloc(fg_state* s) {
 
 // row form (k_helm_factor_y / k_helm_apply_y above): 2-D, nx a multiple of 4 and of the column block, the column block in LDS
 static int helm_cb(const fg_state* s) {      // columns per workgroup of the application, 0 = the array form (k_helm_coeffs + line kernels)
-    if (s->grid.dims != 2 || (s->grid.nx & 63) != 0 || s->grid.ny > HELM_MAX_NY || s->helm_rowform_off) return 0;
+    if (s->grid.dims != 2 || (s->grid.nx & 63) != 0 || s->grid.ny > HELM_MAX_NY || !s->helm_rowform) return 0;
     const int nyp = (s->grid.ny + LP_CH - 1) / LP_CH * LP_CH;
-    const int cb = s->helm_cb_pref == 64 ? 64 : 32;
+    const int cb = 32;      // (64-column workgroups of k_helm_apply_y: 8.1 against 7.0 us)
     const size_t bytes = (size_t)3 * nyp * cb * sizeof(float);
     if (bytes > 160 * 1024) return 0;
     static std::mutex mu;
@@ -702,8 +702,7 @@ static int helm_cb(const fg_state* s) {      // columns per workgroup of the app
     std::lock_guard<std::mutex> lock(mu);
     size_t& granted = granted_dev[dev];
     if (bytes > granted) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_helm_apply_y<32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(k_helm_apply_y<64>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_helm_apply_y<32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
             (void)hipGetLastError();
             return 0;
         }
@@ -756,7 +755,7 @@ int fg_helm_factor(fg_state* s, const float* dt, FgNu nu, int wall_lo, int wall_
 
 // z = M^-1 r (the per-mode Thomas solves of the Helmholtz operator factorised by the last fg_helm_factor), nc systems per env
 int fg_helm_apply(fg_state* s, int nc, const float* r, float* z, hipStream_t st) {
-    if (s->forms_rec) s->forms_rec[FG_FORM_SLOT_HELM] = !s->helm_cb ? FG_FORM_HELM_ARRAY : s->helm_cb == 64 ? FG_FORM_HELM_ROW64 : FG_FORM_HELM_ROW32;
+    if (s->forms_rec) s->forms_rec[FG_FORM_SLOT_HELM] = !s->helm_cb ? FG_FORM_HELM_ARRAY : FG_FORM_HELM_ROW32;
     if (!s->helm_cb) return fg_line_apply(s, s->helm_diag, nullptr, nc, r, z, st);
     HelmArgs a = {};
     a.inv = s->helm_set ? s->line_inv2 : s->line_inv; a.cp = s->helm_set ? s->line_cp2 : s->line_cp;
@@ -765,10 +764,7 @@ int fg_helm_apply(fg_state* s, int nc, const float* r, float* z, hipStream_t st)
     // per system and cell: r, inv, c' read + z written
     const int slot = fg_prof_slot(s, FG_PK_LINE, s->flags, nsys, 16.0 * s->grid.n, 5.0 * s->grid.n, st);
     const int nyp = (s->grid.ny + LP_CH - 1) / LP_CH * LP_CH;
-    if (s->helm_cb == 64)
-        FG_LAUNCH_P(s, slot, k_helm_apply_y<64>, dim3(s->grid.nx / 64, nsys), dim3(256), (size_t)3 * nyp * 64 * sizeof(float), st, a, r, z);
-    else
-        FG_LAUNCH_P(s, slot, k_helm_apply_y<32>, dim3(s->grid.nx / 32, nsys), dim3(256), (size_t)3 * nyp * 32 * sizeof(float), st, a, r, z);
+    FG_LAUNCH_P(s, slot, k_helm_apply_y<32>, dim3(s->grid.nx / 32, nsys), dim3(256), (size_t)3 * nyp * 32 * sizeof(float), st, a, r, z);
     FG_HIP_CHECK(hipGetLastError());
     return FG_OK;
 }

@@ -22,7 +22,7 @@
 // off at run time in that build (fg_mb_create / fg_mb_finalize).  The four-cell BiCGStab and CG kernels (k_mbb_*<DIMS, 4>,
 // k_mbc_*<.., 4, ..>: packs of mb_real, fg_mb_krylov.hip) and the restrictions fused with the p / s update are well-formed in doubles
 // too, but have not been measured or tested there and stay switched off as well (mb_bicgstab: vec_mask, ml_fused; mb_cg:
-// dbg_scalar_cg).  The multilevel preconditioner in kernel form (k_ml_*) and the preconditioned CG on it (k_mbc_ap<.., MBC_PRE>,
+// vec4).  The multilevel preconditioner in kernel form (k_ml_*) and the preconditioned CG on it (k_mbc_ap<.., MBC_PRE>,
 // k_mbc_update<.., true>) are written in mb_real and serve both builds; fg_mb_set_multilevel installs the tables in either.
 // (Until round 4 the fp64 build renamed the keyword `float` for these files.)
 typedef float fg_f32;
@@ -125,7 +125,7 @@ struct fg_mb_state {
     int32_t* flags_pinned = nullptr;
     int32_t* sys_map_dev = nullptr;    // [B d] systems of a compacted launch (mb_bicgstab: MbSolve::sys_map); host copy in sys_map_pinned
     int32_t* sys_map_pinned = nullptr;
-    int dbg_compact = 1;               // FG_MB_COMPACT=0: every launch over all systems
+    FG_MB_SWITCHES(FG_SW_MEMBER)       // every switch member of this handle family: declared, defaulted and described in fg_switches.h
     FgPoll poll = {};             // host polls on pinned sequence words (fg_internal.h FgPoll; created with the pinned mirrors)
     int32_t* verified = nullptr;   // [B d] BiCGStab convergence verification (mb_bicgstab): 0 open, 1 true residual checked, 2 being checked
     fg_solve_info *info_dev, *info_pinned = nullptr;
@@ -139,13 +139,11 @@ struct fg_mb_state {
     // right-preconditioned pressure BiCGStab (kernel form): a trial with exponential back-off (mb_pressure_bicgstab): after a failed
     // attempt the next ml_bicg_skip solves run plain, the back-off doubles with every failure (up to 256) and halves with every success
     int ml_bicg_attempts = 0, ml_bicg_failures = 0, ml_bicg_skip = 0, ml_bicg_backoff = 4;
-    int dbg_ml_warmup = 0;   // FG_MB_ML_WARMUP: pressure solves a handle runs plain before its first multilevel attempt
     int ml_cap4 = 0, ml_cap8 = 0;   // capacity of the tables above (the on-chip CG takes at most 2048 / 512 aggregates, the kernel form 65535 / 2048)
     // work arrays of the kernel form (mb_ml_apply): aggregate sums [B][n4], coarse solution [B][n8], 1 / scale [B], M p and M s [B][N]
     mb_real *ml_r4 = nullptr, *ml_z8 = nullptr, *ml_scale = nullptr, *ml_mp = nullptr, *ml_ms = nullptr;
     uint16_t* ml_p8c = nullptr;   // the 8 x 8 aggregate of every CELL (parent4[a4[i]]): one table level less in the prolongation
     mb_real *ml_cnt4 = nullptr, *ml_g8 = nullptr;   // cells per 4 x 4 aggregate [n4]; A8^+ (cells per 8 x 8 aggregate) [n8]: M (r - c 1) from M's sums of r (k_ml_prolong_cg)
-    int dbg_pcg_kernel = 0;       // FG_MB_PCG_KERNEL=1 (fp32 build): the preconditioned pressure CG in kernel form instead of the on-chip / cluster kernels (the fp64 build's form)
     long long ml_cg_solves = 0;   // pressure CG solves that ran the kernel-form preconditioned loop (fg_mb_config_dump)
     mb_real* ml_r4c = nullptr; uint32_t* ml_pos4 = nullptr;   // r4 once more, ordered by parent: [B][n8][4] (absent children stay 0), and the slot of every aggregate in it
     mb_real* Poff4 = nullptr;    // [B][N][4] pressure off-diagonals interleaved per cell (2-D), written by k_mb_pmatrix next to Poff
@@ -157,7 +155,6 @@ struct fg_mb_state {
     mb_real *ilu_w = nullptr, *ilu_ud = nullptr;                 // [B][F][N] modified off-diagonals (l_ik below, u_ij above the diagonal), [B][N] u_ii
     mb_real *ilu_mp = nullptr, *ilu_ms = nullptr;                // [B][d][N]
     int ilu_state = 0;         // 0 not tried, 1 schedules built, -1 the mesh does not qualify (a cell with the same neighbour across two faces)
-    int dbg_rung_ilu = 1;      // FG_MB_RUNG_ILU=0: the preconditioned rung keeps the right diagonal scaling of rounds 1-3
     // aggregate-owned layout of the on-chip CG (k_mbc_onchip<AGG>, built by fg_mb_set_multilevel when the mesh has at most 256
     // 8 x 8 aggregates of at most four 4 x 4 children of at most 16 cells): thread t = 4 * (8 x 8 aggregate) + child owns the
     // cells of that child, member m (row-major in its rectangle) lives in slot t + 1024 m of a 16 384-slot index space
@@ -167,20 +164,13 @@ struct fg_mb_state {
     uint2* oc_nbr = nullptr;           // [OC_SLOTS] the four neighbour slots of a slot's cell as byte offsets (slot * 4), 16 bits each; prescribed face = the slot itself
     mb_real* oc_d4g = nullptr;           // [1024] 1 / diag(Z4^T S Z4) of the thread's aggregate (0: the thread owns none)
     int32_t* oc_cnt = nullptr;         // [1024] cells the thread owns
-    int oc_rtg_nt = 1024;               // FG_MB_OC_RTG_NT: workgroup size of that instance (1024 x 24 cells or 512 x 48 cells per thread)
     mb_real* oc_rt_scratch = nullptr;   // [B][N] r - mean r of the on-chip preconditioner pass on meshes of 16-24 k cells (fg_mb_onchip.hip RTG)
     mb_real *Poff4s = nullptr, *Pdiag_s = nullptr, *oc_bestx = nullptr;   // [B][OC_SLOTS][4], [B][OC_SLOTS], [B][OC_SLOTS]: slot order; holes stay 0
     bool oc_agg = false;               // tables above installed
     bool oc_matrix_stale = true;       // no k_mb_pmatrix launch has written the slot-ordered matrix since the tables were installed
-    int dbg_oc_agg = 1;                // FG_MB_OC_AGG=0: keep the cell-ordered on-chip kernel
-    int oc_variant = 0;        // FG_MB_OC_VARIANT (tuning switches of the on-chip CG)
     unsigned long long* oc_dbg = nullptr;   // per-phase cycle counts (fg_mb_debug_cycles)
-    int onchip_mode = 1;       // FG_MB_ONCHIP: 0 never, 1 when the mesh fits one workgroup's LDS / registers (default)
     // cluster CG (fg_mb_cluster.hip, round 6): FG_CL_G workgroups per env, each owning a contiguous range of the 8 x 8 aggregates;
     // slot s of workgroup g = thread + NT * member.  Tables built by mb_cluster_build behind fg_mb_set_multilevel
-    int cl_mode = 1;           // FG_MB_CLUSTER: 0 never, 1 meshes beyond 8 k cells (default), 2 every mesh the tables fit
-    int cl_near = 1;           // FG_MB_CL_NEAR=0: granule stores always write through (sc1), also when a cluster's workgroups share an XCD
-    int cl_max_clusters = 0;   // FG_MB_CL_MAXCL: cap on the clusters of a launch (tests: envs beyond it queue inside the kernel)
     bool cl_on = false;        // tables installed
     bool cl_matrix_stale = true;   // no k_mb_pmatrix launch has written the cluster-ordered matrix since
     int cl_cpt = 0, cl_nt = 0, cl_S = 0, cl_W = 0, cl_n8g_max = 0, cl_n_out_max = 0, cl_n_halo_max = 0, cl_cus = 0;
@@ -192,26 +182,15 @@ struct fg_mb_state {
     mb_real *cl_d4g = nullptr, *cl_cnt8 = nullptr, *cl_aci8 = nullptr, *cl_off4 = nullptr, *cl_diag = nullptr, *cl_bestx = nullptr;
     unsigned long long* cl_box = nullptr;
     uint16_t* cl_aci16 = nullptr; mb_real cl_aci16_unscale = 1.f;   // the coarse inverse as fp16 behind a power-of-two scale (meshes whose fp32 rows do not fit LDS)
-    int cl_half = 1;           // FG_MB_CL_HALF=0: such meshes stream the fp32 rows from L2 instead
     int cl_WJ = 0; unsigned long long* cl_jbox = nullptr; uint32_t *cl_jepoch = nullptr, *cl_jabort = nullptr;   // granule boxes of the cluster sweeps (k_mbj_cluster)
-    int cl_jacobi = 1;         // FG_MB_CL_JACOBI=0: the velocity sweeps stay one launch per sweep (k_mbj_sweep_env)
     long long cl_jacobi_solves = 0;
     long long cl_solves = 0, cl_fallbacks = 0;   // launches that solved / that a workgroup gave up on (repeated by the one-workgroup kernels)
     double* x64_best = nullptr; mb_real* best_res = nullptr; int32_t* best_keep = nullptr;   // its best refinement point
     double* x64 = nullptr;     // fp64 iterate of the refined BiCGStab (pressure_use_bicgstab = 2)
-    // debug switches, read ONCE from the environment at fg_mb_create (never on the step path): FG_MB_BICG_VEC4 (per-kernel mask
-    // of the four-cell BiCGStab kernels: 1 p, 2 v, 4 s, 8 t, 16 x; default all), FG_MB_SCALAR_CG=1 (one-cell
-    // CG kernels), FG_MB_TRACE (residual trace on stderr)
-    int dbg_vec_mask = 0, dbg_scalar_cg = 0, dbg_trace = 0, dbg_fail = 0;   // dbg_fail: FG_MB_TRACE_FAIL
     // iterations the last BiCGStab solve of the same place in the step took -- [0..3] velocity non-orthogonal pass,
     // [4 + 4 (c & 1) + (ps & 3)] pressure solve ps of corrector c (+ 16 for its multilevel-preconditioned attempt), [31] anything
     // else: where the next solve of that place polls first
     int pred_bicg[32] = {0};
-    int dbg_ml_cap = 200;   // FG_MB_ML_TRY_CAP: iteration cap of a multilevel-preconditioned pressure BiCGStab attempt (tests: a tiny cap makes every attempt fail)
-    int dbg_fuse_st = 2;   // FG_MB_BICG_FUSE: 0 five BiCGStab kernels, 1 s / t fused (k_mbb_st), 2 also p / v (k_mbb_pv; default)
-    int dbg_ml_fuse = 1;   // FG_MB_ML_FUSE: multilevel BiCGStab forms p / s inside the restriction -- 0 never, 1 up to 32 systems (default), 2 always
-    int dbg_ml_sb = 0;     // systems per workgroup of k_ml_coarse (2 / 4 / 8; 0 = by the rule of mb_ml_restrict_coarse); no longer read from the environment
-    int dbg_pred = 1;      // FG_MB_PRED=0: first convergence poll after two iterations instead of where the previous solve finished
     // per-env outcome of the last fg_mb_piso_step / fg_mb_single_step: 0 ok, 1 a solve ended unconverged (best iterate used),
     // 2 a solve was non-finite: that env's step was NOT committed (state as before the step), the other envs completed
     mb_real* dt_step = nullptr;          // [B] working copy of the caller's dt; failed envs are masked out (dt = 0) in it
@@ -220,7 +199,7 @@ struct fg_mb_state {
     std::vector<int32_t> env_status;   // [B] host, what fg_mb_env_status reports
     int cg_stall_limit = 400;  // fg_mb_set_stall_limit
     int adv_from_result = 0;   // fg_mb_set_advection_start
-    // Jacobi sweeps for the velocity systems (mb_jacobi, fg_mb_krylov.hip): switch (fg_mb_set_advection_jacobi / FG_ADV_JACOBI), per
+    // Jacobi sweeps for the velocity systems (mb_jacobi, fg_mb_krylov.hip): switch (fg_mb_set_advection_jacobi / fg_switches.h), per
     // non-orthogonal pass the sweeps the last solve needed and the solves still to skip after a failure, pinned residuals of the check
     int adv_jacobi = 0, adv_jacobi_env = 0;
     FgJacHist jac_hist[4] = {};      // (fg_internal.h: the rule of the single-block sweeps)

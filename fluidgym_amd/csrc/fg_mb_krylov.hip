@@ -1172,7 +1172,7 @@ static void mb_ml_restrict_coarse(fg_mb_state* s, const MbSolve& q, const MlDev&
         // instead of asking for more than the default 64 KB of a workgroup
         const int n8p = (M.n8 + 3) & ~3;
         const auto bytes = [&](int sb) { return (size_t)((sb * n8p > 4 * sb * ML_ROWS ? sb * n8p : 4 * sb * ML_ROWS) + ML_CG * sb * ML_ROWS) * sizeof(mb_real); };
-        int sb = s->dbg_ml_sb ? s->dbg_ml_sb : (nsys >= 32 ? 8 : 4);
+        int sb = nsys >= 32 ? 8 : 4;
         if (sb == 8 && bytes(8) > 64 * 1024) sb = 4;
         if (FG_MB_F64 && sb == 4 && bytes(4) > 64 * 1024) sb = 2;
         static_assert((2 * ML_N8_MAX + ML_CG * 2 * ML_ROWS) * sizeof(double) <= 64 * 1024, "two systems per workgroup fit at the largest coarse level");
@@ -1467,7 +1467,7 @@ int mb_bicgstab(fg_mb_state* s, const mb_real* dt, const mb_real* diag, const mb
     // a few launches past convergence costs ~2 us each, while every poll is a stream synchronisation: 10-20 us of idle GPU), then
     // every 2 (every 10 beyond 20) iterations
     const int pred = s->pred_bicg[opt.pred_slot & 31];
-    int next_poll = (pred > 2 && s->dbg_pred) ? pred : 2;
+    int next_poll = pred > 2 ? pred : 2;
     for (int it = 0; it < max_iterations && !done; ++it) {
         if (it > 0 && it % R.restart_every == 0) mb_bicg_reopen(R, MB_OPEN_RESTART, it, 1);
         mb_bicg_iterate(R, it);
@@ -1806,7 +1806,7 @@ static int mb_cg_kernels(fg_mb_state* s, const mb_real* dt, const mb_real* diag,
     q.best_x = s->w[4]; q.best_it = s->best_it; q.stall_limit = R.stall_limit;
     q.accept_factor = R.accept_factor; q.accept_window = R.accept_window;
     const dim3 sg((nsys + 63) / 64), sb(64), grid((n + FG_BLOCK - 1) / FG_BLOCK, nsys), blk(FG_BLOCK);
-    const bool vec4 = (n % 4 == 0) && !s->dbg_scalar_cg;   // FG_MB_SCALAR_CG=1 forces the one-cell-per-thread kernels
+    const bool vec4 = (n % 4 == 0) && !FG_MB_F64;   // (the fp64 build runs the one-cell-per-thread kernels; a switch of its own until round 5)
     const dim3 grid4((n / 4 + FG_BLOCK - 1) / FG_BLOCK, nsys);
     hipLaunchKernelGGL(k_mbs_begin, sg, sb, 0, st, dt, q, nsys);
     MB_DISPATCH(s, hipLaunchKernelGGL(k_mbs_init<DIMS>, grid, blk, 0, st, s->dev, q, R.use_x0, project_mean ? C_SUM : -1, 0););

@@ -470,57 +470,21 @@ extern "C" int fg_mb_create(int32_t dims, int32_t batch, int32_t device, fg_mb_h
     fg_mb_state* s = new fg_mb_state();
     s->d = dims; s->F = 2 * dims; s->B = batch;
     s->host_only = device < 0;
-    {   // debug switches: the only getenv calls of this path, never on the step path
-        const char* e = getenv("FG_MB_BICG_VEC4");
-        s->dbg_vec_mask = !e ? 31 : ((e[0] == '1' && e[1] == 0) ? 31 : atoi(e));   // bit per kernel: 1 p, 2 v, 4 s, 8 t, 16 x
-        s->dbg_scalar_cg = 0;      // (FG_MB_SCALAR_CG until round 5: the one-cell CG kernels are what the fp64 build runs, set below)
-        e = getenv("FG_MB_BICG_FUSE"); s->dbg_fuse_st = e ? atoi(e) : 2;   // 0 five kernels, 1 s / t fused, 2 also p / v (default)
-        s->dbg_pred = 1;           // (FG_MB_PRED until round 5)
-        e = getenv("FG_ADV_JACOBI"); s->adv_jacobi = e ? atoi(e) : 0; s->adv_jacobi_env = e ? 1 : 0;      // (as on the single-block path: fg_api.hip)
-        e = getenv("FG_MB_ML_FUSE"); s->dbg_ml_fuse = e ? atoi(e) : 1;
-        s->dbg_ml_sb = 0;          // (FG_MB_ML_SB until round 5) systems per workgroup of k_ml_coarse: by batch size
-        e = getenv("FG_MB_ML_TRY_CAP"); if (e && atoi(e) > 0) s->dbg_ml_cap = atoi(e);
-        s->dbg_trace = getenv("FG_MB_TRACE") != nullptr;
-        if (const char* e = getenv("FG_MB_COMPACT")) s->dbg_compact = atoi(e);
-        if (const char* e = getenv("FG_MB_OC_RTG_NT")) s->oc_rtg_nt = atoi(e);   // 1: the register-resident form on 16-24 k cells instead of k_mbc_l2
-        s->dbg_fail = getenv("FG_MB_TRACE_FAIL") != nullptr;
-        e = getenv("FG_MB_ONCHIP"); s->onchip_mode = (e && e[0] == '0') ? 0 : 1;
-        e = getenv("FG_MB_OC_AGG"); s->dbg_oc_agg = (e && e[0] == '0') ? 0 : 1;
-        e = getenv("FG_MB_CL_JACOBI"); s->cl_jacobi = (e && e[0] == '0') ? 0 : 1;
-        e = getenv("FG_MB_CL_HALF"); s->cl_half = (e && e[0] == '0') ? 0 : 1;
-        e = getenv("FG_MB_CL_NEAR"); s->cl_near = (e && e[0] == '0') ? 0 : 1;
-        e = getenv("FG_MB_CL_MAXCL"); s->cl_max_clusters = e ? atoi(e) : 0;
-        e = getenv("FG_MB_CLUSTER"); s->cl_mode = e ? atoi(e) : 1;   // 0 never, 1 meshes beyond 8 k cells (default), 2 every mesh its tables fit
-        e = getenv("FG_MB_RUNG_ILU"); s->dbg_rung_ilu = (e && e[0] == '0') ? 0 : 1;
-        e = getenv("FG_MB_PCG_KERNEL"); s->dbg_pcg_kernel = (e && e[0] == '1') ? 1 : 0;
-        e = getenv("FG_MB_OC_VARIANT"); s->oc_variant = e ? atoi(e) : 0;   // bit 0: no compiler fences in the stencil pass; bit 1: split [F][N] coefficient layout
-    }
-#if FG_MB_F64
-    // the fp64 build runs the one-cell-per-thread kernels: the four-cell forms are well-formed in doubles but neither measured nor
-    // tested there, the on-chip / cluster CG are written for 32-bit words (fg_mb.h); the multilevel preconditioner runs in kernel
-    // form there once fg_mb_set_multilevel has installed it
-    s->dbg_vec_mask = 0; s->dbg_scalar_cg = 1; s->onchip_mode = 0; s->dbg_oc_agg = 0; s->cl_mode = 0;
-#endif
+    fg_switches_read(s);      // (the environment is read here and nowhere else: fg_switches.h)
     *out = s;
     return FG_OK;
 }
 
 extern "C" int fg_mb_config_dump(fg_mb_handle s, char* buf, int n) {
     FG_REQUIRE(s && buf && n > 0, FG_ERR_INVALID_ARG, "fg_mb_config_dump: bad argument");
-    char tmp[2048];
-    const int len = snprintf(tmp, sizeof(tmp),
-        "{\"FG_MB_BICG_VEC4\": %d, \"FG_MB_SCALAR_CG\": %d, \"FG_MB_BICG_FUSE\": %d, \"FG_MB_PRED\": %d, \"FG_MB_ML_FUSE\": %d, \"FG_MB_ML_SB\": %d, "
-        "\"FG_MB_ML_TRY_CAP\": %d, \"FG_MB_ML_WARMUP\": %d, \"FG_MB_GRAPH\": 0, \"FG_MB_TRACE\": %d, \"FG_MB_COMPACT\": %d, \"FG_MB_OC_RTG_NT\": %d, "
-        "\"FG_MB_ONCHIP\": %d, \"FG_MB_OC_AGG\": %d, \"FG_MB_RUNG_ILU\": %d, \"FG_MB_OC_VARIANT\": %d, \"FG_MB_CLUSTER\": %d, \"FG_MB_PCG_KERNEL\": %d, \"multilevel_on\": %d, \"multilevel_cg_solves\": %lld, "
-        "\"cluster_on\": %d, \"cluster_members_per_thread\": %d, \"cluster_threads\": %d, \"cluster_halo_max\": %d, \"cluster_solves\": %lld, \"cluster_fallbacks\": %lld, \"cluster_jacobi_solves\": %lld}",
-        (int)s->dbg_vec_mask, (int)s->dbg_scalar_cg, (int)s->dbg_fuse_st, (int)s->dbg_pred, (int)s->dbg_ml_fuse, (int)s->dbg_ml_sb, (int)s->dbg_ml_cap,
-        (int)s->dbg_ml_warmup, (int)s->dbg_trace, (int)s->dbg_compact, (int)s->oc_rtg_nt, (int)s->onchip_mode, (int)s->dbg_oc_agg,
-        (int)s->dbg_rung_ilu, (int)s->oc_variant, (int)s->cl_mode, (int)s->dbg_pcg_kernel, (int)((s->ml_on && s->ml_a4 != nullptr) ? 1 : 0), s->ml_cg_solves,
-        (int)(mb_cluster_wanted(s) ? 1 : 0), (int)s->cl_cpt, (int)s->cl_nt, (int)s->cl_n_halo_max,
-        s->cl_solves, s->cl_fallbacks, s->cl_jacobi_solves);
-    if (len >= n) return len + 1;
-    memcpy(buf, tmp, (size_t)len + 1);
-    return FG_OK;
+    std::string out = "{";
+    fg_switches_json(s, out);
+    const std::pair<const char*, long long> state[] = {
+        {"multilevel_on", (s->ml_on && s->ml_a4 != nullptr) ? 1 : 0}, {"multilevel_cg_solves", s->ml_cg_solves}, {"cluster_on", mb_cluster_wanted(s) ? 1 : 0},
+        {"cluster_members_per_thread", s->cl_cpt}, {"cluster_threads", s->cl_nt}, {"cluster_halo_max", s->cl_n_halo_max}, {"cluster_solves", s->cl_solves},
+        {"cluster_fallbacks", s->cl_fallbacks}, {"cluster_jacobi_solves", s->cl_jacobi_solves}};
+    for (const auto& kv : state) fg_json_put(out, kv.first, kv.second);
+    return fg_json_out(out + "}", buf, n);
 }
 
 extern "C" int fg_mb_destroy(fg_mb_handle s) {

@@ -403,11 +403,11 @@ int fg_fd_rowmean_prefactor(fg_state* s, const fg_real* dt, hipStream_t st) {
     return FG_OK;
 }
 
-int fg_cg_slots(const fg_state* s) {   // ~cg_wgs_per_slot workgroups per accumulator slot, power of two
+int fg_cg_slots(const fg_state* s) {   // ~256 workgroups per accumulator slot (a switch until round 5: no test or bench leg ever changed it), power of two
     int tiles_per_env = 1;
     FG_DISPATCH(s, { tiles_per_env = fg_launch_geometry<DIMS, VEC>(s->grid).tiles; });
     int ns = 1;
-    while (ns < FG_CG_SLOTS && tiles_per_env / ns > s->cg_wgs_per_slot) ns *= 2;
+    while (ns < FG_CG_SLOTS && tiles_per_env / ns > 256) ns *= 2;
     return ns;
 }
 

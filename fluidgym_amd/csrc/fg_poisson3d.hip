@@ -394,13 +394,7 @@ __global__ __launch_bounds__(FG_BLOCK) __attribute__((amdgpu_waves_per_eu(MODE =
 }  // namespace
 
 // geometry -----------------------------------------------------------------------------------------
-static int z_shape() {  // lanes along x: 16 (64 x 16 tile), 32 (128 x 8), 64 (256 x 4); FG_ZMARCH_BXL overrides
-    static const int v = 0;      // (FG_ZMARCH_BXL until round 5: the tile width follows the grid)
-    return v;
-}
-static int z_pick_bxl(const FgGrid& g) {
-    const int forced = z_shape();
-    if (forced == 16 || forced == 32 || forced == 64) return forced;
+static int z_pick_bxl(const FgGrid& g) {      // lanes along x: 16 (64 x 16 tile), 32 (128 x 8), 64 (256 x 4)
     // widest tile the grid is a multiple of: 256 x 4 measured best at 256^3 (1 KiB contiguous per wave access)
     if (g.nx % 256 == 0 && g.ny % 4 == 0) return 64;
     if (g.nx % 128 == 0 && g.ny % 8 == 0) return 32;
@@ -414,7 +408,7 @@ bool fg_zmarch_ok(const fg_state* s, int* zc_out) {
     // tiles must coincide with the grid (every thread valid; halo loaders handle wrap / clamp at tile edges)
     if (g.dims != 3 || s->vec != 4 || g.nz < 32 || (g.nx % TX) != 0 || (g.ny % TY) != 0) return false;
     const int tiles = (g.nx / TX) * (g.ny / TY);
-    static const int force = [] { const char* e = getenv("FG_FORCE_ZMARCH"); return e ? atoi(e) : 0; }();
+    const int force = s->zmarch_force;
     if (force < 0) return false;            // FG_FORCE_ZMARCH=-1: always use the generic brick kernels
     if (force > 0) { *zc_out = force; return true; }  // FG_FORCE_ZMARCH=ZC: tests exercise small grids
     int zc = 32;
@@ -444,7 +438,7 @@ static int launch_march(const fg_state* s, const Z3Args& a, int zc, hipStream_t 
     // Most of the gain is the geometry (one full round, 9 % z-halo planes instead of 25 %); two planes in flight per thread on
     // top of it: nothing (Jacobi 53.7 us), and in the two-barrier apply it spills (124 VGPRs at four waves already).
     // FG_ZMARCH_SB: bit MODE forces it on with the caller's chunk length, 0 = never; unset = the rule above.
-    static const int sb_mask = [] { const char* e = getenv("FG_ZMARCH_SB"); return e ? atoi(e) : -1; }();
+    const int sb_mask = s->zmarch_sb;
     bool sb = sb_mask >= 0 && ((sb_mask >> MODE) & 1);
     if (sb_mask < 0 && MODE != MODE_APPLY) {
         static const int slots = [] {

@@ -6,20 +6,14 @@
 #include "fg_internal.h"
 
 int fg_poll_create(FgPoll* P, int n) {
-    P->n = n; P->epoch = 0;
-    const char* e = getenv("FG_POLL_SPIN");
-    P->spin = !(e && atoi(e) == 0);
+    P->n = n; P->epoch = 0;      // (P->spin / P->words: the handle's switches, already read)
     FG_HIP_CHECK(hipHostMalloc(&P->seq, sizeof(int32_t) * (size_t)n));
     for (int i = 0; i < n; ++i) P->seq[i] = 0;
     P->gran = nullptr; P->n_gran = 0;
-#if !FG_F64
-    // FG_POLL_WORDS=0: the mirror + release form everywhere (the A/B switch of the result words)
-    const char* w = getenv("FG_POLL_WORDS");
-    if (!P->spin || (w && atoi(w) == 0)) return FG_OK;
+    if (!P->words) return FG_OK;      // the mirror + release form everywhere (fp64 build, no spinning, or the A/B switch of the result words)
     P->n_gran = 8 * n;
     FG_HIP_CHECK(hipHostMalloc(&P->gran, sizeof(unsigned long long) * (size_t)P->n_gran));
     for (int i = 0; i < P->n_gran; ++i) P->gran[i] = 0ull;
-#endif
     return FG_OK;
 }
 
@@ -122,12 +116,13 @@ int fg_solve_infos_report(const fg_state* s, int count, fg_solve_info* info_host
 #include <map>
 #include <vector>
 #include <string>
+int fg_htrace_on = 0, fg_roctx_on = 0;      // the process-scope switches as read below (fg_switches.h)
 namespace {
 struct HTrace {
     bool on; const char* last; std::chrono::steady_clock::time_point t;
     struct Row { long long n = 0; double sum = 0, mn = 1e30; std::vector<float> v; };
     std::map<std::string, Row> sum;
-    HTrace() : on(false), last(nullptr) { const char* e = getenv("FG_HTRACE"); on = e && atoi(e) != 0; }
+    HTrace() : on(false), last(nullptr) { on = fg_htrace_on = fg_switch_parse(getenv("FG_HTRACE"), FG_SW_OFF, 0); }
     ~HTrace() {
         if (!on) return;
         for (auto& kv : sum) {
@@ -162,8 +157,7 @@ struct Roctx {
     int (*push)(const char*) = nullptr;
     int (*pop)() = nullptr;
     Roctx() {
-        const char* e = getenv("FG_ROCTX");
-        if (!(e && atoi(e) != 0)) return;
+        if (!(fg_roctx_on = fg_switch_parse(getenv("FG_ROCTX"), FG_SW_OFF, 0))) return;
         for (const char* lib : {"librocprofiler-sdk-roctx.so", "librocprofiler-sdk-roctx.so.1", "libroctx64.so", "libroctx64.so.4"}) {
             void* h = dlopen(lib, RTLD_NOW | RTLD_GLOBAL);
             if (!h) continue;

@@ -32,7 +32,7 @@ int fg_prof_slot(const fg_state* cs, int kind, const int32_t* flags, int nsys, d
     if (!cs->prof.on) return -1;
     FgProf& P = const_cast<fg_state*>(cs)->prof;
     const long long k = P.launches[kind]++;
-    if (P.used >= FG_PROF_POOL || (k % P.period) != 0) return -1;
+    if (P.used >= FG_PROF_POOL || (k % cs->prof_period) != 0) return -1;
     const int slot = P.used++;
     P.meta[slot] = FgProfMeta{kind, nsys, bytes_per_sys, flops_per_sys};
     // the count goes straight into the host-pinned word (no device-to-host copy per poll: those copies were 2.6 of the headline's
@@ -86,8 +86,6 @@ extern "C" int fg_profile_enable(fg_handle s, int on) {
     }
     FG_HIP_CHECK(hipDeviceSynchronize());
     P.on = on; P.used = 0; P.prefetched = 0;
-    const char* e = getenv("FG_PROF_PERIOD");
-    P.period = e && atoi(e) > 0 ? atoi(e) : 64;   // every 64th launch of a kind is timed (8 cost the timed region ~5 %: a count kernel + two events per sample; 32 until round 4)
     for (int k = 0; k < FG_PK_COUNT; ++k) {
         P.ms[k] = P.bytes[k] = P.flops[k] = P.full_ms[k] = P.full_bytes[k] = 0.0;
         P.n[k] = P.full_n[k] = P.launches[k] = P.all_n[k] = 0;

@@ -490,11 +490,7 @@ class NativeSolver:
     def config_dump(self) -> dict:
         """The switches this handle runs under (``fg_config_dump``: the FG_* variables read at create time + the solver policies set
         through the API) plus the process environment's FG_* / FLUIDGYM_AMD_* variables."""
-        import json
-
-        buf = ctypes.create_string_buffer(4096)
-        L.check(self.lib.fg_config_dump(self.handle, buf, 4096), lib=self.lib)
-        out = json.loads(buf.value.decode())
+        out = L.read_json(self.lib.fg_config_dump, self.handle, lib=self.lib)
         out["env"] = {k: v for k, v in sorted(os.environ.items()) if k.startswith(("FG_", "FLUIDGYM_"))}
         return out
 

@@ -640,12 +640,9 @@ class MultiBlockDomain:
 
     def config_dump(self) -> dict:
         """The switches this handle runs under (``fg_mb_config_dump``) plus the process environment's FG_* / FLUIDGYM_* variables."""
-        import json
         import os
 
-        buf = ctypes.create_string_buffer(4096)
-        L.check(self.lib.fg_mb_config_dump(self.handle, buf, 4096))
-        out = json.loads(buf.value.decode())
+        out = L.read_json(self.lib.fg_mb_config_dump, self.handle)
         out["env"] = {k: v for k, v in sorted(os.environ.items()) if k.startswith(("FG_", "FLUIDGYM_"))}
         return out
 

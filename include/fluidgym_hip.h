@@ -966,6 +966,9 @@ int fg_mb_solver_counters(fg_mb_handle h, int64_t* out13_host, int32_t reset);
  * be traced to the code paths that produced it.  (No counterpart in the reference: its solver has no such switches.) */
 int fg_config_dump(fg_handle h, char* buf, int n);
 int fg_mb_config_dump(fg_mb_handle h, char* buf, int n);
+/* What a handle created NOW would read from the environment: {variable: value} for every switch of a family (0 single-block,
+ * 1 multi-block), parsed by the rules of the switch table; needs no device.  Same buffer convention as the dumps. */
+int fg_switch_values(int32_t family, char* buf, int32_t n);
 int fg_mb_solver_unconverged(fg_mb_handle h, int64_t* out4_host);   /* as fg_solver_unconverged */
 /* Simulation.single_step for such a domain (simulation.py:206-280): boundary-flux guard, per-env adaptive substeps
  * (_PISO_adaptive_step, PISOtorch_simulation.py:2004-2064), the advective-outflow PRE hook on ONE FIXED face given as

@@ -131,7 +131,7 @@ for _cap in (1, 3):
     CASES[f"press.fdcg.fused.cap{_cap}"] = _press("chan", FDCG, cap=_cap)
 CASES["press.fdcg.previous"] = _press("chan", FDCG, previous=True)
 CASES["press.fdcg.3d"] = _press("chan3", FDCG)
-CASES["press.cg.zmarch"] = _press("zm", CG, {"FG_FORCE_ZMARCH": "8"}, tol=1e-6, child=True)      # (the switch is read once per process)
+CASES["press.cg.zmarch"] = _press("zm", CG, {"FG_FORCE_ZMARCH": "8"}, tol=1e-6, child=True)      # (in a child process, as when the switch was read once per process; per handle now: test_gpu_switch_per_handle.py)
 CASES["f64.press.fdcg"] = _press("chan", FDCG, lib="f64", tol=1e-12)
 
 TRANSPORTS = {"words0": {"FG_POLL_WORDS": "0"}, "spin0": {"FG_POLL_SPIN": "0"}}
@@ -226,7 +226,7 @@ def _solve_here(spec):
 
 
 def _child(name, path):
-    """(entry of the child process of a case whose switch is read once per process)"""
+    """(entry of the child process of a case that runs in a process of its own)"""
     np.savez(path, **_solve_here(CASES[name]))
 
 
