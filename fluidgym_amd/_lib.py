@@ -139,6 +139,21 @@ class FgNoiseSegment(Structure):
     ]
 
 
+class FgNormSegment(Structure):
+    """One tensor of a ``fg_obs_normalize`` launch (``fg_norm_segment``): ``dst[r][i] = (src[r][i] - mean) * rstd`` with the record
+    ``mean``, ``m2`` (device fp64 ``[n]``, or ``[1]`` pooled), strides in elements."""
+    _fields_ = [
+        ("src", c_void_p),
+        ("dst", c_void_p),
+        ("src_stride", c_int64),
+        ("dst_stride", c_int64),
+        ("n", c_int32),
+        ("pooled", c_int32),
+        ("mean", c_void_p),
+        ("m2", c_void_p),
+    ]
+
+
 class FgStepOptions(Structure):
     _fields_ = [
         ("corrector_steps", c_int32),
@@ -307,6 +322,10 @@ SIGNATURES = {
                                  POINTER(FgRenderCamera), POINTER(FgRenderOptions), c_int32, c_int32, POINTER(c_int32), c_int32, c_void_p,
                                  c_void_p]),
     "fg_obs_noise_add": (c_int, [POINTER(FgNoiseSegment), c_int32, c_int32, c_int32, ctypes.c_uint64, c_void_p, c_void_p, c_void_p]),
+    "fg_obs_normalize": (c_int, [POINTER(FgNormSegment), c_int32, c_int32, c_int32, c_int64, c_int64, c_void_p, c_int32, c_int32,
+                                 ctypes.c_double, ctypes.c_double, c_void_p]),
+    "fg_obs_return_normalize": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, ctypes.c_double, c_int64,
+                                        ctypes.c_double, ctypes.c_double, c_int32, c_void_p]),
     "fg_baseline_opposition": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, POINTER(c_int32), POINTER(ctypes.c_double), c_int32,
                                        c_int32, c_void_p, c_void_p]),
     "fg_baseline_pd": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, ctypes.c_double, ctypes.c_double,

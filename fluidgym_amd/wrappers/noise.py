@@ -23,7 +23,7 @@ import torch
 
 from .. import _lib as L
 from .fluid_wrapper import FluidWrapper
-from .util import leading_dims
+from .util import leading_dims, pop_state_entry, push_state_entry
 
 MAX_SEGMENTS = 8            # segments of one fg_obs_noise_add launch (csrc/fg_obsnoise.hip)
 ACTION_TAG = 128            # the tag of the action tensor; observation keys take their index in the sorted key list (< 128)
@@ -135,28 +135,12 @@ class CounterNoiseWrapper(FluidWrapper):
         return self._counters
 
     # ---- state: the inner state with this wrapper's counters under a key of its own
-    def _own_keys(self, state: dict) -> List[str]:
-        keys, i = [], 0
-        while (self._state_key if i == 0 else f"{self._state_key}#{i}") in state:
-            keys.append(self._state_key if i == 0 else f"{self._state_key}#{i}")
-            i += 1
-        return keys
-
     def get_state(self):
-        inner = self._env.get_state()
-        if not isinstance(inner, dict):
-            raise TypeError(f"{type(self).__name__}.get_state: the wrapped env's state is not a dict")
-        state = dict(inner)
-        taken = len(self._own_keys(state))       # wrappers of this kind further in took the lower numbers
-        state[self._state_key if taken == 0 else f"{self._state_key}#{taken}"] = None if self._counters is None else self._counters.clone()
-        return state
+        return push_state_entry(self._env.get_state(), self._state_key, None if self._counters is None else self._counters.clone(),
+                                type(self).__name__)
 
     def set_state(self, state) -> None:
-        mine = self._own_keys(state)
-        if not mine:
-            raise KeyError(f"{type(self).__name__}.set_state: the state holds no '{self._state_key}' entry")
-        rest = dict(state)
-        counters = rest.pop(mine[-1])
+        rest, counters = pop_state_entry(state, self._state_key, type(self).__name__)
         self._env.set_state(rest)
         self._counters = None if counters is None else counters.clone()
         self._row_ids = None

@@ -1,7 +1,7 @@
 """Space helpers of the wrappers (reference ``fluidgym/wrappers/util.py``), on ``fluidgym_amd.spaces``."""
 from __future__ import annotations
 
-from typing import List, Optional
+from typing import List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -47,3 +47,32 @@ def leading_dims(tensor: torch.Tensor, space) -> int:
     if lead < 0 or tuple(tensor.shape[lead:]) != tuple(space.shape):
         raise ValueError(f"a tensor of shape {tuple(tensor.shape)} does not end in the shape {tuple(space.shape)} of its space")
     return lead
+
+
+def numbered_state_keys(state: dict, key: str) -> List[str]:
+    """The entries ``key``, ``key#1``, ``key#2``, ... that ``state`` holds, in that order: wrappers of one kind nested in each other
+    keep their ``get_state()`` entries apart by number, the innermost taking the bare key."""
+    keys, i = [], 0
+    while (key if i == 0 else f"{key}#{i}") in state:
+        keys.append(key if i == 0 else f"{key}#{i}")
+        i += 1
+    return keys
+
+
+def push_state_entry(inner, key: str, value, who: str) -> dict:
+    """A copy of the wrapped env's state ``inner`` with ``value`` under the next free number of ``key``."""
+    if not isinstance(inner, dict):
+        raise TypeError(f"{who}.get_state: the wrapped env's state is not a dict")
+    state = dict(inner)
+    taken = len(numbered_state_keys(state, key))       # wrappers of this kind further in took the lower numbers
+    state[key if taken == 0 else f"{key}#{taken}"] = value
+    return state
+
+
+def pop_state_entry(state, key: str, who: str) -> Tuple[dict, object]:
+    """``(rest, value)``: the highest-numbered ``key`` entry of ``state`` -- the outermost wrapper's -- and the state without it."""
+    mine = numbered_state_keys(state, key)
+    if not mine:
+        raise KeyError(f"{who}.set_state: the state holds no '{key}' entry")
+    rest = dict(state)
+    return rest, rest.pop(mine[-1])

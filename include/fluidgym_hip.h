@@ -802,6 +802,48 @@ typedef struct fg_noise_segment {
 int fg_obs_noise_add(const fg_noise_segment* seg, int32_t n_seg, int32_t rows, int32_t dtype, uint64_t seed,
                      const uint32_t* counters, const int32_t* row_ids, void* stream);
 
+/* ---- running normalisation of observations and rewards of a batch (fp32 library only; csrc/fg_obsnorm.hip) ----
+ * A row is one space-shaped item.  Every statistic slot keeps the record (n, mean, M2): n rows merged so far, a HOST integer passed by
+ * value, mean and M2 fp64 on the device.  One update with the selected rows R (m = |R|), all in fp64, every operation rounded on its own:
+ *   mean_b = sum_{r in R} x[r] / m;  M2_b = sum_{r in R} (x[r] - mean_b)^2                       (two passes)
+ *   delta = mean_b - mean_a;  n = n_a + m;  mean = mean_a + delta * (m / n);  M2 = M2_a + M2_b + delta^2 * (n_a * m / n)
+ *   (n_a = 0: the record's memory is not read, the merge returns the batch)
+ * and every row, selected or not, is normalised with the record after the update:
+ *   rstd = 1 / sqrt(M2 / n + epsilon);  y = (x - mean) * rstd, clipped to [-clip, clip] where clip > 0, rounded once to `dtype`.
+ * fg_obs_normalize
+ *   seg       HOST array of n_seg segments (copied into the kernel arguments), one tensor of an observation dict each: src, dst device
+ *             pointers of `dtype`; src_stride, dst_stride in elements between rows; n contiguous elements per row; mean, m2 device
+ *             double [n] (pooled = 0: one slot per element) or [1] (pooled = 1: one slot per key over rows and elements, whose count
+ *             is n_rows * n).  dst == src is allowed, any other overlap is not
+ *   dtype     0: float, 1: double (an fp64 env's tensors go through this entry of the fp32 library)
+ *   n_before  rows in the record before the call; n_add: rows this call merges (m when update != 0, else 0)
+ *   row_list  device int32 [n_rows_sel] of ascending rows, or NULL: all rows;  update: 0 only normalises (the record is not written)
+ *   Element slots, updating or frozen: the whole dict is ONE launch; statistics, merge and normalisation of a column happen in the
+ *   workgroup that owns it.  Pooled slots while updating take one launch more (reduce and merge, then normalise).
+ * fg_obs_return_normalize: G[r] = gamma * G[r] + reward[r] (G fp64 [rows] on the device), the update above of the one scalar record
+ *   stats = {mean, M2} (device double [2]) with R = every G of this call, and out[r] = reward[r] * rstd (no mean subtraction), clipped
+ *   where clip > 0.  One workgroup, one launch.  update = 0 only scales; G still advances.
+ * Order rule: the order of every sum is a function of (m, n, pooled) alone -- each lane adds its rows in ascending order, the lanes of
+ * a wave combine by the xor butterfly, the waves in ascending order (written out at the top of csrc/fg_obsnorm.hip) -- not of the
+ * load form (16-byte words where bases, pitches and n allow, single elements otherwise: the same bits), the addresses or the timing.
+ * No floating-point atomic.  Asynchronous on `stream`; nothing returns to the host, nothing is allocated.
+ * Before any launch (and without a GPU) FG_ERR_INVALID_ARG: a null pointer, n_seg outside [1, 8], rows outside [1, 65535], n outside
+ * [1, 2^26], a stride smaller than n, an unknown dtype, n_add that is not the number of rows the call merges, n_before < 0,
+ * update == 0 with n_before == 0, n_rows_sel outside [1, rows] when a list is given, epsilon <= 0, gamma outside [0, 1]. */
+typedef struct fg_norm_segment {
+    const void* src;
+    void* dst;
+    int64_t src_stride, dst_stride;
+    int32_t n;
+    int32_t pooled;
+    double* mean;
+    double* m2;
+} fg_norm_segment;
+int fg_obs_normalize(const fg_norm_segment* seg, int32_t n_seg, int32_t rows, int32_t dtype, int64_t n_before, int64_t n_add,
+                     const int32_t* row_list, int32_t n_rows_sel, int32_t update, double epsilon, double clip, void* stream);
+int fg_obs_return_normalize(const void* reward, void* out, double* G, double* stats, int32_t rows, int32_t dtype, double gamma,
+                            int64_t n_before, double epsilon, double clip, int32_t update, void* stream);
+
 /* ---- baseline controllers of the TCF and RBC envs (csrc/fg_baselines.hip; both libraries, handle-free) -------------------------
  * One action of the whole batch in ONE launch each (fluidgym_amd/baselines.py).  Fields are read in place:
  * cell (env, z, y, x) is v[env * batch_stride + (z * ny + y) * nx + x] (batch_stride in reals, >= nz * ny * nx; 2-D: nz = 1).
