@@ -154,6 +154,26 @@ class FgNormSegment(Structure):
     ]
 
 
+class FgPointGrid(Structure):
+    """The grid record of ``fg_point_sample`` / ``fg_tracer_advect`` (``fg_point_grid``): extents, periodic flags, the node arrays of
+    the axes (device), the box, the velocity and the boundary velocities of the FIXED faces with their batch strides in reals."""
+    _fields_ = [
+        ("dims", c_int32),
+        ("batch", c_int32),
+        ("nx", c_int32),
+        ("ny", c_int32),
+        ("nz", c_int32),
+        ("periodic", c_int32 * 3),
+        ("nodes", c_void_p * 3),
+        ("lo", c_float * 3),
+        ("len", c_float * 3),
+        ("velocity", c_void_p),
+        ("velocity_stride", c_int64),
+        ("bvel", c_void_p * 6),
+        ("bvel_stride", c_int64 * 6),
+    ]
+
+
 class FgStepOptions(Structure):
     _fields_ = [
         ("corrector_steps", c_int32),
@@ -330,6 +350,10 @@ SIGNATURES = {
                                        c_int32, c_void_p, c_void_p]),
     "fg_baseline_pd": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, ctypes.c_double, ctypes.c_double,
                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fg_point_sample": (c_int, [POINTER(FgPointGrid), POINTER(c_void_p), POINTER(c_int64), c_int32, c_void_p, c_int64, c_int32, c_void_p,
+                                c_void_p]),
+    "fg_tracer_advect": (c_int, [POINTER(FgPointGrid), c_float, c_int32, ctypes.c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_int32, c_void_p]),
     "fg_envglue_jet_schedule": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "fg_envglue_channel_observe": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_void_p,
                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -421,6 +445,8 @@ _F64_STRUCTS[FgStepOptions] = _f64_struct(FgStepOptions)
 _F64_STRUCTS[FgSimOptions] = _f64_struct(FgSimOptions)
 _F64_STRUCTS[FgMbStepOptions] = _f64_struct(FgMbStepOptions)
 _F64_STRUCTS[FgMbSimOptions] = _f64_struct(FgMbSimOptions)
+_F64_STRUCTS[FgPointGrid] = _f64_struct(FgPointGrid)
+FgPointGridF64 = _F64_STRUCTS[FgPointGrid]
 FgStepOptionsF64, FgSimOptionsF64 = _F64_STRUCTS[FgStepOptions], _F64_STRUCTS[FgSimOptions]
 FgMbStepOptionsF64, FgMbSimOptionsF64 = _F64_STRUCTS[FgMbStepOptions], _F64_STRUCTS[FgMbSimOptions]
 _F64_KEEP_FLOAT = ("fg_set_fd_preconditioner", "fg_set_fd_fast_transform", "fg_set_fd_helmholtz", "fg_coords_to_transforms", "fg_stream_triad")

@@ -214,6 +214,20 @@ class ChannelJetEnv2D(FluidEnv):
             shear = self._nu * (u[:, 0, 0, :].mean(dim=1) + u[:, 0, -1, :].mean(dim=1)) / (0.5 * self._hy)
         return cross, shear
 
+    def _tracer_respawn_faces(self) -> tuple:
+        return ("-x", "+x")      # a tracer that leaves through the outflow (or the inflow) starts again at its seed
+
+    def _run_sim_steps(self, n: int, schedule) -> bool:
+        """The ``n`` sim steps of an env step: one ``multi_step`` call -- or, while a tracer cloud is active, one call per sim step
+        (the same arithmetic in the same order) with the cloud advected in between."""
+        if self._tracers is None:
+            return self._sim.multi_step(n, schedule)
+        for k in range(n):
+            if not self._sim.multi_step(1, None if schedule is None else {f: t[k: k + 1] for f, t in schedule.items()}):
+                return False
+            self._advect_tracers()
+        return True
+
     def _step_native(self, action: torch.Tensor):
         """``_step_impl`` with the schedule and the observation by ``fg_envglue_*`` (same values: the schedule to the bit, the means to
         fp32 rounding of a different summation order)."""
@@ -231,7 +245,7 @@ class ChannelJetEnv2D(FluidEnv):
             L.check(lib.fg_envglue_jet_schedule(target.data_ptr(), self._current_action.contiguous().data_ptr(), self._decay.data_ptr(),
                                                 self._jet_rows.data_ptr(), n, B, X, jets.data_ptr(), last.data_ptr(), stream))
             self._jets = jets
-        if not self._sim.multi_step(n, {2: jets[:, 0], 3: jets[:, 1]} if self._enable_actions else None):
+        if not self._run_sim_steps(n, {2: jets[:, 0], 3: jets[:, 1]} if self._enable_actions else None):
             raise RuntimeError("simulation step failed")
         if self._enable_actions:
             self._current_action = last
@@ -265,7 +279,7 @@ class ChannelJetEnv2D(FluidEnv):
             self._jets = jets          # (the walls stay bound to their last slices after the step)
         # the n sim steps of this env step in one native call (fg_multi_step): before sim step k the walls are BOUND to that step's
         # slices (the same wall-normal velocity on both: zero net flux) -- a pointer update, no copy launch
-        if not self._sim.multi_step(n, {2: jets[:, 0], 3: jets[:, 1]} if self._enable_actions else None):
+        if not self._run_sim_steps(n, {2: jets[:, 0], 3: jets[:, 1]} if self._enable_actions else None):
             raise RuntimeError("simulation step failed")
         if self._enable_actions:
             self._current_action = controls[n - 1]

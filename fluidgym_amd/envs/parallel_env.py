@@ -643,6 +643,15 @@ class ParallelFluidEnv:
     def set_state_bank(self, states, env: Optional[int] = None) -> None:
         raise NotImplementedError("set_state_bank is not implemented for ParallelFluidEnv.")
 
+    def probe(self, points, fields=None):
+        raise NotImplementedError("probe is not implemented for ParallelFluidEnv.")
+
+    def start_tracers(self, n: int, seed: Optional[int] = None, positions=None, substeps: int = 4, every: int = 1):
+        raise NotImplementedError("start_tracers is not implemented for ParallelFluidEnv.")
+
+    def stop_tracers(self):
+        raise NotImplementedError("stop_tracers is not implemented for ParallelFluidEnv.")
+
     def save_gif(self, filename: str, output_path=None) -> None:
         raise NotImplementedError("save_gif is not implemented for ParallelFluidEnv.")
 

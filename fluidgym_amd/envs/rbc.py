@@ -442,6 +442,8 @@ class RBCEnvBase(FlowStatisticsMixin, FluidEnv):
                 self._record_time_correlation_sample()
             if self._flow_hist is not None:
                 self._record_histogram_sample()
+            if self._tracers is not None:
+                self._advect_tracers()
         nu = self.compute_global_nusselt()
         obs = self._get_global_obs()
         return obs, self.nu_ref - nu, False, {"nusselt": nu}

@@ -379,6 +379,8 @@ class TCF3DBottomEnv(FlowStatisticsMixin, FluidEnv):
                 self._record_time_correlation_sample()
             if self._flow_hist is not None:
                 self._record_histogram_sample()
+            if self._tracers is not None:
+                self._advect_tracers()
             tb.append(b)
             tt.append(t)
         tau_bottom, tau_top = torch.stack(tb).mean(dim=0), torch.stack(tt).mean(dim=0)

@@ -871,6 +871,51 @@ int fg_baseline_pd(const fg_real* v, int64_t batch_stride, int32_t batch, int32_
                    const double* wy, double kp, double kd_over_dt, double* e_state, int32_t* first, uint64_t* tickets,
                    fg_real* action, void* stream);
 
+/* ---- point probes and Lagrangian tracers on a single-block grid (csrc/fg_tracers.hip; both libraries, handle-free) -------------
+ * Both entry points share one interpolant of the cell-centred fields of a stretched rectilinear grid (fluidgym_amd/simulation/
+ * tracers.py).  fg_point_grid is a HOST record, read during the call: the fields are read in place, cell
+ * (env, c, z, y, x) of the velocity is velocity[env * velocity_stride + ((c * nz + z) * ny + y) * nx + x], the boundary velocities
+ * bvel[f] (f = 2 * axis + side, NULL on periodic axes) have extent 1 along their normal axis, as for fg_env_restore_field.
+ *   nodes[a]   DEVICE array of the axis' nodes: the n cell centres on a periodic axis; the low face, the n centres and the high face
+ *              (n + 2) on a FIXED one.  lo[a], len[a]: the low face and the length of the box along the axis.
+ * A position is wrapped into [lo, lo + len) on a periodic axis (the interval between the last and the first centre spans the seam) and
+ * clamped to [nodes[0], nodes[n + 1]], the face nodes, on a FIXED one; its interval is found by an integer binary search over the node array, staged in LDS,
+ * and clamped to a valid interval before any load -- a NaN compares false everywhere and lands in interval 0; a position becomes an
+ * index in no other way.  The value is the multilinear blend of the 2^d corners (x, then y, then z) with w = (x - node_i) /
+ * (node_i+1 - node_i) and a + w (b - a), b itself at w == 1.  A centre node reads the field; a face node reads, for the velocity, that
+ * face's bvel at the corner's other indices (the first axis in the order y, x, z where a corner is a face node on several) and, for
+ * the extra fields, the adjacent cell.
+ * fg_point_sample: out[env][p][0..d) = the velocity, out[env][p][d + k] = extra[k] (HOST tables of n_extra <= 8 device pointers to
+ *   [batch][nz][ny][nx] fields and their batch strides, e.g. pressure and a scalar channel) at points[env * points_env_stride + p * d
+ *   + a]; points_env_stride = 0: one point set for all envs.
+ * fg_tracer_advect: `substeps` midpoint steps of h = dt / substeps in the frozen field, x* = x + h/2 u(x), x <- x + h u(x*), for the
+ *   n_tracers tracers of every env (pos, seed_pos [batch][n][d], age [batch][n], wraps [batch][n][d] int32, lost [batch] uint32).
+ *   After every sub-step: a non-finite position respawns (position := seed position, wraps := 0, age := 0 at the end of the call)
+ *   and adds 1 to lost[env] (an integer atomic); else, per axis: a periodic axis wraps the position and adds the signed number of
+ *   crossings to wraps, so that pos + wraps * len is the unwrapped path; beyond a FIXED face whose bit f is set in respawn_faces the
+ *   tracer respawns; beyond any other FIXED face the position is clamped to the face.  age grows by dt per call.
+ * One thread per point / tracer, grid (ceil(n / 256), batch); an env's tracers read that env's fields alone, there is no
+ * floating-point atomic, so a result depends neither on the batch nor on the launch order and repeats bit for bit.  Asynchronous on
+ * `stream`; nothing returns to the host.  Before any launch (and without a GPU) FG_ERR_INVALID_ARG: a null pointer, dims not 2 or 3,
+ * a non-positive extent (nz != 1 in 2-D), a periodic flag that is not 0 / 1, a non-finite lo or a len that is not positive and
+ * finite, a missing bvel on a FIXED axis, substeps < 1, n_points / n_tracers < 1, n_extra outside 0..8, batch outside 1..65535, a
+ * stride smaller than its field, a respawn bit of a face the grid does not have, a non-finite dt, more than 2^30 cells per env;
+ * FG_ERR_UNSUPPORTED: node arrays of more than 32 KiB. */
+typedef struct fg_point_grid {
+    int32_t dims, batch, nx, ny, nz;     /* nz = 1 in 2-D */
+    int32_t periodic[3];                 /* x, y, z */
+    const fg_real* nodes[3];
+    fg_real lo[3], len[3];
+    const fg_real* velocity;
+    int64_t velocity_stride;
+    const fg_real* bvel[6];
+    int64_t bvel_stride[6];
+} fg_point_grid;
+int fg_point_sample(const fg_point_grid* g, const fg_real* const* extra, const int64_t* extra_stride, int32_t n_extra,
+                    const fg_real* points, int64_t points_env_stride, int32_t n_points, fg_real* out, void* stream);
+int fg_tracer_advect(const fg_point_grid* g, fg_real dt, int32_t substeps, uint32_t respawn_faces, const fg_real* seed_pos,
+                     fg_real* pos, fg_real* age, int32_t* wraps, uint32_t* lost, int32_t n_tracers, void* stream);
+
 /* ---- env glue either side of the n sim steps of an env step (fp32 library only) ------------------------------
  * fg_envglue_jet_schedule: the action smoothing of the reference's jet envs (cylinder_env_base.py:748-753, a_k = a_{k-1} +
  * alpha (target - a_{k-1}) before every sim step) for the n sim steps of one env step at once: control[k][b] = target[b] +
