@@ -21,6 +21,7 @@ from .config import config  # noqa: F401
 from .simulation.policy import get_solver_policy, set_solver_policy  # noqa: F401
 from .baselines import OppositionControl, PDControl, run_baseline_episodes  # noqa: F401
 from .simulation.tracers import PointGrid, TracerCloud, sample_points  # noqa: F401
+from .simulation.mb_tracers import MbPointMesh, MeshProbes, MeshTracerCloud, build_point_tables  # noqa: F401
 
 __version__ = "0.1.0"
 

@@ -174,6 +174,37 @@ class FgPointGrid(Structure):
     ]
 
 
+class FgMbPointMesh(Structure):
+    """The mesh record of ``fg_mb_point_locate`` / ``fg_mb_point_sample`` / ``fg_mb_tracer_advect`` (``fg_mb_point_mesh``): sizes, the
+    device tables of ``simulation/mb_tracers.MbPointMesh``, ``slack``, the periodic shift vectors (row ``s`` at ``3 s``), the velocity
+    and the boundary velocity with their strides in reals."""
+    _fields_ = [
+        ("dims", c_int32),
+        ("batch", c_int32),
+        ("n_cells", c_int32),
+        ("n_slots", c_int32),
+        ("n_vertices", c_int32),
+        ("kv", c_int32),
+        ("kc", c_int32),
+        ("n_shifts", c_int32),
+        ("cell_vert", c_void_p),
+        ("cell_xyz", c_void_p),
+        ("neighbors", c_void_p),
+        ("face_code", c_void_p),
+        ("vel_idx", c_void_p),
+        ("vel_w", c_void_p),
+        ("cell_idx", c_void_p),
+        ("cell_w", c_void_p),
+        ("slack", c_float),
+        ("shifts", c_float * 12),
+        ("velocity", c_void_p),
+        ("velocity_stride", c_int64),
+        ("bvel", c_void_p),
+        ("bvel_stride", c_int64),
+        ("bvel_comp_stride", c_int64),
+    ]
+
+
 class FgStepOptions(Structure):
     _fields_ = [
         ("corrector_steps", c_int32),
@@ -354,6 +385,12 @@ SIGNATURES = {
                                 c_void_p]),
     "fg_tracer_advect": (c_int, [POINTER(FgPointGrid), c_float, c_int32, ctypes.c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_int32, c_void_p]),
+    "fg_mb_point_locate": (c_int, [POINTER(FgMbPointMesh), c_void_p, c_int64, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
+                                   c_void_p]),
+    "fg_mb_point_sample": (c_int, [POINTER(FgMbPointMesh), POINTER(c_void_p), POINTER(c_int64), c_int32, c_void_p, c_void_p, c_int64,
+                                   c_int32, c_void_p, c_void_p]),
+    "fg_mb_tracer_advect": (c_int, [POINTER(FgMbPointMesh), c_float, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_int32, c_void_p]),
     "fg_envglue_jet_schedule": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "fg_envglue_channel_observe": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_void_p,
                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -447,6 +484,8 @@ _F64_STRUCTS[FgMbStepOptions] = _f64_struct(FgMbStepOptions)
 _F64_STRUCTS[FgMbSimOptions] = _f64_struct(FgMbSimOptions)
 _F64_STRUCTS[FgPointGrid] = _f64_struct(FgPointGrid)
 FgPointGridF64 = _F64_STRUCTS[FgPointGrid]
+_F64_STRUCTS[FgMbPointMesh] = _f64_struct(FgMbPointMesh)
+FgMbPointMeshF64 = _F64_STRUCTS[FgMbPointMesh]
 FgStepOptionsF64, FgSimOptionsF64 = _F64_STRUCTS[FgStepOptions], _F64_STRUCTS[FgSimOptions]
 FgMbStepOptionsF64, FgMbSimOptionsF64 = _F64_STRUCTS[FgMbStepOptions], _F64_STRUCTS[FgMbSimOptions]
 _F64_KEEP_FLOAT = ("fg_set_fd_preconditioner", "fg_set_fd_fast_transform", "fg_set_fd_helmholtz", "fg_coords_to_transforms", "fg_stream_triad")

@@ -30,6 +30,7 @@ from .cylinder_grid import BOTTOM, LEFT, RIGHT, TOP, build_domain, extrude_mesh,
 from .flow_statistics import FieldStatisticsMixin, FlowStatisticsMixin
 from .fluid_env import FluidEnv, is_per_env, per_env_parameter, refuse_per_env
 from .forces import WallRing
+from .tracers import MeshTracerMixin
 
 CYLINDER_JET_2D_DEFAULT_CONFIG = {
     "reynolds_number": 1e2, "resolution": 24, "dt": 1e-2, "adaptive_cfl": 0.8, "step_length": 0.25,
@@ -45,7 +46,7 @@ ONCHIP_PCG_MAX_CELLS = 24 * 1024   # the multilevel-preconditioned on-chip CG (2
 VORTICITY_RENDER_LEVELS = {100: 1.5, 250: 2.5, 500: 3.5}   # jet_cylinder_env_3d.py:15-19: level of the 3-D picture, by Reynolds number
 
 
-class CylinderEnvBase(FieldStatisticsMixin, FlowStatisticsMixin, FluidEnv):      # (multi-block: the plane statistics refuse with
+class CylinderEnvBase(MeshTracerMixin, FieldStatisticsMixin, FlowStatisticsMixin, FluidEnv):      # (multi-block: the plane statistics refuse with
                                                                                  # NotImplementedError, the per-cell ones record)
     _supports_marl = False
     _action_smoothing_alpha: float = 0.1
@@ -334,6 +335,8 @@ class CylinderEnvBase(FieldStatisticsMixin, FlowStatisticsMixin, FluidEnv):     
             self._sim.single_step()
             if self._field_stats is not None:
                 self._record_field_sample()
+            if self._mesh_tracers is not None:
+                self._advect_mesh_tracers()
             self._ring.forces(self._domain, self._nu_forces, layer_height=self.D / self._circle_resolution_angular, out=raw[k])
         self._last_control_mirror = (self._last_control, c_last)
         obs = self._get_global_obs()

@@ -652,6 +652,15 @@ class ParallelFluidEnv:
     def stop_tracers(self):
         raise NotImplementedError("stop_tracers is not implemented for ParallelFluidEnv.")
 
+    def locate_probes(self, points, strict: bool = True):
+        raise NotImplementedError("locate_probes is not implemented for ParallelFluidEnv.")
+
+    def start_mesh_tracers(self, n: int, seed: Optional[int] = None, positions=None, substeps: int = 4, every: int = 1):
+        raise NotImplementedError("start_mesh_tracers is not implemented for ParallelFluidEnv.")
+
+    def stop_mesh_tracers(self):
+        raise NotImplementedError("stop_mesh_tracers is not implemented for ParallelFluidEnv.")
+
     def save_gif(self, filename: str, output_path=None) -> None:
         raise NotImplementedError("save_gif is not implemented for ParallelFluidEnv.")
 

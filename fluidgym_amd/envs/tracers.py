@@ -7,6 +7,7 @@ from __future__ import annotations
 
 from typing import Optional, Sequence
 
+import numpy as np
 import torch
 
 from ..simulation.domain import Domain
@@ -80,3 +81,128 @@ class TracerMixin:
             raise RuntimeError("set_state: the state holds a tracer cloud but none is active; call start_tracers() with its size first")
         self._tracers.load_state_dict(state["cloud"])
         self._tracers_every, self._tracers_tick = int(state["every"]), int(state["tick"])
+
+
+class MeshTracerMixin:
+    """``locate_probes`` and ``start_mesh_tracers`` / ``stop_mesh_tracers`` of the multi-block envs (cylinder, airfoil): point probes at
+    physical positions of the curvilinear mesh, located once and sampled in one launch (``simulation/mb_tracers.MeshProbes``), and a
+    cloud of Lagrangian tracers (``MeshTracerCloud``) advected on the GPU after every ``every``-th sim step of ``step()`` while it is
+    active.  Tracers that reach the inflow or an outflow face return to their seeds; walls and jets stop them.  ``reset()`` reseeds
+    every env's tracers, ``reset_envs(envs)`` those of the chosen envs; ``get_state()`` carries the cloud under ``"mesh_tracers"`` while
+    one is active; ``close()`` drops cloud and mesh tables.  Without an active cloud the step path launches nothing."""
+    _mesh_tracers = None
+    _mesh_tracers_every: int = 1
+    _mesh_tracers_tick: int = 0
+    _point_mesh = None
+
+    def _require_multi_block(self, entry: str):
+        from ..simulation.mb_tracers import MbPointMesh
+        from ..simulation.multiblock import MultiBlockDomain
+
+        if getattr(self, "_domain", None) is None:
+            raise RuntimeError(f"{entry}: reset() the env first (the domain does not exist yet)")
+        if not isinstance(self._domain, MultiBlockDomain):
+            raise NotImplementedError(f"{entry} needs a multi-block domain (cylinder, airfoil envs); single-block envs have probe and "
+                                      "start_tracers")
+        if self._point_mesh is None or self._point_mesh.domain is not self._domain:
+            self._point_mesh = MbPointMesh(self._domain)
+        return self._point_mesh
+
+    def _require_single_block(self, entry: str) -> None:
+        try:
+            super()._require_single_block(entry)
+        except NotImplementedError as e:
+            raise NotImplementedError(f"{e}; multi-block envs have locate_probes, start_mesh_tracers and stop_mesh_tracers") from None
+
+    @property
+    def mesh_tracers(self):
+        """The active ``MeshTracerCloud``, or None."""
+        return self._mesh_tracers
+
+    def locate_probes(self, points, strict: bool = True):
+        """``MeshProbes`` at the physical positions ``points`` (``[P, d]`` for every env, or ``[B, P, d]``): located once here;
+        ``.sample(fields)`` is one launch per call.  ``strict``: a point outside the fluid is a ``ValueError``."""
+        from ..simulation.mb_tracers import MeshProbes
+
+        return MeshProbes(self._require_multi_block("locate_probes"), points, strict=strict)
+
+    def _mesh_respawn_faces(self) -> list:
+        """The ``(block, face)`` pairs at which a tracer returns to its seed: the inflow face of the left block and the outflow faces."""
+        mesh = self._mesh
+        return [(0, "-x")] + list(getattr(mesh, "outflows", None) or [mesh.outflow])
+
+    def _mesh_respawn_slots(self) -> np.ndarray:
+        from ..simulation.multiblock import face_index
+
+        dom = self._domain
+        mask = np.zeros(max(dom.n_boundary_faces, 1), np.uint8)
+        for b, face in self._mesh_respawn_faces():
+            blk, f = dom.blocks[b], face_index(face)
+            s0 = blk.boundary_slot0[f]
+            if s0 < 0:
+                raise ValueError(f"face {face} of block {blk.name} is not a FIXED boundary")
+            mask[s0:s0 + blk.face_cells(f)] = 1
+        return mask[:dom.n_boundary_faces]
+
+    def start_mesh_tracers(self, n: int, seed: Optional[int] = None, positions=None, substeps: int = 4, every: int = 1):
+        """Start a fresh cloud of ``n`` tracers per env (``MeshTracerCloud``: ``seed`` or ``positions``); after every ``every``-th sim step
+        of ``step()`` it is advanced by ``every`` sim time steps in the velocity field of that moment."""
+        from ..simulation.mb_tracers import MeshTracerCloud
+
+        mesh = self._require_multi_block("start_mesh_tracers")
+        if int(every) < 1:
+            raise ValueError(f"every must be at least 1, got {every}")
+        self._mesh_tracers = MeshTracerCloud(mesh, n, seed=seed, positions=positions, substeps=substeps,
+                                             respawn_slots=self._mesh_respawn_slots().astype(bool))
+        self._mesh_tracers_every, self._mesh_tracers_tick = int(every), 0
+        return self._mesh_tracers
+
+    def stop_mesh_tracers(self):
+        """Stop advecting and hand out the cloud."""
+        self._require_multi_block("stop_mesh_tracers")
+        if self._mesh_tracers is None:
+            raise RuntimeError("stop_mesh_tracers: no tracers are active")
+        cloud, self._mesh_tracers = self._mesh_tracers, None
+        return cloud
+
+    def _advect_mesh_tracers(self) -> None:
+        """Called after a sim step while a cloud is active.  Every ``single_step()`` of ``MultiBlockSimulation`` advances the flow by
+        exactly ``time_step`` (the adaptive CFL only splits that interval into sub-steps inside the call), so the ``every`` sim steps
+        since the last advance lasted ``every * time_step`` whatever their sub-steps were: tracer time equals sim time."""
+        self._mesh_tracers_tick += 1
+        if self._mesh_tracers_tick % self._mesh_tracers_every == 0:
+            self._mesh_tracers.advect(self._mesh_tracers_every * float(self._sim.time_step))
+
+    def reset(self, *args, **kw):
+        out = super().reset(*args, **kw)
+        if self._mesh_tracers is not None:
+            self._mesh_tracers.reseed()
+            self._mesh_tracers_tick = 0
+        return out
+
+    def reset_envs(self, envs, *args, **kw):
+        out = super().reset_envs(envs, *args, **kw)
+        if self._mesh_tracers is not None:
+            self._mesh_tracers.reseed(envs)
+        return out
+
+    def get_state(self) -> dict:
+        state = super().get_state()
+        if self._mesh_tracers is not None:
+            state["mesh_tracers"] = {"cloud": self._mesh_tracers.state_dict(), "every": self._mesh_tracers_every,
+                                     "tick": self._mesh_tracers_tick}
+        return state
+
+    def set_state(self, state: dict) -> None:
+        super().set_state(state)
+        if "mesh_tracers" in state:
+            if self._mesh_tracers is None:
+                raise RuntimeError("set_state: the state holds a mesh tracer cloud but none is active; call start_mesh_tracers() with its "
+                                   "size first")
+            saved = state["mesh_tracers"]
+            self._mesh_tracers.load_state_dict(saved["cloud"])
+            self._mesh_tracers_every, self._mesh_tracers_tick = int(saved["every"]), int(saved["tick"])
+
+    def close(self) -> None:
+        self._mesh_tracers = self._point_mesh = None      # (they hold the closed domain)
+        super().close()

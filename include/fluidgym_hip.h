@@ -916,6 +916,65 @@ int fg_point_sample(const fg_point_grid* g, const fg_real* const* extra, const i
 int fg_tracer_advect(const fg_point_grid* g, fg_real dt, int32_t substeps, uint32_t respawn_faces, const fg_real* seed_pos,
                      fg_real* pos, fg_real* age, int32_t* wraps, uint32_t* lost, int32_t n_tracers, void* stream);
 
+/* ---- point probes and Lagrangian tracers on a curvilinear multi-block mesh (csrc/fg_mb_tracers.hip; both libraries, handle-free) --
+ * One interpolant for the three entry points (fluidgym_amd/simulation/mb_tracers.py).  fg_mb_point_mesh is a
+ * HOST record, read during the call; its tables are DEVICE arrays built once by the host (mb_tracers.build_point_tables):
+ *   cell_vert [n_cells][2^d]      merged vertex ids of a cell's corners (corner k: bit 0 = x, bit 1 = y, bit 2 = z)
+ *   cell_xyz  [n_cells][2^d][d]   the corners' positions as the cell's own block stores them
+ *   neighbors [2d][n_cells]       the neighbour cell across face f = 2 * axis + side, or -1 - slot on a FIXED face
+ *   face_code [2d][n_cells]       0, or 1 + 2 s (+ 1): crossing the face shifts the position by -shifts[s] (by +shifts[s]) and adds
+ *                                 +1 (-1) to the crossing count s
+ *   vel_idx, vel_w   [n_vertices][kv]   the velocity stencil of a vertex in ELL form (a weight of 0 is padding; an index >= n_cells
+ *                                       names boundary slot index - n_cells);  cell_idx, cell_w [n_vertices][kc]: cell-only fields
+ *   shifts[3 s + a]  the n_shifts <= 4 periodic vectors;  slack: the resolution of the local coordinates, in (0, 0.25)
+ * The fields are read in place: velocity[env * velocity_stride + c * n_cells + cell], bvel[env * bvel_stride + c * bvel_comp_stride
+ * + slot].  A vertex value is sum_k w_k phi_k in table order; the value at (cell, xi) is the multilinear blend of the 2^d vertex
+ * values (x, then y, then z; a + w (b - a), b itself at w == 1).
+ * fg_mb_point_locate: walks from start_cell (clamped to 0..n_cells-1) to the cell of points[env * points_env_stride + p * d + a]
+ *   (points_env_stride = 0: one point set and one start_cell[n_points] for all envs; else n_points * d and start_cell[batch][n_points]):
+ *   Newton on the cell map from xi = 1/2 (at most 8 iterations, iterates clamped to [-1, 2]^d, stop below slack / 4); inside where
+ *   xi in [-slack, 1 + slack]^d; else through the most violated face that has a neighbour; at most max_walk cell changes.
+ *   cell_out, status_out [batch][n_points], xi_out [batch][n_points][d] (clamped to [0, 1]^d).  status 0: found; 1: outside (every
+ *   violated face is FIXED: the point stays in that cell); 2: not found (walk exhausted, or a NaN).
+ * fg_mb_point_sample: out[env][p][0..d) = the velocity, out[env][p][d + k] = extra[k] (HOST tables of n_extra <= 8 device pointers to
+ *   [batch][n_cells] fields and their batch strides) at cell[env * cell_env_stride + p], xi[(env * cell_env_stride + p) * d + a]; the
+ *   cell index is clamped to 0..n_cells-1 and xi to [0, 1]^d (a NaN: 0) before any load.  One launch, no walk.
+ * fg_mb_tracer_advect: `substeps` midpoint steps of h = dt / substeps in the frozen field for the n_tracers tracers of every env
+ *   (pos, seed_pos [batch][n][d]; cell, seed_cell [batch][n]; age [batch][n]; wraps [batch][n][n_shifts] int32; lost [batch] uint32;
+ *   respawn_slots uint8 [max(n_slots, 1)]).  x* = x + h/2 u(x) is located from the tracer's cell, x + h u(x*) from there, each by a walk of
+ *   at most 64 cell changes.  A walk that ends at a FIXED face puts the tracer on the face (the cell map at the clamped xi), or, where
+ *   respawn_slots[slot] != 0, back to its seed (position, cell, wraps := 0, age := 0 at the end of the call); a non-finite position
+ *   or an exhausted walk does the same and adds 1 to lost[env] (an integer atomic).  A respawn ends the call for the tracer.
+ * One thread per point / tracer, grid (ceil(n / 256), batch), no LDS, no floating-point atomic: an env's result does not depend on
+ * the batch and repeats bit for bit.  Asynchronous on `stream`; nothing returns to the host.  Before any launch (and without a GPU)
+ * FG_ERR_INVALID_ARG: a null pointer, dims not 2 or 3, batch outside 1..65535, n_cells outside 1..2^28, a negative count, slack outside
+ * (0, 0.25), a non-finite shift or dt, a stride smaller than its field, n_points / n_tracers / substeps < 1, n_extra outside 0..8;
+ * FG_ERR_UNSUPPORTED: kv or kc above 16, more than 4 shift vectors. */
+typedef struct fg_mb_point_mesh {
+    int32_t dims, batch, n_cells, n_slots, n_vertices, kv, kc, n_shifts;
+    const int32_t* cell_vert;
+    const fg_real* cell_xyz;
+    const int32_t* neighbors;
+    const uint8_t* face_code;
+    const int32_t* vel_idx;
+    const fg_real* vel_w;
+    const int32_t* cell_idx;
+    const fg_real* cell_w;
+    fg_real slack;
+    fg_real shifts[12];
+    const fg_real* velocity;
+    int64_t velocity_stride;
+    const fg_real* bvel;
+    int64_t bvel_stride, bvel_comp_stride;
+} fg_mb_point_mesh;
+int fg_mb_point_locate(const fg_mb_point_mesh* mesh, const fg_real* points, int64_t points_env_stride, int32_t n_points,
+                       const int32_t* start_cell, int32_t max_walk, int32_t* cell_out, fg_real* xi_out, int32_t* status_out, void* stream);
+int fg_mb_point_sample(const fg_mb_point_mesh* mesh, const fg_real* const* extra, const int64_t* extra_stride, int32_t n_extra,
+                       const int32_t* cell, const fg_real* xi, int64_t cell_env_stride, int32_t n_points, fg_real* out, void* stream);
+int fg_mb_tracer_advect(const fg_mb_point_mesh* mesh, fg_real dt, int32_t substeps, const uint8_t* respawn_slots, const fg_real* seed_pos,
+                        const int32_t* seed_cell, fg_real* pos, int32_t* cell, fg_real* age, int32_t* wraps, uint32_t* lost,
+                        int32_t n_tracers, void* stream);
+
 /* ---- env glue either side of the n sim steps of an env step (fp32 library only) ------------------------------
  * fg_envglue_jet_schedule: the action smoothing of the reference's jet envs (cylinder_env_base.py:748-753, a_k = a_{k-1} +
  * alpha (target - a_{k-1}) before every sim step) for the n sim steps of one env step at once: control[k][b] = target[b] +
