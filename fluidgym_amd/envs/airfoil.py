@@ -316,10 +316,7 @@ class AirfoilEnvBase(CylinderEnvBase):
             if self._enable_actions:
                 self._apply_action(control)
             self._sim.single_step()
-            if self._field_stats is not None:
-                self._record_field_sample()
-            if self._mesh_tracers is not None:
-                self._advect_mesh_tracers()
+            self._after_sim_step()
             cd, cl = self._get_drag_and_lift()
             cds.append(cd); cls.append(cl)
         obs = self._get_global_obs()

@@ -218,14 +218,14 @@ class ChannelJetEnv2D(FluidEnv):
         return ("-x", "+x")      # a tracer that leaves through the outflow (or the inflow) starts again at its seed
 
     def _run_sim_steps(self, n: int, schedule) -> bool:
-        """The ``n`` sim steps of an env step: one ``multi_step`` call -- or, while a tracer cloud is active, one call per sim step
-        (the same arithmetic in the same order) with the cloud advected in between."""
-        if self._tracers is None:
+        """The ``n`` sim steps of an env step: one ``multi_step`` call -- or, while any step hook (a tracer cloud) is active, one call
+        per sim step (the same arithmetic in the same order) with the hooks run in between."""
+        if not self._step_hooks:
             return self._sim.multi_step(n, schedule)
         for k in range(n):
             if not self._sim.multi_step(1, None if schedule is None else {f: t[k: k + 1] for f, t in schedule.items()}):
                 return False
-            self._advect_tracers()
+            self._after_sim_step()
         return True
 
     def _step_native(self, action: torch.Tensor):

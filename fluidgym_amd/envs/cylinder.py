@@ -333,10 +333,7 @@ class CylinderEnvBase(MeshTracerMixin, FieldStatisticsMixin, FlowStatisticsMixin
             if self._enable_actions:
                 self._apply_action(controls[k])
             self._sim.single_step()
-            if self._field_stats is not None:
-                self._record_field_sample()
-            if self._mesh_tracers is not None:
-                self._advect_mesh_tracers()
+            self._after_sim_step()
             self._ring.forces(self._domain, self._nu_forces, layer_height=self.D / self._circle_resolution_angular, out=raw[k])
         self._last_control_mirror = (self._last_control, c_last)
         obs = self._get_global_obs()

@@ -14,7 +14,11 @@ no distributions).
 The multi-block envs (cylinder, airfoil) have no homogeneous plane; ``FieldStatisticsMixin`` gives them ``start_field_statistics`` /
 ``stop_field_statistics``: the time-averaged fields per cell, in 3-D averaged over the span as well
 (``simulation/cell_moments.CellMoments``; the reference's ``WelfordOnlineParallel_Torch`` / ``CovarianceOnlineParallel_Torch`` per
-block)."""
+block).
+
+Every ``start_*`` checks its own arguments, makes the recorder and hands it to ``_start_hook`` (``envs/step_hooks.py``) with the one
+line that takes a sample; every ``stop_*`` is one ``_stop_hook``.  Counting the sim steps, the order among the recorders and an env
+with nothing switched on are the hook list's business."""
 from __future__ import annotations
 
 from typing import Optional, Sequence
@@ -29,49 +33,19 @@ from ..simulation.plane_stats import CHANNEL_SETS, PlaneMoments
 from ..simulation.plane_timecorr import PlaneTimeCorrelation
 
 
-def _check_start(env, entry: str, every: int, single_block: Optional[str] = None, needs_3d: bool = False) -> None:
+def _check_start(env, entry: str, single_block: Optional[str] = None, needs_3d: bool = False) -> None:
     """The checks every ``start_*`` begins with: reset() done, (``single_block``: what needs one) a single-block domain, (``needs_3d``)
-    a 3-D one, ``every`` at least 1."""
+    a 3-D one.  (``every`` is checked by ``_start_hook``.)"""
     if getattr(env, "_domain", None) is None:
         raise RuntimeError(f"{entry}: reset() the env first (the domain does not exist yet)")
     if single_block is not None and env._flow_blocks() != 1:
         raise NotImplementedError(f"{single_block} need a single-block domain")
     if needs_3d and env._ndims != 3:
         raise NotImplementedError(f"{single_block} need a 3-D domain")
-    if int(every) < 1:
-        raise ValueError(f"every must be at least 1, got {every}")
-
-
-def _due(env, name: str) -> bool:
-    """Count a sim step for the recorder ``name``; True at every ``every``-th one."""
-    tick = getattr(env, name + "_tick") + 1
-    setattr(env, name + "_tick", tick)
-    return tick % getattr(env, name + "_every") == 0
 
 
 class FlowStatisticsMixin:
-    _flow_stats: Optional[PlaneMoments] = None      # None (the default): the step path does nothing for the statistics
-    _flow_stats_every: int = 1
-    _flow_stats_tick: int = 0
     _flow_stats_scalar: bool = False                # whether the passive scalar is recorded as channel T
-    _flow_spectra: Optional[PlaneSpectra] = None    # None (the default): the step path does nothing for the spectra
-    _flow_spectra_every: int = 1
-    _flow_spectra_tick: int = 0
-    _flow_budgets: Optional[PlaneBudgets] = None    # None (the default): the step path does nothing for the budgets
-    _flow_budgets_every: int = 1
-    _flow_budgets_tick: int = 0
-    _flow_timecorr: Optional[PlaneTimeCorrelation] = None   # None (the default): the step path does nothing for the correlations
-    _flow_timecorr_every: int = 1
-    _flow_timecorr_tick: int = 0
-    _flow_hist: Optional[PlaneHistograms] = None    # None (the default): the step path does nothing for the histograms
-    _flow_hist_every: int = 1
-    _flow_hist_tick: int = 0
-
-    def start_flow_statistics(self, order: int = 2, every: int = 1) -> None:
-        """Start a fresh record of moments up to ``order``; a sample is taken after every ``every``-th sim step of ``step()``."""
-        _check_start(self, "start_flow_statistics", every, "flow statistics")
-        self._flow_stats = PlaneMoments(self._flow_channels(), order)
-        self._flow_stats_every, self._flow_stats_tick = int(every), 0
 
     def _flow_blocks(self) -> int:
         count = getattr(self._domain, "getNumBlocks", None)
@@ -80,104 +54,79 @@ class FlowStatisticsMixin:
     def _flow_channels(self):
         return ("u", "v") + (("w",) if self._ndims == 3 else ()) + ("p",) + (("T",) if self._flow_stats_scalar else ())
 
+    def _flow_fields(self, channels) -> tuple:
+        """``(velocity, pressure, scalar)`` of the block as bound now, None for a field that is no channel of ``channels``."""
+        blk = self._domain.getBlock(0)
+        return blk.velocity, blk.pressure if "p" in channels else None, blk.passiveScalar if "T" in channels else None
+
+    def start_flow_statistics(self, order: int = 2, every: int = 1) -> None:
+        """Start a fresh record of moments up to ``order``; a sample is taken after every ``every``-th sim step of ``step()``."""
+        _check_start(self, "start_flow_statistics", "flow statistics")
+        stats = PlaneMoments(self._flow_channels(), order)
+        self._start_hook("flow_stats", stats, every, lambda: stats.update(*self._flow_fields(stats.channels)))
+
     def stop_flow_statistics(self) -> PlaneMoments:
         """Stop recording and hand out the record (on the GPU; its accessors, ``pooled()`` and ``save`` read it back)."""
-        if self._flow_stats is None:
-            raise RuntimeError("stop_flow_statistics: no statistics are being recorded")
-        stats, self._flow_stats = self._flow_stats, None
-        return stats
-
-    def _record_flow_sample(self) -> None:
-        """Called after a sim step while statistics are active."""
-        if not _due(self, "_flow_stats"):
-            return
-        blk = self._domain.getBlock(0)
-        self._flow_stats.update(blk.velocity, blk.pressure, blk.passiveScalar if self._flow_stats_scalar else None)
+        return self._stop_hook("flow_stats", "stop_flow_statistics: no statistics are being recorded")
 
     def start_flow_spectra(self, planes: Sequence[int], every: int = 1, symmetric: bool = True) -> None:
         """Start a fresh record of the wavenumber spectra of the rows ``planes`` (and, ``symmetric``, of their mirror images) of
         the channels of the moments; a sample is taken after every ``every``-th sim step of ``step()``."""
-        _check_start(self, "start_flow_spectra", every, "flow spectra")
+        _check_start(self, "start_flow_spectra", "flow spectra")
         vel = self._domain.getBlock(0).velocity
         nz, ny, nx = ((1,) + tuple(int(s) for s in vel.shape[2:]))[-3:]
         check_extents(nz, nx, vel.element_size(), "start_flow_spectra")
         spectra = PlaneSpectra(self._flow_channels(), planes, symmetric)
         spectra.plane_table(ny)                            # planes outside the grid are refused here, not at the first sample
-        self._flow_spectra = spectra
-        self._flow_spectra_every, self._flow_spectra_tick = int(every), 0
+        self._start_hook("flow_spectra", spectra, every, lambda: spectra.update(*self._flow_fields(spectra.channels)))
 
     def stop_flow_spectra(self) -> PlaneSpectra:
         """Stop recording and hand out the record (on the GPU; its accessors, ``pooled()`` and ``save`` read it back)."""
-        if self._flow_spectra is None:
-            raise RuntimeError("stop_flow_spectra: no spectra are being recorded")
-        spectra, self._flow_spectra = self._flow_spectra, None
-        return spectra
-
-    def _record_spectra_sample(self) -> None:
-        """Called after a sim step while spectra are active."""
-        if not _due(self, "_flow_spectra"):
-            return
-        blk = self._domain.getBlock(0)
-        self._flow_spectra.update(blk.velocity, blk.pressure, blk.passiveScalar if self._flow_stats_scalar else None)
+        return self._stop_hook("flow_spectra", "stop_flow_spectra: no spectra are being recorded")
 
     def start_flow_budgets(self, every: int = 1, forcing: Optional[bool] = None) -> None:
         """Start a fresh record of the Reynolds-stress budgets; a sample is taken after every ``every``-th sim step of ``step()``.
         The coordinates are the block's cell centres, periodic x / z faces wrap, ``forcing`` defaults to whether the block has a
         velocity source."""
-        _check_start(self, "start_flow_budgets", every, "flow budgets", needs_3d=True)
+        _check_start(self, "start_flow_budgets", "flow budgets", needs_3d=True)
         blk = self._domain.getBlock(0)
         if forcing is None:
             forcing = blk.velocitySource is not None
         elif forcing and blk.velocitySource is None:
             raise ValueError("start_flow_budgets: forcing=True needs a block with a velocity source")
         x, y, z = (0.5 * (np.asarray(e, np.float64)[1:] + np.asarray(e, np.float64)[:-1]) for e in blk.edges)
-        self._flow_budgets = PlaneBudgets(x, y, z, forcing=bool(forcing), wrap=(not blk.isFixed("-x"), not blk.isFixed("-z")))
-        self._flow_budgets_every, self._flow_budgets_tick = int(every), 0
+        budgets = PlaneBudgets(x, y, z, forcing=bool(forcing), wrap=(not blk.isFixed("-x"), not blk.isFixed("-z")))
+
+        def sample():
+            blk = self._domain.getBlock(0)
+            budgets.update(blk.velocity, blk.pressure, blk.velocitySource if budgets.forcing else None)
+
+        self._start_hook("flow_budgets", budgets, every, sample)
 
     def stop_flow_budgets(self) -> PlaneBudgets:
         """Stop recording and hand out the record (on the GPU; its accessors, ``pooled()`` and ``save`` read it back)."""
-        if self._flow_budgets is None:
-            raise RuntimeError("stop_flow_budgets: no budgets are being recorded")
-        budgets, self._flow_budgets = self._flow_budgets, None
-        return budgets
-
-    def _record_budgets_sample(self) -> None:
-        """Called after a sim step while budgets are active."""
-        if not _due(self, "_flow_budgets"):
-            return
-        blk = self._domain.getBlock(0)
-        self._flow_budgets.update(blk.velocity, blk.pressure, blk.velocitySource if self._flow_budgets.forcing else None)
+        return self._stop_hook("flow_budgets", "stop_flow_budgets: no budgets are being recorded")
 
     def start_flow_time_correlation(self, lags: int, every: int = 1, stride: Optional[int] = None,
                                     channels: Optional[Sequence[str]] = None) -> None:
         """Start a fresh record of the temporal correlations over ``lags`` samples; a sample is taken after every ``every``-th sim
-        step of ``step()``.  ``stride`` None: one base at the first sample, as the reference; ``stride = S``: a new base at every
-        ``S``-th sample.  ``channels`` default to the velocity components; any channel set of the moments is taken."""
-        _check_start(self, "start_flow_time_correlation", every, "flow time correlations")
+        step of ``step()``, its time the simulation's host-side clock.  ``stride`` None: one base at the first sample, as the
+        reference; ``stride = S``: a new base at every ``S``-th sample.  ``channels`` default to the velocity components; any channel
+        set of the moments is taken."""
+        _check_start(self, "start_flow_time_correlation", "flow time correlations")
         velocity = ("u", "v") + (("w",) if self._ndims == 3 else ())
         channels = velocity if channels is None else tuple(channels)
         if channels != velocity and (channels not in CHANNEL_SETS or ("w" in channels) != (self._ndims == 3)):
             raise ValueError(f"channels must be {velocity} or one of {CHANNEL_SETS} that fits the {self._ndims}-D domain, got {channels}")
         if "T" in channels and not self._domain.getBlock(0).hasPassiveScalar():
             raise ValueError("start_flow_time_correlation: channel T needs a domain with a passive scalar")
-        self._flow_timecorr = PlaneTimeCorrelation(channels, lags, stride)
-        self._flow_timecorr_every, self._flow_timecorr_tick = int(every), 0
+        corr = PlaneTimeCorrelation(channels, lags, stride)
+        self._start_hook("flow_timecorr", corr, every,
+                         lambda: corr.update(*self._flow_fields(corr.channels), time=self._sim.total_time))
 
     def stop_flow_time_correlation(self) -> PlaneTimeCorrelation:
         """Stop recording and hand out the record (on the GPU; its accessors, ``pooled()`` and ``save`` read it back)."""
-        if self._flow_timecorr is None:
-            raise RuntimeError("stop_flow_time_correlation: no time correlations are being recorded")
-        corr, self._flow_timecorr = self._flow_timecorr, None
-        return corr
-
-    def _record_time_correlation_sample(self) -> None:
-        """Called after a sim step while time correlations are active; the sample's time is the simulation's host-side clock."""
-        if not _due(self, "_flow_timecorr"):
-            return
-        blk = self._domain.getBlock(0)
-        corr = self._flow_timecorr
-        corr.update(blk.velocity, blk.pressure if "p" in corr.channels else None,
-                    blk.passiveScalar if "T" in corr.channels else None, time=self._sim.total_time)
+        return self._stop_hook("flow_timecorr", "stop_flow_time_correlation: no time correlations are being recorded")
 
     def start_flow_histograms(self, ranges=None, bins: int = 128, joint: Sequence = (), joint_bins: int = 32,
                               rows: Optional[Sequence[int]] = None, channels: Optional[Sequence[str]] = None, every: int = 1) -> None:
@@ -186,7 +135,7 @@ class FlowStatisticsMixin:
         after every ``every``-th sim step of ``step()``.  ``ranges`` maps a channel to ``(lo, hi)`` or to ``[n_rows, 2]``; None takes,
         per listed row and channel, the minimum and maximum over the batch of the current state, widened by half the span on each
         side (by 1 where the span is zero)."""
-        _check_start(self, "start_flow_histograms", every, "flow histograms")
+        _check_start(self, "start_flow_histograms", "flow histograms")
         channels = self._flow_channels() if channels is None else tuple(channels)
         blk = self._domain.getBlock(0)
         if any(c not in CHANNEL_ORDER for c in channels) or ("w" in channels and self._ndims != 3):
@@ -207,46 +156,23 @@ class FlowStatisticsMixin:
                 lo, hi = f.amin(dim=1).cpu().numpy(), f.amax(dim=1).cpu().numpy()
                 pad = np.where(hi > lo, 0.5 * (hi - lo), 1.0)
                 ranges[c] = np.stack([lo - pad, hi + pad], axis=1)
-        self._flow_hist = PlaneHistograms(channels, ranges, bins, joint, joint_bins, rows)
-        self._flow_hist_every, self._flow_hist_tick = int(every), 0
+        hist = PlaneHistograms(channels, ranges, bins, joint, joint_bins, rows)
+        self._start_hook("flow_hist", hist, every, lambda: hist.update(*self._flow_fields(hist.channels)))
 
     def stop_flow_histograms(self) -> PlaneHistograms:
         """Stop recording and hand out the record (on the GPU; its accessors, ``pooled()`` and ``save`` read it back)."""
-        if self._flow_hist is None:
-            raise RuntimeError("stop_flow_histograms: no histograms are being recorded")
-        hist, self._flow_hist = self._flow_hist, None
-        return hist
-
-    def _record_histogram_sample(self) -> None:
-        """Called after a sim step while histograms are active."""
-        if not _due(self, "_flow_hist"):
-            return
-        blk = self._domain.getBlock(0)
-        hist = self._flow_hist
-        hist.update(blk.velocity, blk.pressure if "p" in hist.channels else None, blk.passiveScalar if "T" in hist.channels else None)
+        return self._stop_hook("flow_hist", "stop_flow_histograms: no histograms are being recorded")
 
 
 class FieldStatisticsMixin:
-    _field_stats: Optional[CellMoments] = None      # None (the default): the step path does nothing for the statistics
-    _field_stats_every: int = 1
-    _field_stats_tick: int = 0
-
     def start_field_statistics(self, every: int = 1, span_average: bool = True) -> None:
-        """Start a fresh per-cell record of ``u, v(, w), p``; a sample is taken after every ``every``-th sim step of ``step()``.
-        ``span_average`` (3-D): one column per ``(block, y, x)``, averaged over the span; off, every cell is recorded."""
-        _check_start(self, "start_field_statistics", every)
-        self._field_stats = CellMoments.for_domain(self._domain, span_average)
-        self._field_stats_every, self._field_stats_tick = int(every), 0
+        """Start a fresh per-cell record of ``u, v(, w), p``; a sample is taken after every ``every``-th sim step of ``step()`` (the
+        fields are read, never written).  ``span_average`` (3-D): one column per ``(block, y, x)``, averaged over the span; off,
+        every cell is recorded."""
+        _check_start(self, "start_field_statistics")
+        stats = CellMoments.for_domain(self._domain, span_average)
+        self._start_hook("field_stats", stats, every, lambda: stats.update(self._domain.velocity, self._domain.pressure))
 
     def stop_field_statistics(self) -> CellMoments:
         """Stop recording and hand out the record (on the GPU; its accessors, ``pooled()`` and ``save`` read it back)."""
-        if self._field_stats is None:
-            raise RuntimeError("stop_field_statistics: no field statistics are being recorded")
-        stats, self._field_stats = self._field_stats, None
-        return stats
-
-    def _record_field_sample(self) -> None:
-        """Called after a sim step while field statistics are active; the fields are read, never written."""
-        if not _due(self, "_field_stats"):
-            return
-        self._field_stats.update(self._domain.velocity, self._domain.pressure)
+        return self._stop_hook("field_stats", "stop_field_statistics: no field statistics are being recorded")

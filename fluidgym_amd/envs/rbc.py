@@ -432,18 +432,7 @@ class RBCEnvBase(FlowStatisticsMixin, FluidEnv):
         for _ in range(self._n_sim_steps):
             if not self._sim.single_step():
                 raise RuntimeError("simulation step failed")
-            if self._flow_stats is not None:
-                self._record_flow_sample()
-            if self._flow_spectra is not None:
-                self._record_spectra_sample()
-            if self._flow_budgets is not None:
-                self._record_budgets_sample()
-            if self._flow_timecorr is not None:
-                self._record_time_correlation_sample()
-            if self._flow_hist is not None:
-                self._record_histogram_sample()
-            if self._tracers is not None:
-                self._advect_tracers()
+            self._after_sim_step()
         nu = self.compute_global_nusselt()
         obs = self._get_global_obs()
         return obs, self.nu_ref - nu, False, {"nusselt": nu}

@@ -369,18 +369,7 @@ class TCF3DBottomEnv(FlowStatisticsMixin, FluidEnv):
             if not self._sim.single_step():
                 raise RuntimeError("simulation step failed")
             b, t = self._get_wall_stress()
-            if self._flow_stats is not None:
-                self._record_flow_sample()
-            if self._flow_spectra is not None:
-                self._record_spectra_sample()
-            if self._flow_budgets is not None:
-                self._record_budgets_sample()
-            if self._flow_timecorr is not None:
-                self._record_time_correlation_sample()
-            if self._flow_hist is not None:
-                self._record_histogram_sample()
-            if self._tracers is not None:
-                self._advect_tracers()
+            self._after_sim_step()
             tb.append(b)
             tt.append(t)
         tau_bottom, tau_top = torch.stack(tb).mean(dim=0), torch.stack(tt).mean(dim=0)
@@ -391,17 +380,17 @@ class TCF3DBottomEnv(FlowStatisticsMixin, FluidEnv):
     def start_flow_statistics(self, order: int = 2, every: int = 1) -> None:
         super().start_flow_statistics(order=order, every=every)
         e = np.asarray(self._block.edges[1], np.float64)                              # walls at y = -1, +1: u_wall(), y+
-        self._flow_stats.set_wall_units(0.5 * (e[1:] + e[:-1]), self._nu)
+        self._hook("flow_stats").set_wall_units(0.5 * (e[1:] + e[:-1]), self._nu)
 
     def start_flow_budgets(self, every: int = 1, forcing=None) -> None:
         super().start_flow_budgets(every=every, forcing=forcing)
         e = np.asarray(self._block.edges[1], np.float64)
-        self._flow_budgets.set_wall_units(0.5 * (e[1:] + e[:-1]), self._nu)
+        self._hook("flow_budgets").set_wall_units(0.5 * (e[1:] + e[:-1]), self._nu)
 
     def start_flow_time_correlation(self, lags: int, every: int = 1, stride=None, channels=None) -> None:
         super().start_flow_time_correlation(lags, every=every, stride=stride, channels=channels)
         e = np.asarray(self._block.edges[1], np.float64)                              # ETT and t+ from the nominal friction velocity
-        self._flow_timecorr.set_wall_units(0.5 * (e[1:] + e[:-1]), self._nu, self._u_wall)
+        self._hook("flow_timecorr").set_wall_units(0.5 * (e[1:] + e[:-1]), self._nu, self._u_wall)
 
     def _frame_wall_row(self) -> int:
         """The cell row of the wall-parallel pictures.  The reference slices its uniform render grid, y-flipped, at pixel row

@@ -2,7 +2,8 @@
 positions, and a cloud of Lagrangian tracers (``simulation/tracers.TracerCloud``) that is advected on the GPU after every
 ``every``-th sim step of ``step()`` while it is active.  ``reset()`` returns every env's tracers to their seeds, ``reset_envs(envs)``
 those of the chosen envs and no other; ``get_state()`` carries the cloud under the key ``"tracers"`` while one is active and
-``set_state()`` restores it.  Without an active cloud the step, reset and state paths do nothing for the tracers."""
+``set_state()`` restores it.  An active cloud is one entry of the env's hook list (``envs/step_hooks.py``), which does all of that;
+without one the step, reset and state paths do nothing for the tracers."""
 from __future__ import annotations
 
 from typing import Optional, Sequence
@@ -15,9 +16,6 @@ from ..simulation.tracers import PointGrid, TracerCloud
 
 
 class TracerMixin:
-    _tracers: Optional[TracerCloud] = None          # None (the default): the step path does nothing for the tracers
-    _tracers_every: int = 1
-    _tracers_tick: int = 0
     _probe_grid: Optional[PointGrid] = None
 
     def _require_single_block(self, entry: str) -> None:
@@ -30,7 +28,7 @@ class TracerMixin:
     @property
     def tracers(self) -> Optional[TracerCloud]:
         """The active cloud, or None."""
-        return self._tracers
+        return self._hook("tracers")
 
     def probe(self, points, fields: Optional[Sequence[str]] = None) -> torch.Tensor:
         """``fields`` (default ``u, v(, w), p(, T)``) at the physical positions ``points`` (``[P, d]`` for every env, or
@@ -48,39 +46,19 @@ class TracerMixin:
         """Start a fresh cloud of ``n`` tracers per env (``TracerCloud``: ``seed`` or ``positions``); after every ``every``-th sim step
         of ``step()`` it is advanced by ``every`` sim time steps in the velocity field of that moment."""
         self._require_single_block("start_tracers")
-        if int(every) < 1:
-            raise ValueError(f"every must be at least 1, got {every}")
-        self._tracers = TracerCloud(self._domain, n, seed=seed, positions=positions, substeps=substeps,
-                                    respawn_faces=self._tracer_respawn_faces())
-        self._tracers_every, self._tracers_tick = int(every), 0
-        return self._tracers
+        cloud = TracerCloud(self._domain, n, seed=seed, positions=positions, substeps=substeps, respawn_faces=self._tracer_respawn_faces())
+        # (the interval reads the hook's own ``every``: set_state() may have restored another one)
+        return self._start_hook("tracers", cloud, every, lambda: cloud.advect(self._step_hooks["tracers"].every * self._sim_step_time()),
+                                reseed=cloud.reseed, state_key="tracers")
 
     def stop_tracers(self) -> TracerCloud:
         """Stop advecting and hand out the cloud."""
         self._require_single_block("stop_tracers")
-        if self._tracers is None:
-            raise RuntimeError("stop_tracers: no tracers are active")
-        cloud, self._tracers = self._tracers, None
-        return cloud
+        return self._stop_hook("tracers", "stop_tracers: no tracers are active")
 
     def _sim_step_time(self) -> float:
         sim = self._sim
         return float(sim.time_step if sim.substeps == -1 else sim.time_step * max(sim.substeps, 1))
-
-    def _advect_tracers(self) -> None:
-        """Called after a sim step while a cloud is active."""
-        self._tracers_tick += 1
-        if self._tracers_tick % self._tracers_every == 0:
-            self._tracers.advect(self._tracers_every * self._sim_step_time())
-
-    def _tracer_state(self) -> dict:
-        return {"cloud": self._tracers.state_dict(), "every": self._tracers_every, "tick": self._tracers_tick}
-
-    def _set_tracer_state(self, state: dict) -> None:
-        if self._tracers is None:
-            raise RuntimeError("set_state: the state holds a tracer cloud but none is active; call start_tracers() with its size first")
-        self._tracers.load_state_dict(state["cloud"])
-        self._tracers_every, self._tracers_tick = int(state["every"]), int(state["tick"])
 
 
 class MeshTracerMixin:
@@ -89,10 +67,8 @@ class MeshTracerMixin:
     cloud of Lagrangian tracers (``MeshTracerCloud``) advected on the GPU after every ``every``-th sim step of ``step()`` while it is
     active.  Tracers that reach the inflow or an outflow face return to their seeds; walls and jets stop them.  ``reset()`` reseeds
     every env's tracers, ``reset_envs(envs)`` those of the chosen envs; ``get_state()`` carries the cloud under ``"mesh_tracers"`` while
-    one is active; ``close()`` drops cloud and mesh tables.  Without an active cloud the step path launches nothing."""
-    _mesh_tracers = None
-    _mesh_tracers_every: int = 1
-    _mesh_tracers_tick: int = 0
+    one is active; ``close()`` drops cloud and mesh tables: the cloud is one entry of the env's hook list (``envs/step_hooks.py``).
+    Without an active cloud the step path launches nothing."""
     _point_mesh = None
 
     def _require_multi_block(self, entry: str):
@@ -117,7 +93,7 @@ class MeshTracerMixin:
     @property
     def mesh_tracers(self):
         """The active ``MeshTracerCloud``, or None."""
-        return self._mesh_tracers
+        return self._hook("mesh_tracers")
 
     def locate_probes(self, points, strict: bool = True):
         """``MeshProbes`` at the physical positions ``points`` (``[P, d]`` for every env, or ``[B, P, d]``): located once here;
@@ -146,63 +122,19 @@ class MeshTracerMixin:
 
     def start_mesh_tracers(self, n: int, seed: Optional[int] = None, positions=None, substeps: int = 4, every: int = 1):
         """Start a fresh cloud of ``n`` tracers per env (``MeshTracerCloud``: ``seed`` or ``positions``); after every ``every``-th sim step
-        of ``step()`` it is advanced by ``every`` sim time steps in the velocity field of that moment."""
+        of ``step()`` it is advanced by ``every`` sim time steps in the velocity field of that moment.  Every ``single_step()`` of
+        ``MultiBlockSimulation`` advances the flow by exactly ``time_step`` (the adaptive CFL only splits that interval into sub-steps
+        inside the call), so the ``every`` sim steps since the last advance lasted ``every * time_step`` whatever their sub-steps
+        were: tracer time equals sim time."""
         from ..simulation.mb_tracers import MeshTracerCloud
 
         mesh = self._require_multi_block("start_mesh_tracers")
-        if int(every) < 1:
-            raise ValueError(f"every must be at least 1, got {every}")
-        self._mesh_tracers = MeshTracerCloud(mesh, n, seed=seed, positions=positions, substeps=substeps,
-                                             respawn_slots=self._mesh_respawn_slots().astype(bool))
-        self._mesh_tracers_every, self._mesh_tracers_tick = int(every), 0
-        return self._mesh_tracers
+        cloud = MeshTracerCloud(mesh, n, seed=seed, positions=positions, substeps=substeps, respawn_slots=self._mesh_respawn_slots().astype(bool))
+        return self._start_hook("mesh_tracers", cloud, every,
+                                lambda: cloud.advect(self._step_hooks["mesh_tracers"].every * float(self._sim.time_step)),
+                                reseed=cloud.reseed, state_key="mesh_tracers")
 
     def stop_mesh_tracers(self):
         """Stop advecting and hand out the cloud."""
         self._require_multi_block("stop_mesh_tracers")
-        if self._mesh_tracers is None:
-            raise RuntimeError("stop_mesh_tracers: no tracers are active")
-        cloud, self._mesh_tracers = self._mesh_tracers, None
-        return cloud
-
-    def _advect_mesh_tracers(self) -> None:
-        """Called after a sim step while a cloud is active.  Every ``single_step()`` of ``MultiBlockSimulation`` advances the flow by
-        exactly ``time_step`` (the adaptive CFL only splits that interval into sub-steps inside the call), so the ``every`` sim steps
-        since the last advance lasted ``every * time_step`` whatever their sub-steps were: tracer time equals sim time."""
-        self._mesh_tracers_tick += 1
-        if self._mesh_tracers_tick % self._mesh_tracers_every == 0:
-            self._mesh_tracers.advect(self._mesh_tracers_every * float(self._sim.time_step))
-
-    def reset(self, *args, **kw):
-        out = super().reset(*args, **kw)
-        if self._mesh_tracers is not None:
-            self._mesh_tracers.reseed()
-            self._mesh_tracers_tick = 0
-        return out
-
-    def reset_envs(self, envs, *args, **kw):
-        out = super().reset_envs(envs, *args, **kw)
-        if self._mesh_tracers is not None:
-            self._mesh_tracers.reseed(envs)
-        return out
-
-    def get_state(self) -> dict:
-        state = super().get_state()
-        if self._mesh_tracers is not None:
-            state["mesh_tracers"] = {"cloud": self._mesh_tracers.state_dict(), "every": self._mesh_tracers_every,
-                                     "tick": self._mesh_tracers_tick}
-        return state
-
-    def set_state(self, state: dict) -> None:
-        super().set_state(state)
-        if "mesh_tracers" in state:
-            if self._mesh_tracers is None:
-                raise RuntimeError("set_state: the state holds a mesh tracer cloud but none is active; call start_mesh_tracers() with its "
-                                   "size first")
-            saved = state["mesh_tracers"]
-            self._mesh_tracers.load_state_dict(saved["cloud"])
-            self._mesh_tracers_every, self._mesh_tracers_tick = int(saved["every"]), int(saved["tick"])
-
-    def close(self) -> None:
-        self._mesh_tracers = self._point_mesh = None      # (they hold the closed domain)
-        super().close()
+        return self._stop_hook("mesh_tracers", "stop_mesh_tracers: no tracers are active")

@@ -25,7 +25,7 @@ import torch
 
 from .. import _lib as L
 from . import plane_fields as F
-from .state_bank import normalize_envs
+from .tracers import CloudBase, requested_fields
 
 FIELD_NAMES = ("u", "v", "w", "p")
 MAX_EXTRA, MAX_STENCIL, MAX_SHIFTS = 8, 16, 4
@@ -410,13 +410,9 @@ class MbPointMesh:
         """``fields`` (default ``u, v(, w), p``) at the located points ``cell [B, P]`` (or ``[P]``), ``xi [..., P, d]``: ``[B, P, K]``,
         one launch."""
         dom, d = self.domain, self.dims
-        fields = (("u", "v") + (("w",) if d == 3 else ()) + ("p",)) if fields is None else tuple(fields)
-        if not fields or any(f not in FIELD_NAMES for f in fields) or ("w" in fields and d != 3):
-            raise ValueError(f"fields must be names from {FIELD_NAMES} that fit the {d}-D domain, got {fields}")
+        extras, pick = requested_fields(fields, ("u", "v") + (("w",) if d == 3 else ()) + ("p",), FIELD_NAMES, d)
         B, P = int(dom.batch), int(cell.shape[-1])
-        extras = [f for f in dict.fromkeys(fields) if f == "p"]
-        K = d + len(extras)
-        out = torch.empty(B, P, K, dtype=self.dtype, device=self.device)
+        out = torch.empty(B, P, d + len(extras), dtype=self.dtype, device=self.device)
         m, keep = self.record()
         eptr = estride = None                                        # (no table where no cell-only field is asked for)
         if extras:
@@ -424,11 +420,7 @@ class MbPointMesh:
         with torch.cuda.device(self.device):
             L.check(self.lib.fg_mb_point_sample(ctypes.byref(m), eptr, estride, len(extras), F.ptr(cell), F.ptr(xi), P if cell.dim() == 2 else 0,
                                                 P, F.ptr(out), F.stream_ptr(self.device)), lib=self.lib)
-        column = {"u": 0, "v": 1, "w": 2, "p": d}
-        cols = [column[f] for f in fields]
-        if cols == list(range(K)):
-            return out
-        return out.index_select(2, torch.as_tensor(cols, dtype=torch.int64, device=self.device))
+        return pick(out)
 
 
 def _mesh_of(domain_or_mesh) -> MbPointMesh:
@@ -457,7 +449,7 @@ class MeshProbes:
         return self.mesh.sample(self.cell, self.xi, fields)
 
 
-class MeshTracerCloud:
+class MeshTracerCloud(CloudBase):
     """``n`` passive tracers in every env of a multi-block ``domain`` (or its ``MbPointMesh``).
 
     ``seed``: per env a cell drawn with probability proportional to its volume and a uniform ``xi`` mapped through it
@@ -471,15 +463,9 @@ class MeshTracerCloud:
     respawned) live on the GPU."""
 
     def __init__(self, domain, n: int, seed: Optional[int] = None, positions=None, substeps: int = 4, respawn_slots=None):
-        if (seed is None) == (positions is None):
-            raise ValueError("MeshTracerCloud: give exactly one of seed and positions")
-        if int(n) < 1:
-            raise ValueError(f"MeshTracerCloud: n must be at least 1, got {n}")
-        if int(substeps) < 1:
-            raise ValueError(f"MeshTracerCloud: substeps must be at least 1, got {substeps}")
+        super().__init__(n, seed, positions, substeps)
         self.mesh = m = _mesh_of(domain)
         t = m.tables
-        self.n, self.substeps, self.seed = int(n), int(substeps), seed
         B, d = int(m.domain.batch), m.dims
         self.respawn_slots = m.respawn_slots.clone()
         if respawn_slots is not None:
@@ -512,9 +498,8 @@ class MeshTracerCloud:
         self.wraps = torch.zeros(B, self.n, len(t.shifts), dtype=torch.int32, device=m.device)
         self.lost = torch.zeros(B, dtype=torch.int32, device=m.device)
 
-    @property
-    def batch(self) -> int:
-        return int(self.positions.shape[0])
+    _STATE = ("positions", "seed_positions", "cell", "seed_cell", "age", "wraps", "lost", "respawn_slots")
+    _SEEDED = (("positions", "seed_positions"), ("cell", "seed_cell"))
 
     def advect(self, dt: float) -> None:
         """Advance all tracers by ``dt`` in the velocity field as it stands: one launch."""
@@ -532,42 +517,10 @@ class MeshTracerCloud:
             return self.positions.clone()
         return self.positions + self.wraps.to(self.positions.dtype) @ self.mesh.shifts
 
-    def displacement(self) -> torch.Tensor:
-        """The unwrapped path relative to the seed position."""
-        return self.unwrapped() - self.seed_positions
-
     def sample(self, fields: Optional[Sequence[str]] = None) -> torch.Tensor:
         """Field values at the tracers, ``[B, N, K]``: the tracers' cells as starts of a walk, then the gather."""
         cell, xi, _ = self.mesh.locate(self.positions, self.cell, max_walk=TRACER_WALK)
         return self.mesh.sample(cell, xi, fields)
-
-    def reseed(self, envs=None) -> None:
-        """Return the tracers of the envs ``envs`` (indices or a bool mask; None: all) to their seeds with age, wraps and the lost count
-        zero; the other envs keep their bits."""
-        if envs is None:
-            self.positions.copy_(self.seed_positions); self.cell.copy_(self.seed_cell)
-            self.age.zero_(); self.wraps.zero_(); self.lost.zero_()
-            return
-        idx = torch.as_tensor(normalize_envs(envs, self.batch), dtype=torch.int64, device=self.positions.device)
-        self.positions.index_copy_(0, idx, self.seed_positions.index_select(0, idx))
-        self.cell.index_copy_(0, idx, self.seed_cell.index_select(0, idx))
-        self.age.index_fill_(0, idx, 0)
-        self.wraps.index_fill_(0, idx, 0)
-        self.lost.index_fill_(0, idx, 0)
-
-    _STATE = ("positions", "seed_positions", "cell", "seed_cell", "age", "wraps", "lost", "respawn_slots")
-
-    def state_dict(self) -> dict:
-        return {**{k: getattr(self, k).clone() for k in self._STATE}, "substeps": self.substeps}
-
-    def load_state_dict(self, state: dict) -> None:
-        for k in self._STATE:
-            if tuple(state[k].shape) != tuple(getattr(self, k).shape):
-                raise ValueError(f"MeshTracerCloud.load_state_dict: {k} has shape {tuple(state[k].shape)}, this cloud "
-                                 f"{tuple(getattr(self, k).shape)}")
-        for k in self._STATE:
-            getattr(self, k).copy_(state[k])
-        self.substeps = int(state["substeps"])
 
     def save(self, path) -> None:
         """One ``.npz``: the state arrays, the periodic ``shifts``, the mesh ``bounds`` and ``substeps``."""

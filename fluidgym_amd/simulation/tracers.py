@@ -60,6 +60,22 @@ def default_fields(domain) -> tuple:
     return ("u", "v") + (("w",) if domain.dims == 3 else ()) + ("p",) + (("T",) if domain.n_scalars > 0 else ())
 
 
+def requested_fields(fields, default, names, dims: int):
+    """The field-name check and the column selection of a ``sample`` (here and in ``mb_tracers.MbPointMesh``): ``(extras, pick)`` --
+    the cell-only fields among ``fields`` (``default`` for None) that the launch gathers after the ``dims`` velocity components, in
+    the order of their first mention, and ``pick(out)``, which brings the launch's ``[B, P, dims + len(extras)]`` into the order of
+    ``fields`` (``out`` itself where that is its order)."""
+    fields = default if fields is None else tuple(fields)
+    if not fields or any(f not in names for f in fields) or ("w" in fields and dims != 3):
+        raise ValueError(f"fields must be names from {names} that fit the {dims}-D domain, got {fields}")
+    extras = [f for f in dict.fromkeys(fields) if f not in ("u", "v", "w")]
+    column = {"u": 0, "v": 1, "w": 2, **{name: dims + i for i, name in enumerate(extras)}}
+    cols = [column[f] for f in fields]
+    if cols == list(range(dims + len(extras))):
+        return extras, lambda out: out
+    return extras, lambda out: out.index_select(2, torch.as_tensor(cols, dtype=torch.int64, device=out.device))
+
+
 class PointGrid:
     """The node arrays of a single-block domain on its device, built once, and the ``fg_point_grid`` record of a call, filled from
     the block's live tensors (the boundary tensors of a face can be rebound between steps)."""
@@ -131,9 +147,7 @@ class PointGrid:
     def sample(self, points: torch.Tensor, fields: Optional[Sequence[str]] = None) -> torch.Tensor:
         """Values of ``fields`` at ``points`` (``[P, d]``: one point set for all envs, or ``[B, P, d]``), ``[B, P, K]``."""
         dom, d = self.domain, self.dims
-        fields = default_fields(dom) if fields is None else tuple(fields)
-        if not fields or any(f not in FIELD_NAMES for f in fields) or ("w" in fields and d != 3):
-            raise ValueError(f"fields must be names from {FIELD_NAMES} that fit the {d}-D domain, got {fields}")
+        extras, pick = requested_fields(fields, default_fields(dom), FIELD_NAMES, d)
         if not isinstance(points, torch.Tensor):
             points = torch.from_numpy(np.ascontiguousarray(np.asarray(points, np.float64)))
         B = int(dom.solver.B)
@@ -141,19 +155,13 @@ class PointGrid:
             raise ValueError(f"points must be [P, {d}] or [{B}, P, {d}] with P >= 1, got {tuple(points.shape)}")
         pts = points.to(self.device, self.dtype).contiguous()
         P = int(pts.shape[-2])
-        extras = [f for f in dict.fromkeys(fields) if f in ("p", "T")]
-        K = d + len(extras)
-        out = torch.empty(B, P, K, dtype=self.dtype, device=self.device)
+        out = torch.empty(B, P, d + len(extras), dtype=self.dtype, device=self.device)
         g, keep = self.record()
         eptr, estride, ekeep = self.extra_tables(extras)
         with torch.cuda.device(self.device):
             L.check(self.lib.fg_point_sample(ctypes.byref(g), eptr, estride, len(extras), F.ptr(pts), P * d if pts.dim() == 3 else 0, P,
                                              F.ptr(out), F.stream_ptr(self.device)), lib=self.lib)
-        column = {"u": 0, "v": 1, "w": 2, **{name: d + i for i, name in enumerate(extras)}}
-        cols = [column[f] for f in fields]
-        if cols == list(range(K)):
-            return out
-        return out.index_select(2, torch.as_tensor(cols, dtype=torch.int64, device=self.device))
+        return pick(out)
 
 
 def sample_points(domain, points, fields: Optional[Sequence[str]] = None) -> torch.Tensor:
@@ -184,7 +192,63 @@ def respawn_mask(faces, dims: int, periodic) -> int:
     return mask
 
 
-class TracerCloud:
+class CloudBase:
+    """What ``TracerCloud`` and ``mb_tracers.MeshTracerCloud`` share.  A cloud names its state tensors in ``_STATE``, the (live, seed)
+    attribute pairs a reseed copies in ``_SEEDED`` and the integer settings that travel in its state beside ``substeps`` in
+    ``_SCALARS``; it has ``age``, ``wraps`` and ``lost`` among its tensors and an ``unwrapped()``."""
+    _STATE: tuple = ()
+    _SEEDED: tuple = ()
+    _SCALARS: tuple = ()
+
+    def __init__(self, n: int, seed: Optional[int], positions, substeps: int):
+        name = type(self).__name__
+        if (seed is None) == (positions is None):
+            raise ValueError(f"{name}: give exactly one of seed and positions")
+        if int(n) < 1:
+            raise ValueError(f"{name}: n must be at least 1, got {n}")
+        if int(substeps) < 1:
+            raise ValueError(f"{name}: substeps must be at least 1, got {substeps}")
+        self.n, self.substeps, self.seed = int(n), int(substeps), seed
+
+    @property
+    def batch(self) -> int:
+        return int(self.positions.shape[0])
+
+    def displacement(self) -> torch.Tensor:
+        """The unwrapped path relative to the seed position."""
+        return self.unwrapped() - self.seed_positions
+
+    def reseed(self, envs=None) -> None:
+        """Return the tracers of the envs ``envs`` (indices or a bool mask; None: all) to their seeds with age, wraps and the lost count
+        zero; the other envs keep their bits."""
+        cleared = (self.age, self.wraps, self.lost)
+        if envs is None:
+            for live, seed in self._SEEDED:
+                getattr(self, live).copy_(getattr(self, seed))
+            for t in cleared:
+                t.zero_()
+            return
+        idx = torch.as_tensor(normalize_envs(envs, self.batch), dtype=torch.int64, device=self.positions.device)
+        for live, seed in self._SEEDED:
+            getattr(self, live).index_copy_(0, idx, getattr(self, seed).index_select(0, idx))
+        for t in cleared:
+            t.index_fill_(0, idx, 0)
+
+    def state_dict(self) -> dict:
+        return {**{k: getattr(self, k).clone() for k in self._STATE}, **{k: getattr(self, k) for k in ("substeps",) + self._SCALARS}}
+
+    def load_state_dict(self, state: dict) -> None:
+        for k in self._STATE:
+            if tuple(state[k].shape) != tuple(getattr(self, k).shape):
+                raise ValueError(f"{type(self).__name__}.load_state_dict: {k} has shape {tuple(state[k].shape)}, this cloud "
+                                 f"{tuple(getattr(self, k).shape)}")
+        for k in self._STATE:
+            getattr(self, k).copy_(state[k])
+        for k in ("substeps",) + self._SCALARS:
+            setattr(self, k, int(state[k]))
+
+
+class TracerCloud(CloudBase):
     """``n`` passive tracers in every env of a single-block ``domain``.
 
     ``seed``: initial positions uniform in the domain box, drawn on the host per env (``seed_positions`` records the exact draw
@@ -197,14 +261,8 @@ class TracerCloud:
 
     def __init__(self, domain, n: int, seed: Optional[int] = None, positions=None, substeps: int = 4, respawn_faces=()):
         require_single_block(domain, "TracerCloud")
-        if (seed is None) == (positions is None):
-            raise ValueError("TracerCloud: give exactly one of seed and positions")
-        if int(n) < 1:
-            raise ValueError(f"TracerCloud: n must be at least 1, got {n}")
-        if int(substeps) < 1:
-            raise ValueError(f"TracerCloud: substeps must be at least 1, got {substeps}")
+        super().__init__(n, seed, positions, substeps)
         self.grid = g = PointGrid(domain)
-        self.n, self.substeps, self.seed = int(n), int(substeps), seed
         self.respawn_faces = respawn_mask(respawn_faces, g.dims, g.periodic)
         B, d = int(domain.solver.B), g.dims
         if seed is not None:
@@ -222,9 +280,9 @@ class TracerCloud:
         self.wraps = torch.zeros(B, self.n, d, dtype=torch.int32, device=g.device)
         self.lost = torch.zeros(B, dtype=torch.int32, device=g.device)
 
-    @property
-    def batch(self) -> int:
-        return int(self.positions.shape[0])
+    _STATE = ("positions", "seed_positions", "age", "wraps", "lost")
+    _SEEDED = (("positions", "seed_positions"),)
+    _SCALARS = ("respawn_faces",)
 
     def advect(self, dt: float) -> None:
         """Advance all tracers by ``dt`` in the velocity field as it stands: one launch."""
@@ -239,40 +297,9 @@ class TracerCloud:
         """``positions + wraps * length``: the path without the jumps at the periodic seams."""
         return self.positions + self.wraps.to(self.positions.dtype) * self.grid.len_dev
 
-    def displacement(self) -> torch.Tensor:
-        """The unwrapped path relative to the seed position."""
-        return self.unwrapped() - self.seed_positions
-
     def sample(self, fields: Optional[Sequence[str]] = None) -> torch.Tensor:
         """Field values at the tracers, ``[B, N, K]``."""
         return self.grid.sample(self.positions, fields)
-
-    def reseed(self, envs=None) -> None:
-        """Return the tracers of the envs ``envs`` (indices or a bool mask; None: all) to their seed positions with age, wraps and
-        the lost count zero; the other envs keep their bits."""
-        if envs is None:
-            self.positions.copy_(self.seed_positions)
-            self.age.zero_(); self.wraps.zero_(); self.lost.zero_()
-            return
-        idx = torch.as_tensor(normalize_envs(envs, self.batch), dtype=torch.int64, device=self.positions.device)
-        self.positions.index_copy_(0, idx, self.seed_positions.index_select(0, idx))
-        self.age.index_fill_(0, idx, 0)
-        self.wraps.index_fill_(0, idx, 0)
-        self.lost.index_fill_(0, idx, 0)
-
-    _STATE = ("positions", "seed_positions", "age", "wraps", "lost")
-
-    def state_dict(self) -> dict:
-        return {**{k: getattr(self, k).clone() for k in self._STATE}, "substeps": self.substeps, "respawn_faces": self.respawn_faces}
-
-    def load_state_dict(self, state: dict) -> None:
-        for k in self._STATE:
-            t = state[k]
-            if tuple(t.shape) != tuple(getattr(self, k).shape):
-                raise ValueError(f"TracerCloud.load_state_dict: {k} has shape {tuple(t.shape)}, this cloud {tuple(getattr(self, k).shape)}")
-        for k in self._STATE:
-            getattr(self, k).copy_(state[k])
-        self.substeps, self.respawn_faces = int(state["substeps"]), int(state["respawn_faces"])
 
     def save(self, path) -> None:
         """One ``.npz``: the state arrays, the box (``lo``, ``length``, ``periodic``), ``substeps`` and ``respawn_faces``."""

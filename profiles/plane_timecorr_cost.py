@@ -49,7 +49,7 @@ def measure(env_id, envs, channels, reps, inner, triad_gbps):
     env = fluidgym_amd.make(env_id, num_envs=envs, use_marl=False, randomize_initial_state=False, load_domain_statistics=False)
     env.reset(seed=0)
     zero = torch.zeros(env._zero_action.shape, device=env.cuda_device)
-    assert env._flow_timecorr is None                                  # the recorder is off: the step path of the parent commit
+    assert env._hook("flow_timecorr") is None                                  # the recorder is off: the step path of the parent commit
 
     def env_step():
         env._n_steps = 0

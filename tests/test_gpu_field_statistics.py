@@ -60,13 +60,13 @@ def test_recording_leaves_the_run_bit_identical_and_counts_every_nth_step():
 
 def test_field_statistics_are_off_by_default_need_a_reset_and_the_plane_statistics_still_refuse():
     env = fluidgym_amd.make("CylinderJet2D-easy-v0", num_envs=2, **KW)
-    assert env._field_stats is None
+    assert env._hook("field_stats") is None
     with pytest.raises(RuntimeError, match="reset"):
         env.start_field_statistics()
     with pytest.raises(RuntimeError, match="no field statistics"):
         env.stop_field_statistics()
     env.reset(seed=4)
-    assert env._field_stats is None
+    assert env._hook("field_stats") is None
     with pytest.raises(RuntimeError, match="no field statistics"):
         env.stop_field_statistics()
     with pytest.raises(ValueError, match="at least 1"):
@@ -74,7 +74,7 @@ def test_field_statistics_are_off_by_default_need_a_reset_and_the_plane_statisti
     with pytest.raises(NotImplementedError, match="single-block"):
         env.start_flow_statistics()
     env.start_field_statistics()
-    assert isinstance(env.stop_field_statistics(), CellMoments) and env._field_stats is None
+    assert isinstance(env.stop_field_statistics(), CellMoments) and env._hook("field_stats") is None
     env.close()
 
 
@@ -85,10 +85,10 @@ def test_cylinder3d_span_average_on_and_off():
     # one env step recorded per cell, and the same samples into a span-averaged record beside it
     env.start_field_statistics(span_average=False)
     spanned = CellMoments.for_domain(env._domain, span_average=True)
-    record = env._record_field_sample
-    env._record_field_sample = lambda: (record(), spanned.update(env._domain.velocity, env._domain.pressure))
+    hook = env._step_hooks["field_stats"]
+    record = hook.run
+    hook.run = lambda: (record(), spanned.update(env._domain.velocity, env._domain.pressure))
     env.step(torch.zeros(env._zero_action.shape, device=env.cuda_device))
-    del env._record_field_sample
     cells = env.stop_field_statistics()
     assert cells.samples == spanned.samples == env._n_sim_steps and cells.channels == ("u", "v", "w", "p")
     for i, (nx, ny, nz) in enumerate(sizes):

@@ -24,7 +24,7 @@ def _tcf_run(moments: bool, spectra: bool):
     """One env step from the same start; what was recorded and the state it left."""
     env = fluidgym_amd.make("TCFSmall3D-both-easy-v0", **TCF)
     env.reset(seed=4)
-    assert env._flow_spectra is None and env._flow_stats is None
+    assert env._hook("flow_spectra") is None and env._hook("flow_stats") is None
     if moments:
         env.start_flow_statistics(order=2)
     if spectra:
@@ -36,7 +36,7 @@ def _tcf_run(moments: bool, spectra: bool):
         out["moments"] = env.stop_flow_statistics()
     if spectra:
         out["spectra"] = env.stop_flow_spectra()
-        assert env._flow_spectra is None
+        assert env._hook("flow_spectra") is None
         with pytest.raises(RuntimeError, match="no spectra"):
             env.stop_flow_spectra()
     env.close()
@@ -82,7 +82,7 @@ def test_spectra_need_a_reset_a_valid_period_and_planes_of_the_grid():
         env.start_flow_spectra((1,), every=0)
     with pytest.raises(ValueError, match="outside the 16 rows"):
         env.start_flow_spectra((16,))
-    assert env._flow_spectra is None
+    assert env._hook("flow_spectra") is None
     env.start_flow_spectra((1,), every=2, symmetric=False)
     env.step(torch.zeros(env._zero_action.shape, device=env.cuda_device))
     rec = env.stop_flow_spectra()
@@ -96,7 +96,7 @@ def test_rbc2d_takes_the_spectrum_along_x_where_nx_is_a_power_of_two():
     assert env._block.velocity.shape[-1] == 24
     with pytest.raises(ValueError, match="nx must be a power of two"):
         env.start_flow_spectra((1,))
-    assert env._flow_spectra is None
+    assert env._hook("flow_spectra") is None
     env.close()
     env = fluidgym_amd.make("RBC2D-easy-v0", num_envs=2, n_heaters=4, resolution=8, randomize_initial_state=False, step_length=0.5)
     env.reset(seed=1)

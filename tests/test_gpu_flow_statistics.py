@@ -45,7 +45,7 @@ def test_tcf_statistics_count_match_the_wall_stress_and_leave_the_state_alone():
 
 def test_statistics_are_off_by_default_and_need_a_reset():
     env = fluidgym_amd.make("TCFSmall3D-both-easy-v0", **TCF)
-    assert env._flow_stats is None
+    assert env._hook("flow_stats") is None
     with pytest.raises(RuntimeError, match="reset"):
         env.start_flow_statistics()
     with pytest.raises(RuntimeError, match="no statistics"):
@@ -54,7 +54,7 @@ def test_statistics_are_off_by_default_and_need_a_reset():
     env.start_flow_statistics(order=2, every=2)
     env.step(torch.zeros(env._zero_action.shape, device=env.cuda_device))
     stats = env.stop_flow_statistics()
-    assert env._flow_stats is None and stats.n.tolist() == [float((env._n_sim_steps // 2) * 16 * 16)] * 2
+    assert env._hook("flow_stats") is None and stats.n.tolist() == [float((env._n_sim_steps // 2) * 16 * 16)] * 2
     env.close()
 
 

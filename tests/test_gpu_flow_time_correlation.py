@@ -67,7 +67,7 @@ def test_every_second_sim_step_halves_the_samples():
 
 def test_correlations_are_off_by_default_and_need_a_reset():
     env = fluidgym_amd.make("TCFSmall3D-both-easy-v0", **TCF)
-    assert env._flow_timecorr is None
+    assert env._hook("flow_timecorr") is None
     with pytest.raises(RuntimeError, match="reset"):
         env.start_flow_time_correlation(4)
     with pytest.raises(RuntimeError, match="no time correlations"):
@@ -79,11 +79,11 @@ def test_correlations_are_off_by_default_and_need_a_reset():
         env.start_flow_time_correlation(4, channels=("u", "v", "p"))          # a 2-D set on a 3-D domain
     with pytest.raises(ValueError, match="more than the 8"):
         env.start_flow_time_correlation(9, stride=1)
-    assert env._flow_timecorr is None
+    assert env._hook("flow_timecorr") is None
     env.start_flow_time_correlation(3)                                        # the reference's single base
     env.step(torch.zeros(env._zero_action.shape, device=env.cuda_device))
     corr = env.stop_flow_time_correlation()
-    assert env._flow_timecorr is None and corr.full and corr.count.tolist() == [1.0] * 3 and corr.samples == env._n_sim_steps
+    assert env._hook("flow_timecorr") is None and corr.full and corr.count.tolist() == [1.0] * 3 and corr.samples == env._n_sim_steps
     assert np.abs(corr.normalized("u")[..., 0] - 1.0).max() == 0.0
     env.close()
 

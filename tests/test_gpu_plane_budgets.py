@@ -172,7 +172,7 @@ def test_a_changed_batch_or_grid_raises():
 
 def test_tcf_env_records_what_a_host_twin_fed_through_the_same_hook_records(monkeypatch):
     env = fluidgym_amd.make("TCFSmall3D-both-easy-v0", **TCF)
-    assert env._flow_budgets is None
+    assert env._hook("flow_budgets") is None
     with pytest.raises(RuntimeError, match="reset"):
         env.start_flow_budgets()
     with pytest.raises(RuntimeError, match="no budgets"):
@@ -181,7 +181,7 @@ def test_tcf_env_records_what_a_host_twin_fed_through_the_same_hook_records(monk
     with pytest.raises(ValueError):
         env.start_flow_budgets(every=0)
     env.start_flow_budgets(every=2)
-    acc = env._flow_budgets
+    acc = env._hook("flow_budgets")
     blk = env._domain.getBlock(0)
     nz, ny, nx = blk.velocity.shape[2:]
     assert acc.wrap == (True, True) and acc.forcing == (blk.velocitySource is not None) and len(acc.y) == ny
@@ -201,7 +201,7 @@ def test_tcf_env_records_what_a_host_twin_fed_through_the_same_hook_records(monk
         env.step(zero)
     out = env.stop_flow_budgets()
     samples = (2 * env._n_sim_steps) // 2
-    assert out is acc and env._flow_budgets is None and len(fed) == samples
+    assert out is acc and env._hook("flow_budgets") is None and len(fed) == samples
     n, mean, cen = out._state()
     assert n.tolist() == [float(samples * nz * nx)] * 2
     truth = one_shot([channel_stack(smp, (acc.x, acc.y, acc.z), acc.forcing, acc.wrap) for smp in fed], acc.forcing)
@@ -212,14 +212,15 @@ def test_tcf_env_records_what_a_host_twin_fed_through_the_same_hook_records(monk
     print(f"env record against the host twin: mean {hm.max():.2e}, central {hc.max():.2e} of the absolute-monomial sum")
     assert np.array_equal(n, host._state()[0]) and hm.max() <= BOUND_GOLDEN and hc.max() <= BOUND_GOLDEN
     assert out.u_wall().shape == (2,) and np.isfinite(out.budget(0, 0, as_wall=True)["production"]).all()
-    # no budgets active: the step path must not reach the sampler at all
+    # no budgets active: the step path must not reach the sampler at all (it is the closure start_flow_budgets hands to the hook list)
     def boom(*a, **k):
         raise AssertionError("the budget sampler ran although no budgets are recorded")
 
-    monkeypatch.setattr(FlowStatisticsMixin, "_record_budgets_sample", boom)
+    monkeypatch.setattr(FlowStatisticsMixin, "start_flow_budgets", boom)
     monkeypatch.setattr(PlaneBudgets, "update", boom)
+    assert not env._step_hooks
     env.step(zero)
-    assert env._flow_budgets is None
+    assert env._hook("flow_budgets") is None
     env.close()
 
 

@@ -359,7 +359,7 @@ def test_env_start_and_stop_guards():
     with pytest.raises(RuntimeError, match="reset"):
         env.start_flow_histograms()
     env.reset(seed=1)
-    assert env._flow_hist is None
+    assert env._hook("flow_hist") is None
     with pytest.raises(RuntimeError, match="no histograms"):
         env.stop_flow_histograms()
     with pytest.raises(ValueError):
@@ -371,7 +371,7 @@ def test_env_start_and_stop_guards():
                               joint=(("v", "T"),), joint_bins=4)
     env.step(torch.zeros(2, 4, 1, device="cuda"))
     hist = env.stop_flow_histograms()
-    assert env._flow_hist is None and hist.n_samples == env._n_sim_steps // 2 and hist.counts("T").shape == (2, 2, 16)
+    assert env._hook("flow_hist") is None and hist.n_samples == env._n_sim_steps // 2 and hist.counts("T").shape == (2, 2, 16)
     with pytest.raises(RuntimeError, match="no histograms"):
         env.stop_flow_histograms()
     env.close()

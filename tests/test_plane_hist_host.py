@@ -383,7 +383,7 @@ def test_symbol_is_declared_typed_and_exported():
 
 def test_env_needs_a_reset_and_is_off_by_default():
     env = fluidgym_amd.make("RBC2D-easy-v0", num_envs=2, cuda_device="cpu")
-    assert env._flow_hist is None
+    assert env._hook("flow_hist") is None
     with pytest.raises(RuntimeError, match="reset"):
         env.start_flow_histograms()
     with pytest.raises(RuntimeError, match="no histograms"):
