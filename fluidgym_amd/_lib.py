@@ -94,6 +94,17 @@ class FgEnvSel(Structure):
     ]
 
 
+class FgMbResetNoise(Structure):
+    """The reset noise of ``fg_mb_restore_envs`` (``fg_mb_reset_noise``): the seed, the amplitudes on velocity and pressure and one
+    episode word per record (a host array)."""
+    _fields_ = [
+        ("seed", ctypes.c_uint64),
+        ("sigma_velocity", ctypes.c_double),
+        ("sigma_pressure", ctypes.c_double),
+        ("episodes", POINTER(ctypes.c_uint32)),
+    ]
+
+
 class FgFrameSpec(Structure):
     """Which plane of a field ``fg_frame_colorize`` draws, and how it is oriented (``fg_frame_spec``)."""
     _fields_ = [
@@ -315,6 +326,8 @@ SIGNATURES = {
     "fg_env_reset_solver_state": (c_int, [c_void_p, POINTER(FgEnvSel), c_int32, c_void_p]),
     "fg_mb_env_restore_field": (c_int, [c_void_p, c_int, c_void_p, c_int32, POINTER(FgEnvSel), c_int32, c_int32, c_void_p]),
     "fg_mb_env_reset_solver_state": (c_int, [c_void_p, POINTER(FgEnvSel), c_int32, c_void_p]),
+    "fg_mb_restore_envs": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, POINTER(FgEnvSel), c_int32, POINTER(FgMbResetNoise),
+                                   c_void_p]),
     "fg_set_pressure_refinement": (c_int, [c_void_p, c_int32, c_float, c_float]),
     "fg_get_buffer": (c_int, [c_void_p, c_int, POINTER(c_void_p), POINTER(c_int64)]),
     "fg_read_buffer": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),

@@ -63,6 +63,10 @@ struct MbBlock {
     std::vector<double> det;     // [ncells]
 };
 
+// one tile of the per-env restore (fg_mb_envrestore.hip): `count` <= 1024 consecutive elements, `start` onwards, of ONE segment -- the
+// cells of a block (face 0) or the slots of a FIXED face (face 1) -- that begins at `first` and is nz planes of `plane` elements
+struct MbRestoreTile { int32_t first, plane, nz, start, count, face; };
+
 // the viscosity as the step's kernels take it: the handle's scalar, or env b's entry of an installed array (fg_mb_set_viscosity_batch)
 struct MbNu {
     mb_real v; const mb_real* per_env;
@@ -125,6 +129,12 @@ struct fg_mb_state {
     int32_t* flags_pinned = nullptr;
     int32_t* sys_map_dev = nullptr;    // [B d] systems of a compacted launch (mb_bicgstab: MbSolve::sys_map); host copy in sys_map_pinned
     int32_t* sys_map_pinned = nullptr;
+    // per-env restore (fg_mb_envrestore.hip): tile table built at the first fg_mb_restore_envs (host; uploaded unless host_only), the
+    // span symmetry of the topology (nz when the handle is 3-D with every block z-periodic and of one nz, else 0), selection records [B]
+    std::vector<MbRestoreTile> restore_tiles;
+    int restore_nz = -1;               // -1: tables not built yet
+    MbRestoreTile* restore_tiles_dev = nullptr;
+    void* restore_sel_dev = nullptr;
     FG_MB_SWITCHES(FG_SW_MEMBER)       // every switch member of this handle family: declared, defaulted and described in fg_switches.h
     FgPoll poll = {};             // host polls on pinned sequence words (fg_internal.h FgPoll; created with the pinned mirrors)
     int32_t* verified = nullptr;   // [B d] BiCGStab convergence verification (mb_bicgstab): 0 open, 1 true residual checked, 2 being checked

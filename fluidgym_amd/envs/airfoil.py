@@ -283,6 +283,11 @@ class AirfoilEnvBase(CylinderEnvBase):
         for _ in range(n_steps):
             self._sim.single_step()
 
+    _mesh_reset_sigma = 0.01     # the noise of _randomize_domain, as reset_mesh_envs adds it per env
+
+    def _mesh_reset_warmup_env_steps(self) -> int:
+        return int(0.05 * self._episode_length)
+
     # ---- forces, actuation, step
     def _get_drag_and_lift(self):
         """[B] in 2-D; [B, NZ] per spanwise layer in 3-D (face area = edge length x D / res_z, :448-449)."""

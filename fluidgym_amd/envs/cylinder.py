@@ -30,6 +30,7 @@ from .cylinder_grid import BOTTOM, LEFT, RIGHT, TOP, build_domain, extrude_mesh,
 from .flow_statistics import FieldStatisticsMixin, FlowStatisticsMixin
 from .fluid_env import FluidEnv, is_per_env, per_env_parameter, refuse_per_env
 from .forces import WallRing
+from .mesh_reset import MeshResetMixin
 from .tracers import MeshTracerMixin
 
 CYLINDER_JET_2D_DEFAULT_CONFIG = {
@@ -46,7 +47,7 @@ ONCHIP_PCG_MAX_CELLS = 24 * 1024   # the multilevel-preconditioned on-chip CG (2
 VORTICITY_RENDER_LEVELS = {100: 1.5, 250: 2.5, 500: 3.5}   # jet_cylinder_env_3d.py:15-19: level of the 3-D picture, by Reynolds number
 
 
-class CylinderEnvBase(MeshTracerMixin, FieldStatisticsMixin, FlowStatisticsMixin, FluidEnv):      # (multi-block: the plane statistics refuse with
+class CylinderEnvBase(MeshResetMixin, MeshTracerMixin, FieldStatisticsMixin, FlowStatisticsMixin, FluidEnv):      # (multi-block: the plane statistics refuse with
                                                                                  # NotImplementedError, the per-cell ones record)
     _supports_marl = False
     _action_smoothing_alpha: float = 0.1
@@ -60,6 +61,7 @@ class CylinderEnvBase(MeshTracerMixin, FieldStatisticsMixin, FlowStatisticsMixin
     _vortex_street_refinement_base: float = 0.95
     _metrics = ["drag", "lift"]
     _initial_domain_steps = 400
+    _mesh_reset_sigma = 0.025    # the noise of _randomize_domain, as reset_mesh_envs adds it per env
 
     def __init__(self, reynolds_number: float, resolution: int, dt: float, adaptive_cfl: float, step_length: float,
                  episode_length: int, lift_penalty: float = 1.0, ndims: int = 2, initial_domain_steps: Optional[int] = None,
@@ -228,6 +230,10 @@ class CylinderEnvBase(MeshTracerMixin, FieldStatisticsMixin, FlowStatisticsMixin
         for _ in range(n_steps):
             self._sim.single_step()
 
+    def _mesh_reset_warmup_env_steps(self) -> int:
+        period = 1.0 / (0.3 * self._U_mean / self.cylinder_diameter)
+        return 2 * int(period / self._step_length) - 1
+
     # ---- observations, forces, step (cylinder_env_base.py:541-776)
     def _get_global_obs(self) -> Dict[str, torch.Tensor]:
         dom = self._domain
@@ -384,11 +390,12 @@ class CylinderEnvBase(MeshTracerMixin, FieldStatisticsMixin, FlowStatisticsMixin
         self._domain.Restore(snap)
 
     def _get_extra_state(self):
-        return {"last_control": self._last_control.clone()}
+        return {"last_control": self._last_control.clone(), "mesh_reset_count": self.mesh_reset_count.copy()}
 
     def _set_extra_state(self, extra) -> None:
         if extra is not None:
             self._last_control = extra["last_control"].clone()
+        self.mesh_reset_count[:] = (extra or {}).get("mesh_reset_count", 0)      # a state from before the counter loads zeros
 
     def render(self, *a, **kw) -> np.ndarray:
         speed = torch.linalg.vector_norm(self.get_velocity()[0], dim=0)

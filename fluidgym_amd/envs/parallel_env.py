@@ -643,6 +643,15 @@ class ParallelFluidEnv:
     def set_state_bank(self, states, env: Optional[int] = None) -> None:
         raise NotImplementedError("set_state_bank is not implemented for ParallelFluidEnv.")
 
+    def reset_mesh_envs(self, envs, randomize: Optional[bool] = None):
+        raise NotImplementedError("reset_mesh_envs is not implemented for ParallelFluidEnv.")
+
+    def set_mesh_state_bank(self, states, env: Optional[int] = None) -> None:
+        raise NotImplementedError("set_mesh_state_bank is not implemented for ParallelFluidEnv.")
+
+    def record_mesh_state_bank(self, n_states: int, every: Optional[int] = None):
+        raise NotImplementedError("record_mesh_state_bank is not implemented for ParallelFluidEnv.")
+
     def probe(self, points, fields=None):
         raise NotImplementedError("probe is not implemented for ParallelFluidEnv.")
 

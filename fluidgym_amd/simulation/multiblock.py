@@ -686,6 +686,62 @@ class MultiBlockDomain:
         if "solver_hints" in snap:
             self.solver_hints(snap["solver_hints"].tolist())
 
+    def span_nz(self) -> Optional[int]:
+        """``nz`` when a mirror and a roll along z map a state of this mesh onto a state of it (``mb_state_bank.span_symmetry``
+        of the blocks' vertices), else None; worked out once."""
+        if not hasattr(self, "_span_nz"):
+            from .mb_state_bank import span_symmetry
+
+            self._span_nz = span_symmetry([b.coords for b in self.blocks], [2 in b.periodic_axes for b in self.blocks]) if self.dims == 3 else None
+        return self._span_nz
+
+    def RestoreEnvs(self, bank, envs, src=0, flip_z=0, shift_z=0, noise=None):
+        """Restore the envs ``envs`` -- and no other -- from states of ``bank`` (a ``MeshStateBank``): velocity, pressure and
+        boundary velocity of env ``envs[i]`` become those of state ``src[i]``, mirrored along the span where ``flip_z[i]`` and then
+        rolled by ``shift_z[i]`` layers -- per block and per FIXED face ``torch.roll(torch.flip(t, [z]), shift, z)``, with the sign
+        change of ``w`` under the mirror (every argument one value or one per chosen env).  The pressure is transformed with the
+        velocity.  ``noise``: None, or ``(seed, sigma_velocity, sigma_pressure, episodes)`` -- counter-based Gaussian noise on
+        velocity and pressure that depends on (seed, env, ``episodes[i]``, component, cell) only (``fg_mb_restore_envs``).  ONE
+        call into the library, one launch; returns the selection records.
+
+        ``ValueError`` for what the library refuses -- an index out of range, an env named twice, a flip that is not 0 / 1, a shift
+        outside ``[0, nz)``, a sigma that is negative or not finite, a bank of another layout -- and for a mirror or roll on a mesh
+        that is no equal-layer, z-periodic prism (``span_nz``)."""
+        from .state_bank import _per_env, build_selection
+
+        if not self.prepared:
+            raise RuntimeError("RestoreEnvs: PrepareSolve() first")
+        envs = [int(e) for e in (envs.tolist() if isinstance(envs, (np.ndarray, torch.Tensor)) else envs)]
+        n, nz = len(envs), self.span_nz()
+        if nz is None and (any(_per_env(flip_z, max(n, 1), "flip_z")) or any(_per_env(shift_z, max(n, 1), "shift_z"))):
+            raise ValueError("RestoreEnvs: flip_z / shift_z need a 3-D mesh whose blocks are all z-periodic, of one nz, with the same x "
+                             "and y in every layer and equally thick layers (mb_state_bank.span_symmetry)")
+        sel = build_selection(envs, src, None, flip_z, None, shift_z, batch=self.batch, n_states=bank.size, dims=self.dims, nx=1,
+                              nz=nz or 1, periodic_x=False, periodic_z=nz is not None)
+        for k, dst in (("velocity", self.velocity), ("pressure", self.pressure), ("boundary_velocity", self.boundary_velocity)):
+            t = bank.fields[k]
+            if tuple(t.shape[1:]) != tuple(dst.shape[1:]) or t.dtype != dst.dtype or t.device != dst.device or not t.is_contiguous():
+                raise ValueError(f"RestoreEnvs: the bank's {k} {tuple(t.shape[1:])} {t.dtype} on {t.device} does not match the "
+                                 f"domain's {tuple(dst.shape[1:])} {dst.dtype} on {dst.device}")
+        rec = None
+        if noise is not None:
+            seed, sigma_u, sigma_p, episodes = noise
+            sigma_u, sigma_p = float(sigma_u), float(sigma_p)
+            if not (np.isfinite(sigma_u) and np.isfinite(sigma_p) and sigma_u >= 0.0 and sigma_p >= 0.0):
+                raise ValueError("RestoreEnvs: a noise amplitude is negative or not finite")
+            if self.n_cells > 1 << 26:
+                raise ValueError("RestoreEnvs: reset noise needs at most 2^26 cells")
+            ep = [int(e) & 0xFFFFFFFF for e in _per_env(episodes, n, "episodes")]
+            self._restore_episodes = (ctypes.c_uint32 * n)(*ep)
+            rec = L.FgMbResetNoise(int(seed) & 0xFFFFFFFFFFFFFFFF, sigma_u, sigma_p, self._restore_episodes)
+        st = torch.cuda.current_stream(self.device).cuda_stream
+        nb = self.n_boundary_faces
+        L.check(self.lib.fg_mb_restore_envs(self.handle, ctypes.c_void_p(bank.fields["velocity"].data_ptr()),
+                                            ctypes.c_void_p(bank.fields["pressure"].data_ptr()),
+                                            ctypes.c_void_p(bank.fields["boundary_velocity"].data_ptr()) if nb else None, bank.size, sel, n,
+                                            None if rec is None else ctypes.byref(rec), ctypes.c_void_p(st)), lib=self.lib)
+        return sel
+
     @property
     def solver(self):
         return self

@@ -1104,6 +1104,38 @@ int fg_mb_solver_hints(fg_mb_handle h, int32_t* hints48, int32_t set);
 int fg_mb_env_restore_field(fg_mb_handle h, int which_field, const fg_real* bank, int32_t S, const fg_env_sel* sel, int32_t n_sel,
                             int32_t signed_components, void* stream);
 int fg_mb_env_reset_solver_state(fg_mb_handle h, const fg_env_sel* sel, int32_t n_sel, void* stream);
+/* ---- per-env restore of a multi-block handle from a bank of stored states (csrc/fg_mb_envrestore.hip) ----
+ * A multi-block handle carries three per-env arrays between steps -- velocity [B][d][N], pressure [B][N] and the boundary velocity
+ * [B][d][NB] -- and ONE launch restores all three for every record of sel (the records of fg_env_restore_field; flip_x and shift_x
+ * must be 0): env `env` becomes state `src` of the banks, mirrored (flip_z) and then rolled (shift_z) along the span.  The span is a
+ * symmetry of the topology when the handle is 3-D and every block is z-periodic with one nz (whether the layers are equally thick is
+ * the caller's business: simulation/mb_state_bank.span_symmetry); on every other handle flip_z and shift_z must be 0 and the restore
+ * is a copy.  The cells of a block, cell_offset + (z ny + y) nx + x, and the slots of a FIXED x- or y-face, slot0 + z len + t, are
+ * segments {first, plane, nz}, and on both
+ *     dst[first + z plane + r] = sign(c) bank[src][first + zs plane + r],  zs = flip_z ? nz-1 - ((z - shift_z) mod nz) : (z - shift_z) mod nz
+ * with sign(c) = -1 for component 2 of the velocity and of the boundary velocity under flip_z, else +1: per block and per face
+ * torch.roll(torch.flip(t, [z]), shift_z, z).  Envs not named in sel are not written.
+ * noise (NULL: every value is a copy or a negation): counter-based Gaussian reset noise on velocity (sigma_velocity) and pressure
+ * (sigma_pressure), none on the boundary values.  Destination cell i of component tag c (0..d-1 velocity, d pressure) takes normal
+ * i % 4 of the Philox4x32-10 block with key (seed low, seed high) and counter ((c << 24) | (i / 4), env, episodes[k], 0xFFFFFFFF) for
+ * record k -- the stream of fg_obs_noise_add with a step word that the observation noise never reaches -- and dst = value +
+ * (float)sigma z in the fp32 library, value + sigma (double)z in the fp64 one.  It depends on (seed, env, episode, c, i) only: not on
+ * the batch, nor on the other records of the call.
+ * sel and noise->episodes are HOST arrays [n_sel]; they are checked here, uploaded in one copy to an array the handle owns and read by
+ * the one launch; the call is asynchronous on `stream`.  Every check comes before any launch and before the bound-field check, so a
+ * host-only handle (device < 0) answers every refusal.  FG_ERR_INVALID_ARG: a null handle, sel or bank (bank_boundary may be NULL
+ * when NB == 0), S < 1, n_sel outside 1..B, an env out of range or named twice, src outside [0, S), a non-zero flip_x or shift_x, a
+ * flip that is not 0 / 1, shift_z outside [0, nz), flip_z or shift_z where the span is no symmetry of the topology, a sigma that is
+ * negative or not finite.  FG_ERR_UNSUPPORTED: noise with N > 2^26 (the first counter word).  FG_ERR_NOT_BOUND: the handle is not
+ * finalised or has no bound fields. */
+typedef struct fg_mb_reset_noise {
+    uint64_t seed;
+    double sigma_velocity, sigma_pressure;
+    const uint32_t* episodes;  /* host [n_sel] */
+} fg_mb_reset_noise;
+int fg_mb_restore_envs(fg_mb_handle h, const fg_real* bank_velocity /*[S][d][N]*/, const fg_real* bank_pressure /*[S][N]*/,
+                       const fg_real* bank_boundary /*[S][d][NB], may be NULL when NB == 0*/, int32_t S, const fg_env_sel* sel,
+                       int32_t n_sel, const fg_mb_reset_noise* noise /*NULL: pure copy*/, void* stream);
 /* as fg_solver_counters, for the multi-block path */
 int fg_mb_solver_counters(fg_mb_handle h, int64_t* out13_host, int32_t reset);
 /* The tuning / diagnosis switches a handle runs under (the FG_* environment variables read ONCE at create time, docs/SWITCHES.md,
