@@ -361,6 +361,10 @@ SIGNATURES = {
     "fg_mb_cell_moments": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int64, POINTER(c_int64), c_int32, c_int64, c_void_p, c_void_p,
                                    c_void_p]),
     "fg_mb_cell_moments_widths": (c_int, [c_void_p, c_void_p, c_int64, POINTER(c_int64), c_int32, c_void_p, c_void_p, POINTER(c_int32)]),
+    "fg_mb_wall_distribution": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int32,
+                                        c_int32, c_float, c_void_p, c_void_p, c_void_p]),
+    "fg_mb_wall_moments": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int32,
+                                   c_int32, c_float, c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_void_p]),
     "fg_plane_spectra": (c_int, [POINTER(c_void_p), POINTER(c_int64), c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_int32), c_int32,
                                  c_void_p, c_void_p, c_void_p]),
     "fg_plane_histogram": (c_int, [POINTER(c_void_p), POINTER(c_int64), c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_int32), c_int32,

@@ -81,6 +81,7 @@ class AirfoilEnvBase(CylinderEnvBase):
     D: float = 1.4
     _metrics = ["drag", "lift"]
     _initial_domain_steps = 400
+    _wall_family = "airfoil"            # the surface curves carry x / c and the side (envs/surface.py)
 
     def __init__(self, ndims: int, reynolds_number: float, adaptive_cfl: float, step_length: float, episode_length: int,
                  dt: float, attack_angle_deg: float, initial_domain_steps: Optional[int] = None,
@@ -294,6 +295,9 @@ class AirfoilEnvBase(CylinderEnvBase):
         f = self._ring.forces(self._domain, self._nu, layer_height=self.D / getattr(self, "_res_z", 1))
         norm = 0.5 * self.U_mean ** 2 * self.airfoil_length
         return f[:, 0] / norm, f[:, 1] / norm
+
+    def _wall_force_args(self):
+        return self._nu, self.D / getattr(self, "_res_z", 1)
 
     def _action_to_control(self, action: torch.Tensor) -> torch.Tensor:
         raise NotImplementedError

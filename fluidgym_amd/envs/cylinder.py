@@ -31,6 +31,7 @@ from .flow_statistics import FieldStatisticsMixin, FlowStatisticsMixin
 from .fluid_env import FluidEnv, is_per_env, per_env_parameter, refuse_per_env
 from .forces import WallRing
 from .mesh_reset import MeshResetMixin
+from .surface import SurfaceMixin
 from .tracers import MeshTracerMixin
 
 CYLINDER_JET_2D_DEFAULT_CONFIG = {
@@ -47,7 +48,7 @@ ONCHIP_PCG_MAX_CELLS = 24 * 1024   # the multilevel-preconditioned on-chip CG (2
 VORTICITY_RENDER_LEVELS = {100: 1.5, 250: 2.5, 500: 3.5}   # jet_cylinder_env_3d.py:15-19: level of the 3-D picture, by Reynolds number
 
 
-class CylinderEnvBase(MeshResetMixin, MeshTracerMixin, FieldStatisticsMixin, FlowStatisticsMixin, FluidEnv):      # (multi-block: the plane statistics refuse with
+class CylinderEnvBase(SurfaceMixin, MeshResetMixin, MeshTracerMixin, FieldStatisticsMixin, FlowStatisticsMixin, FluidEnv):      # (multi-block: the plane statistics refuse with
                                                                                  # NotImplementedError, the per-cell ones record)
     _supports_marl = False
     _action_smoothing_alpha: float = 0.1
@@ -311,6 +312,9 @@ class CylinderEnvBase(MeshResetMixin, MeshTracerMixin, FieldStatisticsMixin, Flo
         f = self._ring.forces(self._domain, self._nu_forces, layer_height=self.D / self._circle_resolution_angular)
         norm = 0.5 * self._U_mean ** 2 * self.cylinder_diameter
         return f[:, 0] / norm, f[:, 1] / norm
+
+    def _wall_force_args(self):
+        return self._nu_forces, self.D / self._circle_resolution_angular
 
     def _apply_action(self, action: torch.Tensor) -> None:
         raise NotImplementedError

@@ -165,13 +165,26 @@ class FlowStatisticsMixin:
 
 
 class FieldStatisticsMixin:
-    def start_field_statistics(self, every: int = 1, span_average: bool = True) -> None:
+    def start_field_statistics(self, every: int = 1, span_average: bool = True, surface: bool = False) -> None:
         """Start a fresh per-cell record of ``u, v(, w), p``; a sample is taken after every ``every``-th sim step of ``step()`` (the
         fields are read, never written).  ``span_average`` (3-D): one column per ``(block, y, x)``, averaged over the span; off,
-        every cell is recorded."""
+        every cell is recorded.  ``surface``: the same hook also records the wall curves ``p, tau_w, fx, fy`` of the env's wall ring
+        (``simulation/wall_stats.WallMoments``, one more launch per sample, with the viscosity of the env's drag and lift -- env b's own
+        where the batch has one per env); the record ``stop_field_statistics`` hands out carries it as ``.surface`` (None otherwise)."""
         _check_start(self, "start_field_statistics")
         stats = CellMoments.for_domain(self._domain, span_average)
-        self._start_hook("field_stats", stats, every, lambda: stats.update(self._domain.velocity, self._domain.pressure))
+        if not surface:
+            self._start_hook("field_stats", stats, every, lambda: stats.update(self._domain.velocity, self._domain.pressure))
+            return
+        if getattr(self, "_ring", None) is None:
+            raise NotImplementedError("start_field_statistics(surface=True) needs an env with a wall ring (cylinder, airfoil envs)")
+        wall = stats.surface = self._ring.moments(self._domain.batch, self._domain.dtype, span_average)
+
+        def sample():
+            stats.update(self._domain.velocity, self._domain.pressure)
+            wall.update(self._domain, self._wall_force_args()[0])
+
+        self._start_hook("field_stats", stats, every, sample)
 
     def stop_field_statistics(self) -> CellMoments:
         """Stop recording and hand out the record (on the GPU; its accessors, ``pooled()`` and ``save`` read it back)."""

@@ -120,6 +120,59 @@ class WallRing:
         self.wall_distances, self.wall_normals = dist.to(**f32), normals.to(**f32)
         self.tangent_lengths, self.face_lengths = tl.to(**f32), fl.to(**f32)
         self._native = None   # int32 index tables + packed geometry of fg_mb_wall_forces, built on first use
+        self._native_as = {}  # dtype -> the same tables with the geometry in that dtype (fg_mb_wall_distribution / _moments)
+        self.n_faces = int(fl.shape[0])
+        # the curve coordinates of the faces (host, fp64): midpoints of the face vertices, and the length along the ring from the
+        # first vertex to each midpoint
+        fl64 = fl.numpy()
+        self.face_centers = (0.5 * (vc[:, 1:] + vc[:, :-1])).numpy()                                 # [2, n]
+        self.arc_length = np.concatenate([[0.0], np.cumsum(fl64)[:-1]]) + 0.5 * fl64                 # [n]
+
+    def native_tables(self, dtype=torch.float32):
+        """``(cell_index, slot_index, geom)`` as the wall kernels take them: the int32 ``[layers, n]`` tables ``forces`` builds on first
+        use and its packed geometry ``[5, n]``, in ``dtype`` (one copy per dtype, kept)."""
+        if self._native is None:
+            i32 = dict(dtype=torch.int32, device=self.cell_index.device)
+            geom = torch.stack([self.wall_normals[0], self.wall_normals[1], self.tangent_lengths, self.wall_distances,
+                                self.face_lengths]).contiguous()
+            self._native = (self.cell_index.reshape(self.nz, -1).to(**i32).contiguous(),
+                            self.slot_index.reshape(self.nz, -1).to(**i32).contiguous(), geom)
+        if dtype not in self._native_as:
+            ci, si, geom = self._native
+            self._native_as[dtype] = (ci, si, geom if geom.dtype == dtype else geom.to(dtype).contiguous())
+        return self._native_as[dtype]
+
+    def distribution(self, domain, viscosity, out: torch.Tensor = None) -> torch.Tensor:
+        """``[B, 4, layers, n]`` (``layers`` = 1 in 2-D): per wall face the channels ``p, tau_w, fx, fy`` of
+        ``simulation/wall_stats.py`` -- the wall-adjacent pressure, the wall shear stress along the ring tangent ``(ny, -nx)`` and the
+        traction whose sum with the face lengths is ``forces`` -- from the domain's current fields, in ONE launch of
+        ``fg_mb_wall_distribution``.  ``viscosity``: a float, or a ``[B]`` tensor for one value per env.  Asynchronous on the current
+        stream."""
+        from ..simulation import plane_fields as F
+        from ..simulation.wall_stats import K, check_wall_fields, wall_viscosity
+        from .. import _lib as L
+
+        u, ub, p = check_wall_fields(domain, "WallRing.distribution")
+        ci, si, geom = self.native_tables(u.dtype)
+        B, shape = int(u.shape[0]), (int(u.shape[0]), K, self.nz, self.n_faces)
+        if out is None:
+            out = torch.empty(shape, dtype=u.dtype, device=u.device)
+        elif tuple(out.shape) != shape or out.dtype != u.dtype or not out.is_contiguous() or out.device != u.device:
+            raise ValueError("distribution: out must be a contiguous [B, 4, layers, n] tensor of the domain's dtype on its device")
+        nu, nu_B = wall_viscosity(viscosity, B, u)
+        lib = F.library(u.dtype)
+        with torch.cuda.device(u.device):
+            L.check(lib.fg_mb_wall_distribution(F.ptr(u), F.ptr(ub), F.ptr(p), int(u.shape[1]), B, int(u.shape[2]), int(ub.shape[2]),
+                                                F.ptr(ci), F.ptr(si), F.ptr(geom), self.n_faces, self.nz, nu,
+                                                None if nu_B is None else F.ptr(nu_B), F.ptr(out), F.stream_ptr(u.device)), lib=lib)
+        return out
+
+    def moments(self, batch: int, dtype=torch.float32, span_average: bool = True):
+        """A fresh ``WallMoments`` (``simulation/wall_stats.py``) of this ring for ``batch`` envs: the online mean and central sums
+        of the four channels, one launch of ``fg_mb_wall_moments`` per ``update(domain, viscosity)``."""
+        from ..simulation.wall_stats import WallMoments
+
+        return WallMoments.for_ring(self, batch, dtype, span_average)
 
     def forces(self, domain, viscosity, layer_height: float = 1.0, out: torch.Tensor = None) -> torch.Tensor:
         """(``viscosity``: a float, or a ``[B]`` tensor for one value per env.)  [B, 2] force on the wall from the domain's current fields; [B, 2, NZ] per spanwise layer in 3-D (``out``: a contiguous
@@ -128,11 +181,7 @@ class WallRing:
         reference's own function in tests/test_env_math_golden.py -- costs ~40 launches per sim step and is what the kernel is
         tested against)."""
         if self._native is None:
-            i32 = dict(dtype=torch.int32, device=self.cell_index.device)
-            geom = torch.stack([self.wall_normals[0], self.wall_normals[1], self.tangent_lengths, self.wall_distances,
-                                self.face_lengths]).contiguous()
-            self._native = (self.cell_index.reshape(self.nz, -1).to(**i32).contiguous(),
-                            self.slot_index.reshape(self.nz, -1).to(**i32).contiguous(), geom)
+            self.native_tables()
         out = domain.wall_forces(*self._native, float(layer_height) if self.dims == 3 else 1.0,
                                  viscosity if isinstance(viscosity, torch.Tensor) else float(viscosity), out=out)   # [B, 2, NZ]
         return out if self.dims == 3 else out[:, :, 0]

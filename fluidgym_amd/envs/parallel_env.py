@@ -670,6 +670,9 @@ class ParallelFluidEnv:
     def stop_mesh_tracers(self):
         raise NotImplementedError("stop_mesh_tracers is not implemented for ParallelFluidEnv.")
 
+    def get_surface_distribution(self, p_ref=0.0):
+        raise NotImplementedError("get_surface_distribution is not implemented for ParallelFluidEnv.")
+
     def save_gif(self, filename: str, output_path=None) -> None:
         raise NotImplementedError("save_gif is not implemented for ParallelFluidEnv.")
 

@@ -106,6 +106,7 @@ class CellRecord:
 
     # ---- where the arrays live: overridden by CellMoments
     _mean = _central = None
+    surface = None      # the WallMoments recorded beside it (start_field_statistics(surface=True)), else None
 
     def _state(self):
         if self._mean is None:

@@ -581,6 +581,44 @@ int fg_mb_cell_moments(const fg_real* velocity, const fg_real* pressure, int32_t
  * dereferenced but block_table and widths, nothing is launched.  Same argument checks and codes as fg_mb_cell_moments. */
 int fg_mb_cell_moments_widths(const fg_real* velocity, const fg_real* pressure, int64_t n_cells, const int64_t* block_table,
                               int32_t n_blocks, const double* mean, const double* central, int32_t* widths);
+/* ---- wall distributions of multi-block domains and their online statistics (csrc/fg_wallstats.hip; both libraries, handle-free) --
+ * The integrand of fg_mb_wall_forces per wall face (WallRing.distribution, envs/forces.py) and one sample of WallMoments
+ * (simulation/wall_stats.py): the reference sums the traction over the ring (compute_forces_2d / _3d, envs/util/forces.py:193-377)
+ * and keeps no curve.
+ *   velocity [batch][dims][n_cells], boundary_velocity [batch][dims][n_slots], pressure [batch][n_cells]
+ *                    the flat fields of a multi-block domain, contiguous, read in place (the in-plane components 0 and 1 are read)
+ *   cell_index, slot_index [layers][n]   int32, DEVICE: wall-adjacent cell and boundary slot of every face, in ring order
+ *   geom [5][n]      DEVICE: normal x, normal y, tangential spacing, wall distance, face length (the packing of fg_mb_wall_forces;
+ *                    the face length is not read)
+ *   viscosity, viscosity_B   the scalar, or (non-NULL) one viscosity per env, [batch] on the device
+ * A face (b, layer, j) is the arithmetic of fg_mb_wall_forces without the face length -- neighbours cl = ci[j + 1 mod n],
+ * cr = ci[j - 1 mod n], dn = (u[c] - ub[slot]) / distance, dt = (u[cr] - u[cl]) / (2 spacing), the composed gradients, sxy -- and
+ * gives four channels in fg_real:
+ *   0  p      the pressure of the wall-adjacent cell
+ *   1  tau_w  the viscous traction along the ring tangent t = (ny, -nx)
+ *   2  fx     (2 nu du_dx - p) nx + 2 nu sxy ny
+ *   3  fy     2 nu sxy nx + (2 nu dv_dy - p) ny
+ * The file is compiled with -ffp-contract=off: every product, sum and division is rounded on its own, a face depends on its own
+ * cells only -- not on `batch`, the other envs or the launch -- and repeats bit for bit; both entries compute the same bits.  An
+ * index outside [0, n_cells) / [0, n_slots) is not dereferenced: its face is NaN in all four channels.
+ * fg_mb_wall_distribution: out [batch][4][layers][n], one thread per face, ONE launch.
+ * fg_mb_wall_moments: a record is face j over all layers (span_average != 0: R = n, n_B = layers) or one face (R = layers * n,
+ * n_B = 1); per record the mean of the four channels over its faces and the 10 sums of d_i d_j (i <= j; i ascending, then j), both in
+ * fp64, the layers ascending, in two passes, merged into mean [batch][4][R], central [batch][10][R] (fp64, device, updated in
+ * place) by the order-2 rule of fg_plane_moments with n_A = samples * n_B.  `samples`: calls already merged, counted by the HOST; 0
+ * stores the sample (the accumulators need no initialisation).  One thread per record, ONE launch; no floating-point atomic, no
+ * cross-lane operation, no device counter.
+ * Both are asynchronous on `stream`; nothing returns to the host.  FG_ERR_INVALID_ARG, before anything is launched: a null pointer
+ * (viscosity_B excepted), dims outside 2..3, batch outside 1..65535, a non-positive n or layers, n_cells or n_slots outside
+ * 1..2^31 - 1, more than 2^31 - 1 faces, samples outside 0..2^40 - 1. */
+int fg_mb_wall_distribution(const fg_real* velocity, const fg_real* boundary_velocity, const fg_real* pressure, int32_t dims,
+                            int32_t batch, int64_t n_cells, int64_t n_slots, const int32_t* cell_index, const int32_t* slot_index,
+                            const fg_real* geom, int32_t n, int32_t layers, fg_real viscosity, const fg_real* viscosity_B, fg_real* out,
+                            void* stream);
+int fg_mb_wall_moments(const fg_real* velocity, const fg_real* boundary_velocity, const fg_real* pressure, int32_t dims, int32_t batch,
+                       int64_t n_cells, int64_t n_slots, const int32_t* cell_index, const int32_t* slot_index, const fg_real* geom,
+                       int32_t n, int32_t layers, fg_real viscosity, const fg_real* viscosity_B, int32_t span_average, int64_t samples,
+                       double* mean, double* central, void* stream);
 /* ---- online Reynolds-stress budgets of channel flows (csrc/fg_planebudgets.hip; both libraries, handle-free) -------------------
  * One sample of PlaneBudgets (simulation/plane_budgets.py; the reference's TurbulentEnergyBudgetsOnlineParallel_Torch,
  * online_statistics.py:790-1268): for every row (env, y) the means over (z, x) of K channels -- u, v, w, the three pressure gradients,
