@@ -131,6 +131,57 @@ def make_case(dims=2, n=(16, 12), fixed_axes: Sequence[int] = (), B=2, seed=0, s
     return Case(dims, shape, edges, widths, fixed_faces, B, nu, velocity, bvel, scalar, bscal, scalar_bc, kappa, source)
 
 
+def slab_areas(case: Case, face: int) -> np.ndarray:
+    """Face areas of the slab entries of ``face`` in slab shape: the product of the other axes' widths (the fp32 widths as doubles)."""
+    d, a = case.dims, face >> 1
+    area = np.ones([1 if k == d - 1 - a else s for k, s in enumerate(case.shape)])
+    for o in range(d):
+        if o != a:
+            shape = [1] * d
+            shape[d - 1 - o] = -1
+            area = area * np.asarray(case.widths[o], np.float64).reshape(shape)
+    return area
+
+
+def with_normal_flux(case: Case, seed: int, amp: float = 0.3) -> Case:
+    """``case`` with a non-zero normal velocity on every fixed face (``make_case`` leaves it zero): per env and face random values
+    of zero area-weighted mean, plus a through-flow ``0.2 (a + 1) (-1)^b`` along every fixed axis ``a`` whose direction differs
+    between the envs ``b``.  Each face's random part carries no net flux and the through-flow enters one face of an axis and leaves
+    the other (rectilinear grid: equal total areas), so the boundary fluxes balance and the pressure system stays compatible.  The
+    tangential components are left alone."""
+    rng = np.random.default_rng(seed)
+    for b in range(case.B):
+        for f in sorted(case.fixed_faces):
+            a = f >> 1
+            area = slab_areas(case, f)
+            v = amp * rng.standard_normal(case.bvel[f][b, a].shape)
+            case.bvel[f][b, a] = v - (v * area).sum() / area.sum()
+    for f in case.fixed_faces:
+        a = f >> 1
+        for b in range(case.B):
+            case.bvel[f][b, a] += 0.2 * (a + 1) * (-1) ** b
+    return case
+
+
+# the kernel-parity cases with through-flow on every fixed face (tests/test_normal_flux_inputs.py, tests/test_gpu_normal_flux.py)
+NORMAL_FLUX_CASES = {
+    "2d_box": dict(dims=2, n=(16, 12), fixed_axes=(0, 1)),                   # all four faces, four cells per thread
+    "2d_walls_y": dict(dims=2, n=(32, 12), fixed_axes=(1,)),                 # y faces, periodic x
+    "2d_walls_y_vec1": dict(dims=2, n=(18, 11), fixed_axes=(1,)),            # nx % 4 != 0 -> scalar lanes
+    "3d_box_vec1": dict(dims=3, n=(10, 7, 6), fixed_axes=(0, 1, 2)),         # all six faces
+    "3d_channel": dict(dims=3, n=(16, 10, 8), fixed_axes=(1,)),              # wall-normal blowing / suction of a 3-D channel
+    "3d_walls_z_tile_edges": dict(dims=3, n=(68, 6, 5), fixed_axes=(2,)),    # z faces, tiles partially filled in every axis
+    "2d_scalar": dict(dims=2, n=(24, 16), fixed_axes=(1,), n_scalars=1, neumann_faces=(3,)),          # Dirichlet and Neumann scalar faces
+    "3d_scalar_box": dict(dims=3, n=(12, 6, 5), fixed_axes=(0, 1, 2), n_scalars=1, neumann_faces=(4,)),
+}
+NORMAL_FLUX_DT = [0.04, 0.025]
+
+
+def normal_flux_case(name: str, normal_flux: bool = True) -> Case:
+    case = make_case(**NORMAL_FLUX_CASES[name], B=2, seed=21, with_source=True, vel_scale=0.3)
+    return with_normal_flux(case, 5) if normal_flux else case
+
+
 def rel_err(a: np.ndarray, b: np.ndarray) -> float:
     """max |a-b| / max |b|  (the gate of SURVEY.md section 8d)."""
     scale = max(float(np.abs(b).max()), 1e-30)

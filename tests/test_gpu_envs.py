@@ -1,6 +1,9 @@
 """Env-level tests on the GPU: the reset()/step() contract (reference tests/envs/test_all_envs.py:52-100
 check shapes / types / metric keys the same way), the native outflow-boundary + adaptive-CFL driver
 against the oracle, batching semantics, get_state / set_state."""
+import functools
+from concurrent.futures import ThreadPoolExecutor
+
 import numpy as np
 import pytest
 import torch
@@ -148,29 +151,82 @@ def test_batched_env_equals_independent_envs():
     env1.close()
 
 
-@pytest.mark.parametrize("driver", ["native", "python_hooks"])
-def test_channel_driver_with_outflow_matches_oracle(driver):
-    """Simulation.single_step (flux guard, adaptive CFL, native advective outflow + flux re-balancing, fused
-    PISO step) against the oracle's restatement of the same sequence, 6 steps, per-env different inflow."""
-    nx, ny, L, H, nu, dt, B = 48, 24, 6.0, 2.0, 0.02, 0.06, 2
-    edges = [np.linspace(0, L, nx + 1), np.linspace(-H / 2, H / 2, ny + 1)]
-    dom = Domain(2, torch.tensor([nu]), batch=B)
-    blk = dom.CreateBlock(grids.vertex_grid(edges))
-    blk.CloseBoundary("-x")
-    blk.CloseBoundary("-y")
-    dom.PrepareSolve()
+# geometry -> (n, flow axis, sim steps): a duct of cross-section 2 (x 2) whose cells are 0.125 long along the flow; inflow on the lower
+# face of the flow axis, advective outflow on the upper one, walls on the other faces
+OUTFLOW_GEOMETRIES = {
+    "x": ((48, 24), 0, 6),
+    "y": ((24, 48), 1, 6),               # the same channel turned by 90 degrees: outflow face 3, walls on x
+    "z_folded": ((12, 10, 8), 2, 3),     # outflow face 5; slab 120: the update is folded into the balance launch
+    "z_separate": ((40, 28, 6), 2, 3),   # slab 1120 > 4 x 256: a k_outflow launch of its own
+}
+
+
+def _outflow_inputs(geometry):
+    """(edges, inflow [B, d, slab], u0 [B, d, cells], velm) of a geometry: a parabolic inflow profile that differs per env, noise."""
+    n, flow, _ = OUTFLOW_GEOMETRIES[geometry]
+    d = len(n)
+    H, B = 2.0, 2
+    edges = [np.linspace(0, 0.125 * n[a], n[a] + 1) if a == flow else np.linspace(-H / 2, H / 2, n[a] + 1) for a in range(d)]
+    shape = tuple(reversed(n))
     rng = np.random.default_rng(0)
-    yc = 0.5 * (edges[1][1:] + edges[1][:-1])
-    inflow = np.zeros((B, 2, ny, 1))
+    slab = tuple(1 if k == d - 1 - flow else s for k, s in enumerate(shape))
+    inflow = np.zeros((B, d) + slab)
     for b in range(B):
-        inflow[b, 0, :, 0] = (1.0 + 0.3 * b) * 1.5 * (1 - (2 * yc / H) ** 2)
-    u0 = np.broadcast_to(inflow, (B, 2, ny, nx)).copy() + 0.05 * rng.standard_normal((B, 2, ny, nx))
+        prof = (1.0 + 0.3 * b) * 1.5
+        for a in range(d):
+            if a != flow:
+                c = 0.5 * (edges[a][1:] + edges[a][:-1])
+                prof = prof * (1 - (2 * c / H) ** 2).reshape([-1 if k == d - 1 - a else 1 for k in range(d)])
+        inflow[b, flow] = prof
+    u0 = np.broadcast_to(inflow, (B, d) + shape).copy() + 0.05 * rng.standard_normal((B, d) + shape)
+    velm = np.zeros(d, dtype=np.float32)
+    velm[flow] = 1.0
+    return edges, inflow, u0, velm
+
+
+@functools.lru_cache(maxsize=None)
+def _outflow_oracle(geometry):
+    """The oracle's run of a geometry (the same for both drivers, computed once): the stepped domains of the envs."""
+    n, flow, n_steps = OUTFLOW_GEOMETRIES[geometry]
+    d = len(n)
+    edges, inflow, u0, velm = _outflow_inputs(geometry)
+    g = O.Grid(O.rectilinear_coords(edges))
+    doms = []
+    for b in range(inflow.shape[0]):
+        bc = {f: O.FixedBC(inflow[b].copy() if (f >> 1) == flow else np.zeros(d)) for f in range(2 * d)}
+        doms.append(O.Domain(g, 0.02, u0[b].astype(np.float32).astype(np.float64), np.zeros(g.shape), bc))
+    hooks = {"PRE": [lambda dm, ts: O.update_advective_boundaries(dm, [2 * flow + 1], velm.astype(np.float64), ts, tol=1e-5)]}
+    def run(dm):
+        for step in range(n_steps):
+            O.piso_adaptive_step(dm, 0.06, 0.5, prep_fn=hooks)
+
+    # (the envs side by side: the direct pressure solves of the 40 x 28 x 6 duct take seconds each and leave the interpreter lock)
+    with ThreadPoolExecutor(len(doms)) as pool:
+        list(pool.map(run, doms))
+    return doms
+
+
+# (the +x channel keeps the ids it had before the geometry parameter existed)
+@pytest.mark.parametrize("driver,geometry", [(dr, ge) for ge in OUTFLOW_GEOMETRIES for dr in ("native", "python_hooks")],
+                         ids=[dr + ("" if ge == "x" else "-" + ge) for ge in OUTFLOW_GEOMETRIES for dr in ("native", "python_hooks")])
+def test_channel_driver_with_outflow_matches_oracle(driver, geometry):
+    """Simulation.single_step (flux guard, adaptive CFL, native advective outflow + flux re-balancing, fused
+    PISO step) against the oracle's restatement of the same sequence, 6 steps (3 in 3-D), per-env different inflow."""
+    n, flow, n_steps = OUTFLOW_GEOMETRIES[geometry]
+    d = len(n)
+    nu, dt, B = 0.02, 0.06, 2
+    edges, inflow, u0, velm = _outflow_inputs(geometry)
+    names = ["-x", "+x", "-y", "+y", "-z", "+z"]
+    dom = Domain(d, torch.tensor([nu]), batch=B)
+    blk = dom.CreateBlock(grids.vertex_grid(edges))
+    for a in range(d):
+        blk.CloseBoundary(names[2 * a])
+    dom.PrepareSolve()
     blk.setVelocity(torch.from_numpy(u0).float())
-    blk.getBoundary("-x").setVelocity(torch.from_numpy(inflow).float())
-    out = blk.getBoundary("+x")
+    blk.getBoundary(names[2 * flow]).setVelocity(torch.from_numpy(inflow).float())
+    out = blk.getBoundary(names[2 * flow + 1])
     out.setVelocity(torch.from_numpy(inflow).float())
     dom.solver.reset_solver_state()
-    velm = np.array([1.0, 0.0], dtype=np.float32)
 
     def pre(domain, time_step, **kw):
         update_advective_boundaries(domain, [out], velm, time_step, tol=1e-5)
@@ -183,24 +239,17 @@ def test_channel_driver_with_outflow_matches_oracle(driver):
         sim = Simulation(dom, dt=dt, substeps="ADAPTIVE", adaptive_CFL=0.5, prep_fn={"PRE": [pre]}, pressure_tol=1e-7,
                          advection_tol=1e-7, pressure_return_best_result=True)
         assert not sim._native_ok()
-    g = O.Grid(O.rectilinear_coords(edges))
-    doms = []
-    for b in range(B):
-        bc = {0: O.FixedBC(inflow[b].copy()), 1: O.FixedBC(inflow[b].copy()), 2: O.FixedBC(np.zeros(2)), 3: O.FixedBC(np.zeros(2))}
-        doms.append(O.Domain(g, nu, u0[b].astype(np.float32).astype(np.float64), np.zeros((ny, nx)), bc))
-    hooks = {"PRE": [lambda d, ts: O.update_advective_boundaries(d, [1], velm.astype(np.float64), ts, tol=1e-5)]}
     n_sub = []
-    for step in range(6):
+    for step in range(n_steps):
         assert sim.single_step()
         n_sub.append(sim.substep_count)
-        for d in doms:
-            O.piso_adaptive_step(d, dt, 0.5, prep_fn=hooks)
     assert max(n_sub) >= 2, "the case should exercise adaptive substepping"
+    doms = _outflow_oracle(geometry)
     vel = dom.solver.velocity.cpu().numpy().astype(np.float64)
     bv = out.velocity.cpu().numpy().astype(np.float64)
     for b in range(B):
         assert rel_err(vel[b], doms[b].velocity) < 2e-4
-        assert rel_err(bv[b], np.asarray(doms[b].bvel(1))) < 2e-4
+        assert rel_err(bv[b], np.asarray(doms[b].bvel(2 * flow + 1))) < 2e-4
         assert abs(O.boundary_flux_balance(doms[b])) < 1e-6
     fb = dom.GetBoundaryFluxBalance().cpu().numpy()
     assert np.abs(fb).max() < 1e-5

@@ -13,7 +13,7 @@ import torch
 from fluidgym_amd import _lib as L
 from tests import flow_diag_ref as R
 from tests import helpers_mb as H
-from tests.helpers import make_case
+from tests.helpers import make_case, with_normal_flux
 
 pytestmark = pytest.mark.gpu
 
@@ -46,9 +46,14 @@ def _check_all_kinds(out, refs, d, eps, what):
 
 # ------------------------------------------------------------------------------------------------ single-block
 @functools.lru_cache(maxsize=None)
-def _single(idx):
+def _single(idx, normal_flux=False):
+    """``normal_flux``: a non-zero wall-normal wall value (the wall gradient du_n/dn is then not the gradient towards zero), set
+    BEFORE the rounding of ``exact_case`` so that the inputs stay exactly representable."""
     dims, n, fixed_axes = SINGLE[idx]
-    case = R.exact_case(make_case(dims=dims, n=n, fixed_axes=fixed_axes, B=2, seed=7, nu=0.02, vel_scale=0.6))
+    case = make_case(dims=dims, n=n, fixed_axes=fixed_axes, B=2, seed=7, nu=0.02, vel_scale=0.6)
+    if normal_flux:
+        case = with_normal_flux(case, 5)
+    case = R.exact_case(case)
     grid = case.grid()
     refs = [R.single_block_gradient(case.oracle_domain(b, grid)) for b in range(case.B)]
     u_max = max([np.abs(case.velocity).max()] + [np.abs(v).max() for v in case.bvel.values()])
@@ -61,10 +66,16 @@ def _single_state(ns):
     return [ns.velocity.clone(), ns.pressure.clone()] + [ns.bvel[f].clone() for f in sorted(ns.bvel)]
 
 
+# (the normal_flux=False legs keep the ids they had before the parameter existed; the periodic grid has no wall, so no True leg)
+SINGLE_LEGS = [(i, nf) for nf in (False, True) for i, s in enumerate(SINGLE) if s[2] or not nf]
+
+
 @pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "f64"])
-@pytest.mark.parametrize("idx", range(len(SINGLE)), ids=["x".join(map(str, s[1])) + "-fixed" + "".join(map(str, s[2])) for s in SINGLE])
-def test_single_block_kinds_against_the_oracle_gradient(idx, dtype):
-    case, grid, refs = _single(idx)
+@pytest.mark.parametrize("idx,normal_flux", SINGLE_LEGS,
+                         ids=["x".join(map(str, SINGLE[i][1])) + "-fixed" + "".join(map(str, SINGLE[i][2])) + ("-normal_flux" if nf else "")
+                              for i, nf in SINGLE_LEGS])
+def test_single_block_kinds_against_the_oracle_gradient(idx, normal_flux, dtype):
+    case, grid, refs = _single(idx, normal_flux)
     d, eps = case.dims, _eps(dtype)
     ns = case.native(dtype=dtype)
     ns.pressure.copy_(torch.randn(ns.pressure.shape, dtype=dtype, device=ns.device))

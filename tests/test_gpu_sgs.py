@@ -7,7 +7,7 @@ import pytest
 import torch
 
 from oracle import piso_oracle as O
-from tests.helpers import make_case, rel_err
+from tests.helpers import make_case, rel_err, with_normal_flux
 
 pytestmark = pytest.mark.gpu
 
@@ -16,10 +16,21 @@ def _np(t):
     return t.detach().cpu().numpy().astype(np.float64)
 
 
-@pytest.mark.parametrize("dims,n,fixed_axes", [(2, (16, 12), (1,)), (2, (12, 10), (0, 1)), (3, (8, 6, 5), (1,)), (3, (6, 5, 4), (0, 1, 2)),
-                                               (2, (12, 8), ())])
-def test_smagorinsky_viscosity_matches_the_oracle(dims, n, fixed_axes):
+SMAG_GRIDS = [(2, (16, 12), (1,)), (2, (12, 10), (0, 1)), (3, (8, 6, 5), (1,)), (3, (6, 5, 4), (0, 1, 2)), (2, (12, 8), ())]
+
+
+# (the ids of the normal_flux=False legs are the ones these cases had before the parameter existed;
+#  the periodic grid has no wall to blow through: it has no normal_flux=True leg)
+SMAG_LEGS = [(i, nf) for nf in (False, True) for i, c in enumerate(SMAG_GRIDS) if c[2] or not nf]
+
+
+@pytest.mark.parametrize("dims,n,fixed_axes,normal_flux", [SMAG_GRIDS[i] + (nf,) for i, nf in SMAG_LEGS],
+                         ids=[f"{SMAG_GRIDS[i][0]}-n{i}-fixed_axes{i}" + ("-normal_flux" if nf else "") for i, nf in SMAG_LEGS])
+def test_smagorinsky_viscosity_matches_the_oracle(dims, n, fixed_axes, normal_flux):
+    """``normal_flux``: a non-zero wall-normal wall value, so that du_n/dn at the wall is not the gradient towards zero."""
     case = make_case(dims=dims, n=n, fixed_axes=fixed_axes, B=2, seed=7, nu=0.02, vel_scale=0.6)
+    if normal_flux:
+        case = with_normal_flux(case, 5)
     ns = case.native()
     nu_t = _np(ns.sgs_smagorinsky(0.17))
     ns.close()

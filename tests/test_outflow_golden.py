@@ -10,7 +10,9 @@ import torch
 from oracle import piso_oracle as O
 
 G = np.load(os.path.join(os.path.dirname(__file__), "golden", "reference_outflow.npz"))
-CASES = ["c2d", "c2d_two_free", "c2d_scalar", "c3d"]
+CASES = ["c2d", "c2d_two_free", "c2d_scalar", "c3d",
+         # lower faces, y and z faces, a negative interpolation weight, a y pair with a scalar, five free faces
+         "c2d_lo_x", "c2d_lo_y", "c2d_neg", "c3d_lo_z", "c3d_hi_z", "c3d_y_scalar", "c3d_all_free_but_inflow"]
 
 
 def _case(name):
@@ -88,7 +90,54 @@ def test_hip_single_block_outflow_matches_the_reference(name):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", ["c2d", "c3d"])
+@pytest.mark.parametrize("name", ["c2d_two_free", "c3d_all_free_but_inflow"])
+def test_hip_single_block_outflow_with_env_dependent_data(name):
+    """k_outflow / k_balance_fluxes on a batch whose envs differ: the fixture's fields scaled per env, one time step per env, and an
+    inactive env (dt = 0) in the middle whose boundary arrays must not change by a bit.  Expected values: the oracle's update per env
+    in doubles (pinned by the fixture above)."""
+    from fluidgym_amd.simulation import grids
+    from fluidgym_amd.simulation.domain import Domain
+    from fluidgym_amd.simulation.simulation import update_advective_boundaries
+
+    c = _case(name)
+    d, B = c["d"], 3
+    scale = (1.0, 0.6, 1.7)
+    dts = (c["dt"], 0.0, 2 * c["dt"])
+    per_env = lambda a: np.stack([(np.float32(s) * a).astype(np.float32) for s in scale])
+    edges = [np.concatenate([[0.0], np.cumsum(w.astype(np.float64))]) for w in c["widths"]]
+    dom = Domain(d, torch.tensor([0.01]), batch=B)
+    blk = dom.CreateBlock(vertexCoordinates=grids.vertex_grid(edges))
+    for a in range(d):
+        blk.CloseBoundary(2 * a)
+    dom.PrepareSolve()
+    vel = per_env(c["velocity"])
+    bvel_in = {f: per_env(c["bvel_in"][f]) for f in range(2 * d)}
+    blk.setVelocity(torch.as_tensor(vel))
+    names = ["-x", "+x", "-y", "+y", "-z", "+z"]
+    for f in range(2 * d):
+        blk.getBoundary(names[f]).setVelocity(torch.as_tensor(bvel_in[f]))
+    before = {f: blk.getBoundary(names[f]).velocity.clone() for f in range(2 * d)}
+    bounds = [blk.getBoundary(names[f]) for f in c["free"]]
+    velms = [torch.as_tensor(v).reshape(1, d) for v in c["velm"]]
+    update_advective_boundaries(dom, bounds, velms if len(velms) > 1 else velms[0], dom.solver.dt_tensor(list(dts)), tol=c["tol"])
+    torch.cuda.synchronize()
+    got = {f: blk.getBoundary(names[f]).velocity.cpu().numpy() for f in range(2 * d)}
+    for f in range(2 * d):
+        assert torch.equal(blk.getBoundary(names[f]).velocity[1], before[f][1]), (name, f)      # the inactive env
+    dom.solver.close()
+    g = O.Grid(O.rectilinear_coords(edges))
+    velm = [v.astype(np.float64) for v in c["velm"]]
+    for e in (0, 2):
+        bc = {f: O.FixedBC(velocity=bvel_in[f][e].astype(np.float64)) for f in range(2 * d)}
+        ref = O.Domain(grid=g, viscosity=0.01, velocity=vel[e].astype(np.float64), pressure=np.zeros(g.shape), bc=bc)
+        O.update_advective_boundaries(ref, c["free"], velm if len(velm) > 1 else velm[0], dts[e], tol=c["tol"])
+        for f in range(2 * d):
+            assert _rel(got[f][e], ref.bvel(f)) < 5e-6, (name, e, f, _rel(got[f][e], ref.bvel(f)))
+            assert (f in c["free"]) != np.array_equal(got[f][e], bvel_in[f][e]), (name, e, f)      # free faces moved, the others did not
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["c2d", "c3d", "c2d_lo_x", "c2d_lo_y", "c3d_lo_z", "c3d_hi_z"])
 def test_hip_multi_block_outflow_matches_the_reference(name):
     """fg_mb_update_advective_boundary (csrc/fg_mb_step.hip: k_mb_outflow, k_mb_bflux, k_mb_balance) on the same block given as
     a one-block curvilinear mesh."""
