@@ -268,6 +268,7 @@ class FgMbSimOptions(Structure):
 (FG_MB_BUF_A, FG_MB_BUF_C_OFF, FG_MB_BUF_RHS, FG_MB_BUF_H, FG_MB_BUF_DIV, FG_MB_BUF_P_DIAG, FG_MB_BUF_P_OFF,
  FG_MB_BUF_VELOCITY_RESULT) = range(8)
 FG_MB_BUF_KRYLOV0 = 8
+FG_MB_BUF_PRESSURE_X = 13   # [B,N] the iterate of the last pressure solve as the solver left it
 
 
 class FgSimOptions(Structure):

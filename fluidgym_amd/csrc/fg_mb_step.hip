@@ -1543,6 +1543,7 @@ extern "C" int fg_mb_get_buffer(fg_mb_handle s, int32_t which, const mb_real** p
         case FG_MB_BUF_VELOCITY_RESULT: *ptr = s->ures; *count = B * d * N; break;
         case FG_MB_BUF_KRYLOV0: case FG_MB_BUF_KRYLOV0 + 1: case FG_MB_BUF_KRYLOV0 + 2: case FG_MB_BUF_KRYLOV0 + 3: case FG_MB_BUF_KRYLOV0 + 4:
             *ptr = s->w[which - FG_MB_BUF_KRYLOV0]; *count = B * d * N; break;
+        case FG_MB_BUF_PRESSURE_X: *ptr = s->pres; *count = B * N; break;
         default: fg_set_error("fg_mb_get_buffer: unknown buffer id"); return FG_ERR_INVALID_ARG;
     }
     return FG_OK;

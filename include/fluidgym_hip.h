@@ -1311,6 +1311,8 @@ int fg_mb_profile_iterations(fg_mb_handle h, int64_t* iterations);
 #define FG_MB_BUF_P_OFF 6
 #define FG_MB_BUF_VELOCITY_RESULT 7
 #define FG_MB_BUF_KRYLOV0 8          /* 8..12: the five Krylov work vectors [B,d,N] as the last solve left them (debugging) */
+#define FG_MB_BUF_PRESSURE_X 13     /* [B,N]   the iterate x of the last pressure solve as the solver left it (fg_mb_debug_pressure_cg:
+                                     * untouched; a PISO step's mean removal subtracts the mean in place before it copies to the bound pressure) */
 int fg_mb_get_buffer(fg_mb_handle h, int32_t which, const fg_real** ptr, int64_t* count);
 int fg_mb_read_buffer(fg_mb_handle h, int32_t which, fg_real* dst_device, void* stream); /* device copy, synchronises */
 

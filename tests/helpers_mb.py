@@ -158,6 +158,28 @@ def odd_channel():
     return split_rotated_channel(nx=11, ny=7, cut=4)
 
 
+def odd_channel_3d(nz=3):
+    """``odd_channel`` extruded over ``nz`` z-periodic layers (231 cells with three: not divisible by four, the one-cell-per-thread
+    kernels on a 3-D mesh), both blocks in the same orientation and joined +x -> -x; orthogonal, so CG is a valid pressure solver."""
+    nx, ny, cut = 11, 7, 4
+    x = np.linspace(0.0, 3.0, nx + 1) ** 1.15
+    t = np.linspace(-1.0, 1.0, ny + 1)
+    y = 0.5 * (np.tanh(1.3 * t) / np.tanh(1.3) + 1.0)
+    X, Y = np.meshgrid(x, y)
+    coords = np.stack([X, Y])
+    yc = 0.5 * (y[1:] + y[:-1])
+    z = np.linspace(0.0, 0.9, nz + 1)
+    inflow = np.zeros((3, nz, ny))
+    inflow[0] = 4.0 * yc[None, :] * (1.0 - yc[None, :])
+    inflow[2] = 0.1
+    s = Spec(3, 0.02)
+    s.blocks = [extrude(coords[:, :, :cut + 1].copy(), z), extrude(coords[:, :, cut:].copy(), z)]
+    s.fixed = [(0, 0, inflow.reshape(3, -1)), (1, 1, inflow.reshape(3, -1))]
+    s.periodic = [(0, 2), (1, 2)]
+    s.connections = [(0, 1, 1, 0, 2, 4)]
+    return s
+
+
 def cylinder_3d_small(res=4, res_z=3, nu=0.01):
     """The reference's 3-D cylinder mesh (extruded, z-periodic, connections carry two axes) at a small resolution, with
     perturbed Dirichlet values so that walls and inflow exercise every boundary branch."""

@@ -10,13 +10,17 @@ the shape of the source, not only its arithmetic.
 The on-chip and the cluster CG are switched off (FG_MB_ONCHIP=0, FG_MB_CLUSTER=0), so ``Domain.debug_pressure_cg`` lands in the chunked
 solver.  Compared per case and iteration cap: the five Krylov work arrays (FG_MB_BUF_KRYLOV0..4 = residual, the two direction
 buffers, A p, the kept iterate -- as SHA-256 digests of their bytes, the fixture has no room for the arrays), and the iterations /
-converged / residual words of every env.  The solver's own pressure array x is behind no buffer id (``Domain.pressure`` receives it
-only at the end of a PISO step); it is held through what is computed from it: the kept iterate is a copy of x (of the iteration that
-last halved the residual; what an unconverged solve hands back), and every restart of the recurrence (iteration 100, 200, ...)
-recomputes r = b - A x from x, so all work arrays of the caps 120 and 5000 depend on every bit of x up to their last restart.
-Not covered: the x updates of a converged solve behind its last kept iterate and last restart, W = 1 on a 3-D mesh (every 3-D mesh
-of the helpers has a cell count divisible by four and the fp32 library has no switch to force the one-cell kernels), and z of the
-preconditioned recurrence (no buffer id exposes it; r, p and A p depend on every bit of it)."""
+converged / residual words of every env.  That pins the trajectory, not that x solves the system: the solver's own pressure array x
+(FG_MB_BUF_PRESSURE_X) is read behind each of these solves by tests/test_gpu_mb_cg_solutions.py and held to the fp64 residual it
+leaves in the system, at every cap -- the kept iterate of the caps 20 and 40, the iterate behind the restart of cap 120, the
+converged one with its updates behind the last kept iterate and the last restart.  Here x is held through what is computed from it:
+the kept iterate is a copy of x (of the iteration that last halved the residual; what an unconverged solve hands back), and every
+restart of the recurrence (iteration 100, 200, ...) recomputes r = b - A x from x, so all work arrays of the caps 120 and 5000
+depend on every bit of x up to their last restart.  W = 1 on a 3-D mesh (no mesh of this fixture: every 3-D one has a cell count
+divisible by four) runs there as well, on ``helpers_mb.odd_channel_3d``, against its fp64 residual and the oracle.
+Not covered, here or there: the breakdown recovery (k_mbs_recover: no system of the fixture breaks down), the cluster CG's give-up
+path (a granule that hands the solve back to the one-workgroup kernels), and z of the preconditioned recurrence (no buffer id
+exposes it; r, p and A p depend on every bit of it)."""
 import ctypes
 import hashlib
 import os
@@ -64,14 +68,13 @@ def case_key(lib, mesh, pre, pm):
     return f"{lib}.{mesh}.pm{pm}"
 
 
-def solve_case(lib, mesh, pre, pm, diag, off, rhs, yp, tol):
-    """The pressure systems (diag [B][N], off [B][F][N], rhs [B][N]) by ``debug_pressure_cg`` on a fresh handle, once per entry of
-    CAPS: the digests of the work arrays and the outcome words of each.  SWITCHES must be in the environment."""
+def open_case(lib, mesh, pre, pm, diag, off, rhs, yp):
+    """A fresh handle with the pressure systems (diag [B][N], off [B][F][N], rhs [B][N]) uploaded into its pressure buffers, the
+    multilevel tables and the residual projection installed as the case asks.  SWITCHES must be in the environment."""
     from fluidgym_amd import _lib as L
 
     dtype = torch.float64 if lib == "f64" else torch.float32
     dom = MESHES[mesh]().native(batch=B, dtype=dtype)
-    N = dom.n_cells
     if pre:   # (before the matrix goes in: the tables are built from the unit pressure matrix, through the same buffers)
         assert dom.set_pressure_multilevel(fp64=(lib == "f64")) is not None
     if pm == 2:
@@ -85,6 +88,16 @@ def solve_case(lib, mesh, pre, pm, diag, off, rhs, yp, tol):
         assert t.numel() == cnt.value
         assert hip.hipMemcpy(ptr, ctypes.c_void_p(t.data_ptr()), ctypes.c_size_t(t.element_size() * t.numel()), 3) == 0
     torch.cuda.synchronize()
+    return dom
+
+
+def solve_case(lib, mesh, pre, pm, diag, off, rhs, yp, tol):
+    """The pressure systems by ``debug_pressure_cg`` on a fresh handle (``open_case``), once per entry of CAPS: the digests of the work
+    arrays and the outcome words of each."""
+    from fluidgym_amd import _lib as L
+
+    dom = open_case(lib, mesh, pre, pm, diag, off, rhs, yp)
+    N = dom.n_cells
     res = []
     for cap in CAPS:
         info = dom.debug_pressure_cg(tol, cap, project_mean=(pm != 0))

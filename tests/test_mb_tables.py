@@ -82,7 +82,8 @@ class HostTables:
         self.lib.fg_mb_destroy(self.h)
 
 
-SPECS = [H.split_rotated_channel, H.skewed_pair, H.twisted_ring, H.skewed_pair_3d, _cylinder_spec, H.cylinder_3d_small, H.airfoil_spec]
+SPECS = [H.split_rotated_channel, H.skewed_pair, H.twisted_ring, H.skewed_pair_3d, H.odd_channel_3d, _cylinder_spec, H.cylinder_3d_small,
+         H.airfoil_spec]
 
 
 def test_tables_of_the_reference_airfoil_mesh_reproduce_the_oracle():
@@ -179,4 +180,24 @@ def test_host_only_handle_refuses_compute():
     rc = t.lib.fg_mb_bind(t.h, None, None, None, None)
     assert rc < 0
     assert t.lib.fg_mb_unit_pressure_matrix(t.h, None) < 0
+    t.close()
+
+
+def test_pressure_iterate_buffer_id_matches_the_header_and_needs_a_device():
+    """FG_MB_BUF_PRESSURE_X (the iterate of the last pressure solve): the Python constant is the header's, behind the Krylov work
+    vectors, and a host-only handle refuses it like every other buffer id."""
+    import os
+    import re
+
+    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "fluidgym_hip.h")).read()
+    ids = {k: int(v) for k, v in re.findall(r"#define (FG_MB_BUF_[A-Z0-9_]+) (\d+)", header)}
+    assert ids["FG_MB_BUF_PRESSURE_X"] == L.FG_MB_BUF_PRESSURE_X == 13 == ids["FG_MB_BUF_KRYLOV0"] + 5
+    for name, v in ids.items():
+        assert getattr(L, name) == v, name
+    assert len(set(ids.values())) == len(ids)
+    t = HostTables(H.split_rotated_channel())
+    ptr, cnt = ctypes.c_void_p(), ctypes.c_int64()
+    for which in (L.FG_MB_BUF_DIV, L.FG_MB_BUF_KRYLOV0, L.FG_MB_BUF_PRESSURE_X):
+        assert t.lib.fg_mb_get_buffer(t.h, which, ctypes.byref(ptr), ctypes.byref(cnt)) == L.FG_ERR_UNSUPPORTED, which
+        assert t.lib.fg_mb_read_buffer(t.h, which, None, None) == L.FG_ERR_UNSUPPORTED, which
     t.close()
