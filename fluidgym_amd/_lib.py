@@ -105,6 +105,22 @@ class FgMbResetNoise(Structure):
     ]
 
 
+class FgMbInflowParams(Structure):
+    """One ``fg_mb_inflow_disturbance`` launch (``fg_mb_inflow_params``): slot ranges, mode counts, counters' scaling, the random
+    form's seed and band, and five device pointers (``modes`` NULL: the random form).  The same layout in both libraries."""
+    _fields_ = [
+        ("slot0", c_int32), ("count", c_int32),
+        ("outflow_slot0", c_int32), ("outflow_count", c_int32), ("outflow_slot0_b", c_int32), ("outflow_count_b", c_int32),
+        ("n_streamwise", c_int32), ("n_transverse", c_int32),
+        ("sim_steps", c_int32), ("k", c_int32),
+        ("env_offset", c_int32), ("reserved", c_int32),
+        ("seed", ctypes.c_uint64),
+        ("dt", ctypes.c_double), ("f_lo", ctypes.c_double), ("f_hi", ctypes.c_double), ("streamwise_rms", ctypes.c_double),
+        ("transverse_rms", ctypes.c_double), ("kappa", ctypes.c_double), ("y_mid", ctypes.c_double), ("outflow_tol", ctypes.c_double),
+        ("base", c_void_p), ("y", c_void_p), ("modes", c_void_p), ("counters", c_void_p), ("signal", c_void_p),
+    ]
+
+
 class FgFrameSpec(Structure):
     """Which plane of a field ``fg_frame_colorize`` draws, and how it is oriented (``fg_frame_spec``)."""
     _fields_ = [
@@ -329,6 +345,7 @@ SIGNATURES = {
     "fg_mb_env_reset_solver_state": (c_int, [c_void_p, POINTER(FgEnvSel), c_int32, c_void_p]),
     "fg_mb_restore_envs": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, POINTER(FgEnvSel), c_int32, POINTER(FgMbResetNoise),
                                    c_void_p]),
+    "fg_mb_inflow_disturbance": (c_int, [c_void_p, POINTER(FgMbInflowParams), c_void_p]),
     "fg_set_pressure_refinement": (c_int, [c_void_p, c_int32, c_float, c_float]),
     "fg_get_buffer": (c_int, [c_void_p, c_int, POINTER(c_void_p), POINTER(c_int64)]),
     "fg_read_buffer": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),

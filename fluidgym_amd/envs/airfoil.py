@@ -319,11 +319,12 @@ class AirfoilEnvBase(CylinderEnvBase):
     def _step_impl(self, action: torch.Tensor):
         target = action.reshape(self._num_envs, self._n_controls)
         cds, cls = [], []
-        for _ in range(self._n_sim_steps):
+        for k in range(self._n_sim_steps):
             control = self._last_control + self._action_smoothing_alpha * (target - self._last_control)
             self._last_control = control
             if self._enable_actions:
                 self._apply_action(control)
+            self._before_sim_step(k)
             self._sim.single_step()
             self._after_sim_step()
             cd, cl = self._get_drag_and_lift()

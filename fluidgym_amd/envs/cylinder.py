@@ -28,6 +28,7 @@ from .. import spaces
 from .channel import jet_profile
 from .cylinder_grid import BOTTOM, LEFT, RIGHT, TOP, build_domain, extrude_mesh, make_vortex_street_mesh
 from .flow_statistics import FieldStatisticsMixin, FlowStatisticsMixin
+from .inflow import InflowDisturbanceMixin
 from .fluid_env import FluidEnv, is_per_env, per_env_parameter, refuse_per_env
 from .forces import WallRing
 from .mesh_reset import MeshResetMixin
@@ -48,7 +49,7 @@ ONCHIP_PCG_MAX_CELLS = 24 * 1024   # the multilevel-preconditioned on-chip CG (2
 VORTICITY_RENDER_LEVELS = {100: 1.5, 250: 2.5, 500: 3.5}   # jet_cylinder_env_3d.py:15-19: level of the 3-D picture, by Reynolds number
 
 
-class CylinderEnvBase(SurfaceMixin, MeshResetMixin, MeshTracerMixin, FieldStatisticsMixin, FlowStatisticsMixin, FluidEnv):      # (multi-block: the plane statistics refuse with
+class CylinderEnvBase(InflowDisturbanceMixin, SurfaceMixin, MeshResetMixin, MeshTracerMixin, FieldStatisticsMixin, FlowStatisticsMixin, FluidEnv):      # (multi-block: the plane statistics refuse with
                                                                                  # NotImplementedError, the per-cell ones record)
     _supports_marl = False
     _action_smoothing_alpha: float = 0.1
@@ -342,6 +343,7 @@ class CylinderEnvBase(SurfaceMixin, MeshResetMixin, MeshTracerMixin, FieldStatis
             self._last_control = controls[k]
             if self._enable_actions:
                 self._apply_action(controls[k])
+            self._before_sim_step(k)
             self._sim.single_step()
             self._after_sim_step()
             self._ring.forces(self._domain, self._nu_forces, layer_height=self.D / self._circle_resolution_angular, out=raw[k])
@@ -394,12 +396,14 @@ class CylinderEnvBase(SurfaceMixin, MeshResetMixin, MeshTracerMixin, FieldStatis
         self._domain.Restore(snap)
 
     def _get_extra_state(self):
-        return {"last_control": self._last_control.clone(), "mesh_reset_count": self.mesh_reset_count.copy()}
+        return {"last_control": self._last_control.clone(), "mesh_reset_count": self.mesh_reset_count.copy(),
+                "inflow_disturbance": self._inflow_state_dict()}
 
     def _set_extra_state(self, extra) -> None:
         if extra is not None:
             self._last_control = extra["last_control"].clone()
         self.mesh_reset_count[:] = (extra or {}).get("mesh_reset_count", 0)      # a state from before the counter loads zeros
+        self._load_inflow_state((extra or {}).get("inflow_disturbance"))
 
     def render(self, *a, **kw) -> np.ndarray:
         speed = torch.linalg.vector_norm(self.get_velocity()[0], dim=0)

@@ -100,6 +100,7 @@ class CylinderMesh:
     cylinder_faces: List[Tuple[int, str]] = field(default_factory=lambda: [(LEFT, "+x"), (TOP, "-y"), (RIGHT, "-x"), (BOTTOM, "+y")])
     dims: int = 2
     periodic: List[Tuple[int, str]] = field(default_factory=list)
+    inflow: Tuple[int, str] = (LEFT, "-x")         # block 0 is the inflow block of the cylinder and of the airfoil mesh
 
 
 def make_vortex_street_mesh(resolution: int, domain_height: float = 4.1, domain_length: float = 22.0,
@@ -184,7 +185,7 @@ def extrude_mesh(mesh: CylinderMesh, res_z: int, z0: float = -2.0, z1: float = 2
         # 2-D: the one remaining axis; 3-D: the axes after the face axis in cyclic order -- z first if the face is a y face
         conns.append((b1, f1, b2, f2, "-z", ax) if f1[1] == "y" else (b1, f1, b2, f2, ax, "-z"))
     out = CylinderMesh(coords, list(mesh.names), fixed, conns, mesh.outflow, list(mesh.cylinder_faces), dims=3,
-                       periodic=[(b, "z") for b in range(len(coords))])
+                       periodic=[(b, "z") for b in range(len(coords))], inflow=mesh.inflow)
     if hasattr(mesh, "outflows"):
         out.outflows = list(mesh.outflows)
     return out

@@ -646,6 +646,15 @@ class ParallelFluidEnv:
     def reset_mesh_envs(self, envs, randomize: Optional[bool] = None):
         raise NotImplementedError("reset_mesh_envs is not implemented for ParallelFluidEnv.")
 
+    def start_inflow_disturbance(self, spec=None, **random_kwargs):
+        raise NotImplementedError("start_inflow_disturbance is not implemented for ParallelFluidEnv.")
+
+    def stop_inflow_disturbance(self) -> None:
+        raise NotImplementedError("stop_inflow_disturbance is not implemented for ParallelFluidEnv.")
+
+    def inflow_signal(self):
+        raise NotImplementedError("inflow_signal is not implemented for ParallelFluidEnv.")
+
     def set_mesh_state_bank(self, states, env: Optional[int] = None) -> None:
         raise NotImplementedError("set_mesh_state_bank is not implemented for ParallelFluidEnv.")
 

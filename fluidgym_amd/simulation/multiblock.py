@@ -742,6 +742,69 @@ class MultiBlockDomain:
                                             None if rec is None else ctypes.byref(rec), ctypes.c_void_p(st)), lib=self.lib)
         return sel
 
+    def face_centres(self, face_spec) -> np.ndarray:
+        """Centres ``[d, face cells]`` (doubles) of the cells of one face ``(block, face)``, in the order of the face's boundary slots
+        (lowest remaining axis fastest)."""
+        blk, face = face_spec
+        blk = blk if isinstance(blk, MBBlock) else self.blocks[blk]
+        f = face_index(face)
+        c = np.asarray(blk.coords, dtype=np.float64)
+        ax = c.ndim - 1 - (f >> 1)
+        out = np.take(c, c.shape[ax] - 1 if f & 1 else 0, axis=ax)          # the face's vertices [d, remaining axes]
+        for a in range(1, out.ndim):
+            n = out.shape[a] - 1
+            out = 0.5 * (np.take(out, range(0, n), axis=a) + np.take(out, range(1, n + 1), axis=a))
+        return np.ascontiguousarray(out.reshape(c.shape[0], -1))
+
+    def ApplyInflowDisturbance(self, inflow, outflow, base: torch.Tensor, spec, sim_steps: int, k: int, counters: torch.Tensor,
+                               dt: float, outflow_tol: float = 5e-6, signal: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Rewrite the values of the FIXED face ``inflow`` = (block, face) of every env from ``base`` (a tensor in the layout of
+        ``boundary_velocity``) and the gusts of ``spec`` (an ``InflowDisturbance``; None: zero amplitude, the base profile itself) at
+        env b's time ``(counters[b, 0] * sim_steps + k) * dt``, then scale the ``outflow`` face(s) of every env so that its boundary
+        fluxes balance (``fg_mb_inflow_disturbance``: one launch, nothing read back).  ``counters``: device int32 ``[B, 2]`` = (env
+        steps of the episode, episode).  The transverse gust varies along y, the face centres of ``inflow``.  Returns ``signal``
+        ``[B, 2]`` fp32 = (S_b, G_b at mid-height)."""
+        if not self.prepared:
+            raise RuntimeError("ApplyInflowDisturbance: PrepareSolve() first")
+        slot0, count = self._outflow_slots(inflow)
+        (o0, on), (o1, on1) = self._outflow_ranges(outflow)
+        if tuple(base.shape) != tuple(self.boundary_velocity.shape) or base.dtype != self.boundary_velocity.dtype or \
+                base.device != self.boundary_velocity.device or not base.is_contiguous():
+            raise ValueError("ApplyInflowDisturbance: base must be a contiguous tensor in the layout, dtype and device of boundary_velocity")
+        if tuple(counters.shape) != (self.batch, 2) or counters.dtype != torch.int32 or counters.device != base.device or \
+                not counters.is_contiguous():
+            raise ValueError(f"ApplyInflowDisturbance: counters must be a contiguous int32 [{self.batch}, 2] tensor on the domain's device")
+        cache = self.__dict__.setdefault("_inflow_tables", {})
+        key = (slot0, count)
+        if key not in cache:                                                  # the y table: once per face
+            y = self.face_centres(inflow)[1]
+            cache[key] = (torch.as_tensor(y, dtype=torch.float64).to(base.device), 0.5 * (float(y.min()) + float(y.max())))
+        y_dev, y_mid = cache[key]
+        if signal is None:
+            signal = torch.empty(self.batch, 2, dtype=torch.float32, device=base.device)
+        p = L.FgMbInflowParams()
+        p.slot0, p.count = slot0, count
+        p.outflow_slot0, p.outflow_count, p.outflow_slot0_b, p.outflow_count_b = o0, on, o1, on1
+        p.sim_steps, p.k = int(sim_steps), int(k)
+        p.dt, p.y_mid, p.outflow_tol = float(dt), y_mid, float(outflow_tol)
+        modes = None
+        if spec is not None:
+            p.n_streamwise, p.n_transverse, p.kappa = spec.n_streamwise, spec.n_transverse, spec.kappa
+            if spec.form == "random":
+                p.seed, p.env_offset = spec.seed, spec.env_offset
+                p.f_lo, p.f_hi = spec.band
+                p.streamwise_rms, p.transverse_rms = spec.streamwise_rms, spec.transverse_rms
+            else:
+                mkey = (str(base.device), self.batch)
+                if mkey not in spec._device_modes:                            # the mode table: once per spec
+                    spec._device_modes[mkey] = torch.as_tensor(spec.modes_table(self.batch)).to(base.device)
+                modes = spec._device_modes[mkey]
+        p.base, p.y, p.counters, p.signal = base.data_ptr(), y_dev.data_ptr(), counters.data_ptr(), signal.data_ptr()
+        p.modes = modes.data_ptr() if modes is not None else None
+        st = torch.cuda.current_stream(self.device).cuda_stream
+        L.check(self.lib.fg_mb_inflow_disturbance(self.handle, ctypes.byref(p), ctypes.c_void_p(st)), lib=self.lib)
+        return signal
+
     @property
     def solver(self):
         return self

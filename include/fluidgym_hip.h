@@ -1174,6 +1174,41 @@ typedef struct fg_mb_reset_noise {
 int fg_mb_restore_envs(fg_mb_handle h, const fg_real* bank_velocity /*[S][d][N]*/, const fg_real* bank_pressure /*[S][N]*/,
                        const fg_real* bank_boundary /*[S][d][NB], may be NULL when NB == 0*/, int32_t S, const fg_env_sel* sel,
                        int32_t n_sel, const fg_mb_reset_noise* noise /*NULL: pure copy*/, void* stream);
+/* ---- per-env unsteady inflow of a multi-block handle: gusts (csrc/fg_mb_inflow.hip) ----
+ * ONE launch, one workgroup per env: the inflow slots [slot0, slot0 + count) of every env b are rewritten from a base profile (an
+ * array in the layout of the boundary velocity, [B][d][NB]) and that env's gust signals at t = n dt, n = counters[b][0] * sim_steps
+ * + k:
+ *     ub[b][0][s] = base[b][0][s] * (1 + S_b),   ub[b][1][s] = base[b][1][s] + base[b][0][s] * G_b(y[s]),   ub[b][c >= 2][s] = base
+ *     S_b = sum_k a_k sin 2 pi (f_k t + phi_k),   G_b(y) = sum_k g_k sin 2 pi (h_k t + psi_k - kappa y)
+ * then the signed boundary fluxes of the env are summed over all NB slots and, where their sum exceeds 0.01 outflow_tol, the up to
+ * two outflow ranges are scaled by -fixed / free (the balance rule of the step's PRE hook; its advective update is not run).  The
+ * phases in double, the signals in fp32 by a rule of separately rounded operations written at the top of the source file and
+ * restated in tests/inflow_disturbance_ref.py.  signal[b] = (S_b, G_b(y_mid)).
+ * modes: a device table [B][6][8] of doubles, rows a, f, phi, g, h, psi (n_streamwise / n_transverse of the 8 columns are read), or
+ * NULL: the random form, whose modes are a pure function of (seed, env_offset + b, counters[b][1]) -- Philox4x32-10 with key
+ * (seed low, seed high) and counter ((240 << 24) | k, env_offset + b, counters[b][1], 0); f_k and h_k fall into the k-th of
+ * n_streamwise / n_transverse equal parts of [f_lo, f_hi], every a_k = streamwise_rms sqrt(2 / n_streamwise), every g_k =
+ * transverse_rms sqrt(2 / n_transverse).  n_streamwise = n_transverse = 0 writes the base profile back and rebalances.
+ * Every pointer of the struct is a DEVICE pointer; nothing is read back; asynchronous on `stream`.  Every check comes before the
+ * launch: FG_ERR_INVALID_ARG for a null handle, struct or pointer (modes may be NULL), a mode count outside 0..8, count <= 0, slots
+ * out of range or overlapping, outflow_count <= 0, a dt that is negative or not finite, sim_steps < 1, k outside [0, sim_steps), a
+ * non-finite kappa, y_mid or outflow_tol and, in the random form, a band that is not 0 <= f_lo <= f_hi < inf or an rms that is
+ * negative or not finite; FG_ERR_NOT_BOUND for a handle that is not finalised or has no bound fields. */
+typedef struct fg_mb_inflow_params {
+    int32_t slot0, count;                                                    /* the inflow slots */
+    int32_t outflow_slot0, outflow_count, outflow_slot0_b, outflow_count_b;  /* the outflow ranges (the second may be empty) */
+    int32_t n_streamwise, n_transverse;                                      /* K_s, K_t in 0..8 */
+    int32_t sim_steps, k;                                                    /* sim steps per env step, index of this one */
+    int32_t env_offset, reserved;
+    uint64_t seed;
+    double dt, f_lo, f_hi, streamwise_rms, transverse_rms, kappa, y_mid, outflow_tol;
+    const void* base;          /* [B][d][NB] of fg_real */
+    const double* y;           /* [count] face centres */
+    const double* modes;       /* [B][6][8] or NULL */
+    const uint32_t* counters;  /* [B][2] = (env steps of the episode, episode) */
+    float* signal;             /* [B][2] */
+} fg_mb_inflow_params;
+int fg_mb_inflow_disturbance(fg_mb_handle h, const fg_mb_inflow_params* params, void* stream);
 /* as fg_solver_counters, for the multi-block path */
 int fg_mb_solver_counters(fg_mb_handle h, int64_t* out13_host, int32_t reset);
 /* The tuning / diagnosis switches a handle runs under (the FG_* environment variables read ONCE at create time, docs/SWITCHES.md,
