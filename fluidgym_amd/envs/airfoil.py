@@ -19,7 +19,7 @@ Batched over ``num_envs`` like every env here.  Not carried over: the published 
 """
 from __future__ import annotations
 
-from typing import Dict, Optional
+from typing import Optional
 
 import numpy as np
 import torch
@@ -27,13 +27,11 @@ import torch
 from .. import spaces
 from ..simulation.multiblock import MultiBlockSimulation
 from ..simulation.policy import get_solver_policy
-from ..simulation.resample_mb import MultiBlockResampler, MultiBlockResampler3D
 from .airfoil_grid import BOTTOM, FRONT, TAIL_LOWER, TAIL_UPPER, TOP, make_airfoil_mesh, naca0012_sharp
 from .channel import jet_profile
-from .cylinder import CylinderEnvBase
 from .cylinder_grid import build_domain, extrude_mesh
-from .fluid_env import FluidEnv, refuse_per_env
-from .forces import WallRing
+from .fluid_env import refuse_per_env
+from .mesh_body import MeshBodyEnvBase, SpanwiseAgentsMixin
 
 AIRFOIL_2D_DEFAULT_CONFIG = {
     "reynolds_number": 3e3, "dt": 0.05, "step_length": 0.25, "adaptive_cfl": 0.8, "episode_length": 300,
@@ -70,29 +68,25 @@ def jet_locations(top_coords: np.ndarray):
             for c in JET_CENTERS]
 
 
-class AirfoilEnvBase(CylinderEnvBase):
-    _supports_marl = False
-    _action_smoothing_alpha: float = 0.1
+class AirfoilEnvBase(MeshBodyEnvBase):
     _n_jets: int = 3
+    _n_controls = _n_jets
     U_mean: float = 0.3
+    _U_mean = U_mean
     airfoil_length: float = 1.0
     H: float = 1.4
     L: float = 4.5
     D: float = 1.4
-    _metrics = ["drag", "lift"]
-    _initial_domain_steps = 400
     _wall_family = "airfoil"            # the surface curves carry x / c and the side (envs/surface.py)
+    _mesh_reset_sigma = 0.01     # the noise of _randomize_domain, as reset_mesh_envs adds it per env
+    _fill_max_steps = 128
+    _domain_file_name = "AirfoilDomain"
 
     def __init__(self, ndims: int, reynolds_number: float, adaptive_cfl: float, step_length: float, episode_length: int,
-                 dt: float, attack_angle_deg: float, initial_domain_steps: Optional[int] = None,
-                 lift_drag_reference: float = 0.0, resolution_div: int = 1, surface: Optional[np.ndarray] = None,
-                 pressure_use_BiCG=2, non_ortho_mode: str = "matrix", stall_limit: int = 400,
-                 pressure_deflation: bool = False, debug: bool = False, **kw):
+                 dt: float, attack_angle_deg: float, lift_drag_reference: float = 0.0, resolution_div: int = 1,
+                 surface: Optional[np.ndarray] = None, pressure_use_BiCG=2, stall_limit: int = 400, **kw):
         if attack_angle_deg < 0.0 or attack_angle_deg > 20.0:
             raise ValueError("Attack angle must be between 0 and 20 degrees.")
-        if ndims not in (2, 3):
-            raise ValueError("ndims must be 2 or 3")
-        self._ndims = ndims
         refuse_per_env("reynolds_number", reynolds_number, "the airfoil env", "its mesh grading depends on the Reynolds number")
         self._reynolds_number = reynolds_number
         self._nu = self.U_mean * self.airfoil_length / reynolds_number
@@ -100,24 +94,13 @@ class AirfoilEnvBase(CylinderEnvBase):
         self._resolution_div = int(resolution_div)
         self._surface = np.asarray(naca0012_sharp() if surface is None else surface, np.float64)
         self._lift_drag_reference = float(lift_drag_reference)
-        self._pressure_use_bicg = pressure_use_BiCG
-        self._pressure_deflation = bool(pressure_deflation)
-        if non_ortho_mode not in ("matrix", "rhs"):
-            raise ValueError("non_ortho_mode: 'matrix' (the reference's nonOrthoFlags) or 'rhs' (every cross-metric term lagged)")
-        self._non_ortho_flags = 25 if non_ortho_mode == "matrix" else 10
         self._stall_limit = int(stall_limit)
-        self._U_mean = self.U_mean
-        self._n_controls = self._n_jets
-        if initial_domain_steps is not None:
-            self._initial_domain_steps = int(initial_domain_steps)
         a = -self._attack_angle_deg * np.pi / 180.0
         rot = np.array([[np.cos(a), -np.sin(a)], [np.sin(a), np.cos(a)]])
         self._airfoil_coords = (self._surface @ rot.T).T.astype(np.float32)          # [2, n] as read_airfoil returns it
-        self._airfoil_mask = self._get_airfoil_mask()
-        self._sensor_locations = self._get_sensor_locations()
-        FluidEnv.__init__(self, dt=dt, adaptive_cfl=adaptive_cfl, step_length=step_length, episode_length=episode_length,
-                          ndims=ndims, **kw)
-        self._last_control = None
+        self._airfoil_mask = self._get_airfoil_mask()      # (the sensors inside it are dropped: before the base counts them)
+        super().__init__(ndims=ndims, pressure_use_BiCG=pressure_use_BiCG, dt=dt, adaptive_cfl=adaptive_cfl, step_length=step_length,
+                         episode_length=episode_length, **kw)
 
     @property
     def _cl_cd_ref(self) -> float:
@@ -175,13 +158,6 @@ class AirfoilEnvBase(CylinderEnvBase):
     def _get_action_space(self):
         return spaces.Box(low=-1.0, high=1.0, shape=(self._n_jets,), dtype=np.float32)
 
-    def _get_observation_space(self):
-        n = self._sensor_locations.shape[-1]
-        return spaces.Dict({
-            "velocity": spaces.Box(low=-np.inf, high=np.inf, shape=(n, self._ndims), dtype=np.float32),
-            "pressure": spaces.Box(low=-np.inf, high=np.inf, shape=(n,), dtype=np.float32),
-        })
-
     # ---- domain and simulation (airfoil_env_base.py:216-311)
     def _get_domain(self):
         grow = 1.001 if (self._ndims == 3 and self._reynolds_number >= 5000) else 1.01      # airfoil_env_base.py:217-220
@@ -194,17 +170,6 @@ class AirfoilEnvBase(CylinderEnvBase):
         # the pressure system of this mesh has a residual floor (2-4e-5) far above the reference's tolerance (1e-7): every
         # solve ends on its best iterate after ``stall_limit`` iterations without improvement ("Airfoil")
         dom.set_stall_limit(self._stall_limit)
-        # 2-D: the multilevel preconditioner as a TRIAL of the pressure BiCGStab (solver policy; geometry-only tables, built once):
-        # attempts are capped and verified on the true residual, one that fails is repeated with the plain recurrence and makes
-        # the domain back off exponentially (3x fewer pressure iterations; the stiff start-up solves are the ones that fail)
-        # policy pressure_multilevel_bicgstab (default on since the reductions are order-independent: policy.py)
-        # (a float64 env: only with policy pressure_multilevel_fp64, then with the unfused apply of the fp64 build)
-        self._multilevel = None
-        if self._ndims == 2 and get_solver_policy()["pressure_multilevel_bicgstab"]:
-            if self._dtype == torch.float64 and get_solver_policy()["pressure_multilevel_fp64"]:
-                self._multilevel = dom.set_pressure_multilevel(fp64=True)
-            else:
-                self._multilevel = dom.set_pressure_multilevel()
         return dom
 
     def _get_simulation(self, domain, prep_fn):
@@ -214,18 +179,20 @@ class AirfoilEnvBase(CylinderEnvBase):
                                     outflow=list(self._mesh.outflows), outflow_velocity=(self.U_mean, 0.0, 0.0),
                                     solver_double_fallback=True, BiCG_precondition_fallback=True)   # airfoil_env_base.py:283-285
 
+    def _wall_ring_segments(self) -> list:
+        return [(FRONT, "+x", False), (TOP, "-y", False), (BOTTOM, "+y", True)]
+
+    def _use_pressure_multilevel(self) -> bool:
+        """2-D: the multilevel preconditioner as a TRIAL of the pressure BiCGStab (solver policy pressure_multilevel_bicgstab, default
+        on; geometry-only tables, built once): attempts are capped and verified on the true residual, one that fails is repeated
+        with the plain recurrence and makes the domain back off exponentially (3x fewer pressure iterations; the stiff start-up
+        solves are the ones that fail)."""
+        return self._ndims == 2 and bool(get_solver_policy()["pressure_multilevel_bicgstab"])
+
     def _additional_initialization(self) -> None:
+        super()._additional_initialization()
         dom = self._domain
-        self._ring = WallRing(dom, [(FRONT, "+x", False), (TOP, "-y", False), (BOTTOM, "+y", True)])
-        if self._ndims == 3:
-            self._resampler = MultiBlockResampler3D(self._mesh.coords, self.render_shape, fill_max_steps=128, device=dom.device)
-            self._sensors = self._resampler.sensor_gather(self._sensor_locations.reshape(3, -1).T)
-        else:
-            self._resampler = MultiBlockResampler(self._mesh.coords, self.render_shape[:2], fill_max_steps=128, device=dom.device)
-            self._sensors = self._resampler.sensor_gather(self._sensor_locations.T)
-        self._deflation_cos = dom.set_pressure_deflation() if self._pressure_deflation else 1.0
-        self._initial_boundary = dom.boundary_velocity.clone()
-        self._last_control = torch.zeros(self._num_envs, self._n_controls, device=dom.device, dtype=self._dtype)
+        self._solid_mask = torch.as_tensor(self._airfoil_mask, device=dom.device)
         self._jet_locations_top = self._get_jet_locations()
         self._top_base_profile = torch.as_tensor(self._get_base_jet_profiles(), device=dom.device).to(self._dtype)      # [2, nx_top]
         # outward flux of every boundary slot per unit velocity component: s_f det Minv[axis, :]
@@ -259,45 +226,20 @@ class AirfoilEnvBase(CylinderEnvBase):
             out[:, i0:i1 + 1] = prof[None, :] * normals[:, n_front + i0:n_front + i1 + 1]
         return out
 
-    def _fill_initial_fields(self) -> None:
-        self._developed = getattr(self, "_developed", None)
-        dom = self._domain
-        if self._developed is None:
-            dom.boundary_velocity.copy_(self._initial_boundary)
-            dom.velocity.zero_()
-            dom.velocity[:, 0] = self.U_mean
-            dom.pressure.zero_()
-            self._sim.make_divergence_free()
-            for _ in range(self._initial_domain_steps):
-                self._sim.single_step()
-            self._developed = dom.Clone()
-        dom.Restore(self._developed)
-        self._last_control = torch.zeros(self._num_envs, self._n_controls, device=dom.device, dtype=self._dtype)
-
-    def _randomize_domain(self) -> None:
-        """airfoil_env_base.py:327-332."""
-        max_n = int(0.05 * self._episode_length)
-        n_steps = int(self._np_rng.integers(int(0.5 * max_n), max_n)) + 1
-        dom, g = self._domain, self._torch_rng_cuda
-        dom.velocity.add_(torch.randn(dom.velocity.shape, device=dom.device, generator=g) * 0.01)
-        dom.pressure.add_(torch.randn(dom.pressure.shape, device=dom.device, generator=g) * 0.01)
-        for _ in range(n_steps):
-            self._sim.single_step()
-
-    _mesh_reset_sigma = 0.01     # the noise of _randomize_domain, as reset_mesh_envs adds it per env
-
     def _mesh_reset_warmup_env_steps(self) -> int:
-        return int(0.05 * self._episode_length)
+        return int(0.05 * self._episode_length)      # airfoil_env_base.py:327-332
 
-    # ---- forces, actuation, step
-    def _get_drag_and_lift(self):
-        """[B] in 2-D; [B, NZ] per spanwise layer in 3-D (face area = edge length x D / res_z, :448-449)."""
-        f = self._ring.forces(self._domain, self._nu, layer_height=self.D / getattr(self, "_res_z", 1))
-        norm = 0.5 * self.U_mean ** 2 * self.airfoil_length
-        return f[:, 0] / norm, f[:, 1] / norm
+    # ---- forces, actuation, reward
+    @property
+    def _force_norm(self) -> float:
+        return 0.5 * self.U_mean ** 2 * self.airfoil_length
 
-    def _wall_force_args(self):
-        return self._nu, self.D / getattr(self, "_res_z", 1)
+    @property
+    def _layer_height(self) -> float:
+        return self.D / self._res_z if self._ndims == 3 else 1.0      # face area = edge length x D / res_z (:448-449)
+
+    def _reward(self, cd: torch.Tensor, cl: torch.Tensor) -> torch.Tensor:
+        return cl / cd - self._cl_cd_ref        # airfoil_env_base.py:744-776
 
     def _action_to_control(self, action: torch.Tensor) -> torch.Tensor:
         raise NotImplementedError
@@ -313,47 +255,8 @@ class AirfoilEnvBase(CylinderEnvBase):
         ub.mul_(torch.where(self._free_slots[None, None, :], scale[:, None, None], torch.ones_like(scale)[:, None, None]))
 
     def _apply_action(self, action: torch.Tensor) -> None:
-        self._domain.blocks[TOP].boundary("-y").copy_(self._action_to_control(action.reshape(self._num_envs, self._n_jets)))
+        self._domain.blocks[TOP].boundary("-y").copy_(self._action_to_control(action))
         self._balance_boundary_fluxes()
-
-    def _step_impl(self, action: torch.Tensor):
-        target = action.reshape(self._num_envs, self._n_controls)
-        cds, cls = [], []
-        for k in range(self._n_sim_steps):
-            control = self._last_control + self._action_smoothing_alpha * (target - self._last_control)
-            self._last_control = control
-            if self._enable_actions:
-                self._apply_action(control)
-            self._before_sim_step(k)
-            self._sim.single_step()
-            self._after_sim_step()
-            cd, cl = self._get_drag_and_lift()
-            cds.append(cd); cls.append(cl)
-        obs = self._get_global_obs()
-        # mean over the sim steps as adds in step order (mean(0) of the stack picks its summation order per column: identical envs
-        # then differ in the last bit of drag / lift)
-        cd, cl = cds[0].clone(), cls[0].clone()
-        for k in range(1, len(cds)):
-            cd += cds[k]; cl += cls[k]
-        cd /= len(cds); cl /= len(cls)
-        return obs, cl / cd - self._cl_cd_ref, False, {"drag": cd, "lift": cl}
-
-    def _save_initial_domain(self, mode, idx: int, env: int = 0) -> None:
-        from ..simulation.domain_io import save_multiblock_domain
-
-        out_dir = self._get_domain_dir(idx)
-        out_dir.mkdir(parents=True, exist_ok=True)
-        save_multiblock_domain(self._domain, str(out_dir / mode.value), env=env, name="AirfoilDomain")
-
-    def get_velocity(self) -> torch.Tensor:
-        u = self._resampler(self._domain.velocity)                   # [B, d, (z,) y, x]
-        u[..., torch.as_tensor(self._airfoil_mask, device=u.device)] = 0.0
-        return u
-
-    def _diagnostic_to_view(self, cells: torch.Tensor) -> torch.Tensor:
-        v = self._resampler(cells)
-        v[..., torch.as_tensor(self._airfoil_mask, device=v.device)] = 0.0
-        return v
 
     def _frame_specs(self):
         """airfoil_env_base.py:38-45, 664-702: vorticity in the range of the Reynolds number, ``icefire``, y flipped (the reference
@@ -405,16 +308,14 @@ AIRFOIL_3D_DEFAULT_CONFIG = {
 }
 
 
-class AirfoilEnv3D(AirfoilEnvBase):
+class AirfoilEnv3D(SpanwiseAgentsMixin, AirfoilEnvBase):
     """``AirfoilEnv3D`` (airfoil_env_3d.py:50-593): the wing spans z in [-H/2, H/2] (periodic, ``res_z`` = 96 layers), the
-    three jets are cut into ``n_agents`` spanwise segments with one action triple each.  Observation layout, local windows
-    and the per-layer force bookkeeping are those of the 3-D cylinder env (same reference functions,
-    ``extract_global_3d_obs`` / ``transform_global_to_local_obs_3d``).
+    three jets are cut into ``n_agents`` spanwise segments with one action triple each; observations, agents and per-layer
+    forces are ``mesh_body.SpanwiseAgentsMixin``.
 
     ``init_from_2d``: the reference starts the 3-D flow from a published 2-D initial domain extruded over the span
     (:524-563); here the first half of the development steps is run on the 2-D mesh and extruded the same way."""
 
-    _supports_marl = True
     _n_sensors_per_agent: int = 1
     _res_z: int = 96
 
@@ -424,51 +325,26 @@ class AirfoilEnv3D(AirfoilEnvBase):
                  res_z: Optional[int] = None, **kw):
         if res_z is not None:
             self._res_z = int(res_z)
-        if n_agents < 1 or self._res_z % n_agents != 0:
-            raise ValueError("n_agents must be a positive integer that evenly divides circle_resolution_angular.")
-        if local_2d_obs and not use_marl:
-            raise ValueError("Local 2D observations are only supported in multi-agent mode.")
-        self._local_2d_obs = bool(local_2d_obs)
+        self._init_spanwise(n_agents, self._res_z, local_obs_window, use_marl, local_reward_weight, local_2d_obs)
         self._n_agents = int(n_agents)
-        self._local_obs_window = int(local_obs_window)
-        self._local_reward_weight = local_reward_weight
+        self._n_controls = self._n_agents * self._n_jets
         self._init_from_2d = bool(init_from_2d)
-        if local_2d_obs:
-            self._n_sensors_per_agent = 1
-            self._local_obs_window = 1
         kw.pop("ndims", None)
         super().__init__(ndims=3, reynolds_number=reynolds_number, adaptive_cfl=adaptive_cfl, step_length=step_length,
                          episode_length=episode_length, dt=dt, attack_angle_deg=attack_angle_deg, use_marl=use_marl, **kw)
-        self._n_controls = self._n_agents * self._n_jets
+
+    @property
+    def _n_segments(self) -> int:
+        return self._n_agents
+
+    def _span_pixel_map(self):
+        """The spanwise sensor planes sit on the pixels of the span D (airfoil_env_3d.py:303-344)."""
+        return self.D / 2, self.render_shape[1] / self.D
 
     # ---- spaces (airfoil_env_3d.py:205-275)
     def _get_action_space(self):
         shape = (self._n_jets,) if self._use_marl else (self._n_agents, self._n_jets)
         return spaces.Box(low=-1.0, high=1.0, shape=shape, dtype=np.float32)
-
-    def _get_observation_space(self):
-        n, spa = self._sensor_locations.shape[-1], self._n_sensors_per_agent
-        if self._use_marl and self._local_2d_obs:
-            v_shape, p_shape = (n, 2), (n,)
-        else:
-            lead = self._local_obs_window if self._use_marl else self._n_agents
-            v_shape, p_shape = (lead, spa, 3, n), (lead, spa, n)
-        return spaces.Dict({
-            "velocity": spaces.Box(low=-np.inf, high=np.inf, shape=v_shape, dtype=np.float32),
-            "pressure": spaces.Box(low=-np.inf, high=np.inf, shape=p_shape, dtype=np.float32),
-        })
-
-    @property
-    def n_agents(self) -> int:
-        return self._n_agents if self._use_marl else 1
-
-    @property
-    def _n_sensors_z(self) -> int:
-        return self._n_agents * self._n_sensors_per_agent
-
-    @property
-    def _nz_per_agent(self) -> int:
-        return self._res_z // self._n_agents
 
     @property
     def _cd_ref(self) -> float:
@@ -482,57 +358,16 @@ class AirfoilEnv3D(AirfoilEnvBase):
         s = self._metric_stat("abs_lift")
         return 0.0 if s is None else float(s.mean)
 
-    # ---- sensors (airfoil_env_3d.py:303-344): the kept 2-D pixels on n_sensors_z spanwise planes
-    def _get_sensor_locations(self) -> np.ndarray:
-        xy = super()._get_sensor_locations()                                    # [2, n] after masking
-        nz = self._n_sensors_z
-        z = np.linspace(-self.H / 2, self.H / 2, nz + 1, dtype=np.float32)[:-1] + np.float32(self.H / (2 * nz))
-        pz = np.round((z + np.float32(self.D / 2)) * np.float32(self.render_shape[1] / self.D)).astype(np.int64)
-        out = np.empty((3, nz, xy.shape[1]), np.int64)
-        out[0], out[1], out[2] = xy[0][None, :], xy[1][None, :], pz[:, None]
-        return out
-
-    # ---- observations (obs_extraction.py:60-205)
-    def _get_global_obs(self) -> Dict[str, torch.Tensor]:
-        dom = self._domain
-        B, nz, n = self._num_envs, self._n_sensors_z, self._sensor_locations.shape[-1]
-        u = self._sensors(dom.velocity).to(self._dtype)      # [B, 3, nz * n]
-        p = self._sensors(dom.pressure).to(self._dtype)
-        if self._local_2d_obs:
-            u = u[:, :2]
-        vd = u.shape[1]
-        u = u.permute(0, 2, 1).contiguous().reshape(B, nz, vd, n)              # the reference's view of [z, sensor, comp]
-        u = u.reshape(B, self._n_agents, self._n_sensors_per_agent, vd, n)
-        if self._local_2d_obs:
-            u = u.permute(0, 1, 2, 4, 3)
-        return {"velocity": u, "pressure": p.reshape(B, self._n_agents, self._n_sensors_per_agent, n)}
-
-    def _get_local_obs(self) -> Dict[str, torch.Tensor]:
-        g = self._get_global_obs()
-        W, na = self._local_obs_window, self._n_agents
-        seg = (torch.arange(na)[:, None] + torch.arange(W)[None, :] - W // 2) % na
-        out = {}
-        for k, v in g.items():
-            win = v[:, seg.to(v.device)]                                          # [B, agents, W, ...]
-            if self._local_2d_obs:
-                win = win.reshape(self._num_envs, na, *win.shape[4:])
-            out[k] = win
-        return out
-
     # ---- initial state
-    def _fill_initial_fields(self) -> None:
-        if getattr(self, "_developed", None) is None and self._init_from_2d:
-            self._develop_from_2d()
-        super()._fill_initial_fields()
-
-    def _develop_from_2d(self) -> None:
-        """Half of the development steps on the 2-D mesh, extruded over the span, as the start of the 3-D development."""
-        from ..simulation.multiblock import MultiBlockSimulation as Sim
-
+    def _develop(self) -> None:
+        """``init_from_2d``: half of the development steps on the 2-D mesh, extruded over the span, as the start of the 3-D
+        development."""
+        if not self._init_from_2d:
+            return super()._develop()
         n2d = self._initial_domain_steps // 2
         dom2 = build_domain(self._mesh2d, self._nu, batch=1, device=self._cuda_device)
         try:
-            sim2 = Sim(dom2, dt=self._dt, adaptive_CFL=self._adaptive_cfl, substeps="ADAPTIVE", corrector_steps=2,
+            sim2 = MultiBlockSimulation(dom2, dt=self._dt, adaptive_CFL=self._adaptive_cfl, substeps="ADAPTIVE", corrector_steps=2,
                        advection_tol=1e-6, pressure_tol=1e-7, advect_non_ortho_steps=2, pressure_non_ortho_steps=4,
                        pressure_use_BiCG=self._pressure_use_bicg, outflow=list(self._mesh2d.outflows),
                        outflow_velocity=(self.U_mean, 0.0, 0.0))
@@ -559,7 +394,6 @@ class AirfoilEnv3D(AirfoilEnvBase):
         self._sim.make_divergence_free()
         for _ in range(self._initial_domain_steps - n2d):
             self._sim.single_step()
-        self._developed = self._domain.Clone()
 
     # ---- actuation (airfoil_env_3d.py:366-407)
     def _additional_initialization(self) -> None:
@@ -580,32 +414,3 @@ class AirfoilEnv3D(AirfoilEnvBase):
         for i, (i0, i1) in enumerate(self._jet_locations_top):
             prof[:, :, :, i0:i1 + 1] *= v[:, None, :, i, None]
         return prof.reshape(B, 3, -1)
-
-    def _apply_action(self, action: torch.Tensor) -> None:
-        self._domain.blocks[TOP].boundary("-y").copy_(self._action_to_control(action))
-        self._balance_boundary_fluxes()
-
-    # ---- step (airfoil_env_3d.py:409-458)
-    def _step_impl(self, action: torch.Tensor):
-        obs, _, term, info = super()._step_impl(action)
-        all_cds, all_cls = info.pop("drag"), info.pop("lift")                    # [B, NZ]
-        cd, cl = all_cds.sum(-1) / self.D, all_cls.sum(-1) / self.D
-        return obs, cl / cd - self._cl_cd_ref, term, {"drag": cd, "lift": cl, "all_cds": all_cds, "all_cls": all_cls}
-
-    def _step_marl_impl(self, actions: torch.Tensor):
-        if self._local_reward_weight is None:
-            raise ValueError("local_reward_weight must be set for multi-agent step.")
-        _, global_reward, terminated, info = self._step_impl(actions)
-        local_obs = self._get_local_obs()
-        all_cds, all_cls = info.pop("all_cds"), info.pop("all_cls")
-        B, na = self._num_envs, self._n_agents
-        local_cd = all_cds.reshape(B, na, -1).sum(-1) / (self.D / na)
-        local_cl = all_cls.reshape(B, na, -1).sum(-1) / (self.D / na)
-        w = self._local_reward_weight
-        agent_rewards = w * (local_cl / local_cd - self._cl_cd_ref) + (1 - w) * global_reward[:, None]
-        info["global_reward"] = global_reward
-        return local_obs, agent_rewards, terminated, info
-
-    def render(self, *a, **kw) -> np.ndarray:
-        speed = torch.linalg.vector_norm(self.get_velocity()[0], dim=0)
-        return speed[speed.shape[0] // 2].detach().cpu().numpy()

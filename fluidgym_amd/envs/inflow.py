@@ -94,7 +94,7 @@ class InflowDisturbanceMixin:
             info["inflow"] = self._unbatch(self._inflow_signal.clone())
         return obs, reward, terminated, truncated, info
 
-    # ---- the description travels beside the last control (CylinderEnvBase._get_extra_state / _set_extra_state)
+    # ---- the description travels beside the last control (MeshBodyEnvBase._get_extra_state / _set_extra_state)
     def _inflow_state_dict(self) -> Optional[dict]:
         return None if self._inflow_spec is None else self._inflow_spec.state_dict()
 

@@ -170,7 +170,7 @@ class MeshResetMixin:
         obs = self._get_local_obs() if self._use_marl else self._get_global_obs()
         return self._unbatch(obs)
 
-    # ---- the counter: zeroed by a seeded reset; the env carries it in its extra state (CylinderEnvBase._get_extra_state)
+    # ---- the counter: zeroed by a seeded reset; the env carries it in its extra state (MeshBodyEnvBase._get_extra_state)
     def reset(self, seed: Optional[int] = None, randomize: Optional[bool] = None, per_env: bool = False):
         if seed is not None:
             self.mesh_reset_count[:] = 0

@@ -102,9 +102,9 @@ class _Lanes:
         return getattr(self.envs[0], name)
 
     def _check_solvers(self) -> None:
-        from .cylinder import CylinderEnvBase      # (cylinder and airfoil ids: the multi-block path, fg_mb_*)
+        from .mesh_body import MeshBodyEnvBase      # (cylinder and airfoil ids: the multi-block path, fg_mb_*)
 
-        if self._cuda and isinstance(self.envs[0], CylinderEnvBase):
+        if self._cuda and isinstance(self.envs[0], MeshBodyEnvBase):
             raise ValueError("lanes > 1 is for the single-block solver path: the multi-block cluster kernels need the whole GPU "
                              "co-resident (fluidgym_amd/envs/parallel_env.py, 'Lanes')")
 

@@ -256,3 +256,28 @@ def airfoil_spec(div=4, nu=1e-3, noise=0.1, balanced=False):
         k = -sum(v for key, v in fl.items() if key not in outflow) / sum(fl[key] for key in outflow)
         s.fixed = [(b, f, v * k if (b, f) in outflow else v) for b, f, v in s.fixed]
     return s
+
+
+class FakeRampDomain:
+    """Index ramps in place of the fields: with one-hot sensor rows the env's gather returns the flat pixel index of
+    every sensor, which is what the golden generator fed the reference's observation code."""
+
+    def __init__(self, rs):
+        import torch
+        P = rs[0] * rs[1] * rs[2]
+        self.velocity = torch.arange(3 * P, dtype=torch.float32).reshape(1, 3, P)
+        self.pressure = -torch.arange(P, dtype=torch.float32).reshape(1, P)
+
+
+def ramp_obs_env(env_id, **kw):
+    """A 3-D cylinder / airfoil env on the host whose domain is a ``FakeRampDomain`` and whose sensors are one-hot rows."""
+    import torch
+    import fluidgym_amd
+    from fluidgym_amd.simulation.resample_mb import SensorGather
+
+    env = fluidgym_amd.make(env_id, cuda_device=torch.device("cpu"), **kw)
+    rs = env.render_shape
+    env._domain = FakeRampDomain(rs)
+    px = env._sensor_locations.reshape(3, -1)
+    env._sensors = SensorGather(torch.as_tensor(px[0] + rs[0] * (px[1] + rs[1] * px[2]))[:, None], torch.ones(px.shape[1], 1))
+    return env

@@ -83,28 +83,10 @@ def test_3d_sensor_pixels_match_reference(res, n_jets):
     assert np.array_equal(env._sensor_locations, G[f"r{res}_3d_sensor_pixels"])
 
 
-class _FakeDomain:
-    """Index ramps in place of the fields: with one-hot sensor rows the env's gather returns the flat pixel index of
-    every sensor, which is what the golden generator fed the reference's observation code."""
-
-    def __init__(self, rs):
-        import torch
-        P = rs[0] * rs[1] * rs[2]
-        self.velocity = torch.arange(3 * P, dtype=torch.float32).reshape(1, 3, P)
-        self.pressure = -torch.arange(P, dtype=torch.float32).reshape(1, P)
-
-
 def _obs_env(use_marl):
-    import torch
-    import fluidgym_amd
+    from tests.helpers_mb import ramp_obs_env
 
-    env = fluidgym_amd.make("CylinderJet3D-easy-v0", cuda_device=torch.device("cpu"), resolution=8, n_jets=4, use_marl=use_marl)
-    rs = env.render_shape
-    env._domain = _FakeDomain(rs)
-    px = env._sensor_locations.reshape(3, -1)
-    from fluidgym_amd.simulation.resample_mb import SensorGather
-    env._sensors = SensorGather(torch.as_tensor(px[0] + rs[0] * (px[1] + rs[1] * px[2]))[:, None], torch.ones(px.shape[1], 1))
-    return env
+    return ramp_obs_env("CylinderJet3D-easy-v0", resolution=8, n_jets=4, use_marl=use_marl)
 
 
 def test_3d_global_observation_layout_matches_reference():

@@ -237,3 +237,39 @@ def test_replay_across_a_retry_of_the_velocity_sweeps():
     assert torch.equal(env._domain.velocity, u1) and torch.equal(env._domain.pressure, p1)
     assert torch.equal(r1[1], r2[1])
     env.close()
+
+
+def test_env_step_is_the_per_step_smoothing_and_the_ordered_mean_of_the_wall_coefficients():
+    """The env step (``mesh_body.MeshBodyEnvBase._step_impl``: the controls of all sim steps from the host recurrence, the wall forces
+    in one buffer) against the sequence driven by hand on a second env: ``c + alpha (target - c)`` on the device, ``_apply_action``,
+    ``_before_sim_step``, ``single_step``, ``_after_sim_step``, ``_get_drag_and_lift`` per sim step, their mean as adds in step order."""
+    kw = dict(num_envs=2, resolution_div=2, initial_domain_steps=6, randomize_initial_state=False)
+    action = torch.tensor([[0.8, -0.5, 0.3], [-0.2, 0.9, -0.6]], device="cuda")
+    env = fluidgym_amd.make("Airfoil2D-easy-v0", **kw)
+    env.reset(seed=0)
+    assert float(env._last_control.abs().max()) == 0.0
+    _, reward, _, _, info = env.step(action)
+    hand = fluidgym_amd.make("Airfoil2D-easy-v0", **kw)
+    hand.reset(seed=0)
+    n, alpha = hand._n_sim_steps, hand._action_smoothing_alpha
+    assert n == 5
+    c, cds, cls = torch.zeros_like(action), [], []
+    for k in range(n):
+        c = c + alpha * (action - c)
+        hand._apply_action(c)
+        hand._before_sim_step(k)
+        hand._sim.single_step()
+        hand._after_sim_step()
+        cd, cl = hand._get_drag_and_lift()
+        cds.append(cd), cls.append(cl)
+    assert torch.equal(env._last_control, c) and float(c.abs().min()) > 0
+    cd, cl = cds[0].clone(), cls[0].clone()
+    for k in range(1, n):
+        cd += cds[k]
+        cl += cls[k]
+    cd /= n
+    cl /= n
+    assert torch.equal(info["drag"], cd) and torch.equal(info["lift"], cl)
+    assert torch.equal(reward, cl / cd - env._cl_cd_ref)
+    assert torch.equal(env._domain.velocity, hand._domain.velocity) and torch.equal(env._domain.pressure, hand._domain.pressure)
+    env.close(), hand.close()
