@@ -385,6 +385,8 @@ SIGNATURES = {
                                    c_int32, c_float, c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_void_p]),
     "fg_plane_spectra": (c_int, [POINTER(c_void_p), POINTER(c_int64), c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_int32), c_int32,
                                  c_void_p, c_void_p, c_void_p]),
+    "fg_signal_spectra": (c_int, [POINTER(c_void_p), POINTER(c_int64), POINTER(c_int32), c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,
+                                  POINTER(c_int32), c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fg_plane_histogram": (c_int, [POINTER(c_void_p), POINTER(c_int64), c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_int32), c_int32,
                                    c_void_p, c_void_p, c_int32, POINTER(c_int32), c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "fg_coherence_litmus": (c_int, [c_int32, c_int32, c_int32, c_int32, POINTER(c_int64), POINTER(ctypes.c_double), c_void_p]),

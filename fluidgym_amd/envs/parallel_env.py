@@ -679,6 +679,16 @@ class ParallelFluidEnv:
     def stop_mesh_tracers(self):
         raise NotImplementedError("stop_mesh_tracers is not implemented for ParallelFluidEnv.")
 
+    def start_signal_spectra(self, *args, **kwargs):
+        raise NotImplementedError("start_signal_spectra is not implemented for ParallelFluidEnv.")
+
+    def stop_signal_spectra(self):
+        raise NotImplementedError("stop_signal_spectra is not implemented for ParallelFluidEnv.")
+
+    @property
+    def signal_spectra(self):
+        raise NotImplementedError("signal_spectra is not implemented for ParallelFluidEnv.")
+
     def get_surface_distribution(self, p_ref=0.0):
         raise NotImplementedError("get_surface_distribution is not implemented for ParallelFluidEnv.")
 

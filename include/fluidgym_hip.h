@@ -549,6 +549,36 @@ int fg_plane_moments(const fg_real* const* channels, const int64_t* batch_stride
 int fg_plane_timecorr(const fg_real* const* channels, const int64_t* batch_stride, int32_t K, int32_t batch, int32_t nz, int32_t ny,
                       int32_t nx, int32_t lags, int32_t n_slots, const int32_t* slot_lag, fg_real* base, double* base_ss, double* acc,
                       void* stream);
+/* ---- online Welch power and cross spectra of per-env signals (csrc/fg_signalspectra.hip; both libraries, handle-free) ------------
+ * One sample of SignalSpectra (simulation/signal_spectra.py) for a batch of envs in ONE launch; nothing returns to the host and the
+ * host decides nothing per env.
+ *   sources[i], batch_stride[i], widths[i]   HOST tables of n_sources = 1..8 entries, copied into the kernel arguments: source i is a
+ *                    DEVICE array of fg_real read in place, value c < widths[i] of env b at sources[i][b * batch_stride[i] + c].  The
+ *                    signals are the columns of the sources one after the other, S = sum widths = 1..64.
+ *   segment, noverlap   L, a power of two from 16 up to 4096 (fp32) / 2048 (fp64), and 0 <= noverlap < L; hop = L - noverlap.
+ *   detrend          per segment and signal: 0 none, 1 the mean, 2 the least-squares line (sums in fp64).
+ *   window [L]       DEVICE, fp64: made by the caller, so any window works.
+ *   pairs [n_pairs][2]   HOST table of n_pairs = 0..64 signal pairs (a, b), copied into the kernel arguments.
+ *   ring [batch][S][L]   DEVICE, fg_real: the last L samples of every signal; the sample lands at fill[b] % L.
+ *   fill [batch]     DEVICE, int64: samples since the env last (re)started, incremented here.  The caller zeroes the entries of the
+ *                    envs it restarts: their open segment is dropped, the accumulators stay.
+ *   power [batch][S][L/2+1], cross [batch][n_pairs][L/2+1][2], segments [batch] (int64)   DEVICE, zeroed by the caller before the first
+ *                    sample.  For every env with fill >= L and (fill - L) % hop == 0 after the append, the L ring values of each
+ *                    signal in time order are detrended, multiplied by the window, rounded to fg_real and transformed (a Stockham
+ *                    FFT in LDS); |X_s|^2 is ADDED to power, conj(X_a) X_b (re, im) to cross, 1 to segments, all evaluated in fp64
+ *                    with DC and Nyquist kept.  cross may be null when n_pairs is 0.
+ *   last [batch][S][L/2+1]   DEVICE or null: overwritten with |X_s|^2 of the segment just processed.
+ * One workgroup per env; every signal is transformed on its own, so its numbers are a function of its own L samples, the window and
+ * the detrend and of nothing else: not of batch, of the env's row, of the other signals or of which other envs had a segment due.  Every
+ * accumulator element has one writer; no floating-point atomics.  A non-finite value among the L samples of a signal makes that
+ * signal's power (from then on) and `last`, and the cross spectra of its pairs, NaN, and changes nothing else.  Asynchronous on
+ * `stream`.  FG_ERR_INVALID_ARG: a null pointer (cross and pairs only with n_pairs > 0; last may be null), n_sources outside 1..8, a
+ * width below 1 or S above 64, a batch stride below its width, n_pairs outside 0..64, a pair index outside [0, S), a non-positive
+ * batch, noverlap outside [0, segment), detrend outside 0..2.  FG_ERR_UNSUPPORTED: a segment that is no power of two, below 16, or
+ * whose twiddles and three work buffers of `segment` complex fg_real exceed 160 KB of LDS. */
+int fg_signal_spectra(const fg_real* const* sources, const int64_t* batch_stride, const int32_t* widths, int32_t n_sources, int32_t batch,
+                      int32_t segment, int32_t noverlap, int32_t detrend, const double* window, const int32_t* pairs, int32_t n_pairs,
+                      fg_real* ring, int64_t* fill, double* power, double* cross, int64_t* segments, double* last, void* stream);
 /* ---- online per-cell flow statistics of multi-block domains (csrc/fg_cellstats.hip; both libraries, handle-free) ----------------
  * One sample of CellMoments (simulation/cell_moments.py; the reference's WelfordOnlineParallel_Torch and
  * CovarianceOnlineParallel_Torch applied per block with dims = [0] in 2-D and [0, 2] in 3-D, online_statistics.py:31-266): for every
